@@ -16,8 +16,15 @@ collective on the data path; one barrier + MAX-over-ranks for timing).
     python bench.py --config c3              # the other BASELINE.json configurations at their per-GPU batch:
                                              #   c2 Blending N=4096 B=16 (default, the metric's workload) | c3 Merging N=4096 B=16
                                              #   c4 Blending N=8192 B=8 | c5 Blending N=16384 B=32
+    python bench.py --full                   # also the kernel-class profile, roofline figures and CPU baselines below
+    python bench.py --dump-outputs DIR       # after the timed steps: DIR/points.npy = the (shapes, points, 3) float32 clouds
+                                             # of the last timed trajectory (same arguments -> same inputs)
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times --steps trajectories and prints the headline line (metric, value, unit, ms_per_step, ...).
+Nothing else runs: no profiler is installed in the timed region and no step of the replayed loops is diverted to an eager probe.
+
+Extra objects on the JSON line, with --full only (the timed region then also runs every 50th replayed step eagerly and samples
+launches with HIP events, as the kernel-class profile needs):
   roofline       -- the kernel CLASS with the largest share of kernel time (live HIP-event sampling of every 32nd launch of
                     every C-ABI function inside the timed region, bdm_amd/profiling.py): achieved = algorithmic FLOPs (or
                     bytes) of its launches / their summed duration, against the peak that bounds it (dense 16-bit MFMA peak
@@ -156,6 +163,28 @@ CONFIGS = {  # BASELINE.json configs[1..4] at their per-GPU share (batch / 8 GPU
 }
 
 
+DUMP_MAX_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(path, out, total_shapes, rank, world, dist_backend):
+    """--dump-outputs: the final clouds of the last timed trajectory (what bdm_blending / bdm_merging hand their caller, as
+    points_padded()) -> path/points.npy, float32, all ranks' shapes in global order.  Above DUMP_MAX_BYTES a fixed seeded
+    sample of whole shapes (ascending global index) is written instead.  Collective: every rank calls it."""
+    import numpy as np
+    from bdm_amd.distributed import gather_clouds
+    local = out.float() if dist_backend in (None, "nccl") else out.float().cpu()   # gloo gathers host tensors
+    clouds = gather_clouds(local, total_shapes, rank, world).cpu()
+    if rank != 0:
+        return
+    per_shape = clouds[0].numel() * 4
+    if clouds.numel() * 4 > DUMP_MAX_BYTES:
+        keep = max(1, DUMP_MAX_BYTES // per_shape)
+        pick = torch.randperm(clouds.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        clouds = clouds[pick]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "points.npy"), clouds.numpy())
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without a torch.distributed.run environment: start the N workers ourselves (child processes, one
     rank per GPU over RCCL), BEFORE this process has touched a GPU, relay their output and exit with their status.  The reference
@@ -197,7 +226,11 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="shapes per GPU (default: the configuration's)")
     ap.add_argument("--points", type=int, default=None, help="points per shape (default: the configuration's)")
     ap.add_argument("--ddpm-steps", type=int, default=1000, help="ONLY for smoke runs; any value != 1000 marks the line invalid")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline (and its c1_full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also profile the timed region by kernel class and report roofline figures and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed trajectory's clouds to DIR/points.npy (float32)")
     args = ap.parse_args()
     conf = CONFIGS[args.config]
     custom = (args.batch is not None and args.batch != conf["batch"]) or (args.points is not None and args.points != conf["points"])
@@ -273,11 +306,13 @@ def main():
     for _ in range(args.warmup):
         trajectory()
 
-    model.eager_probe_every = 50  # replayed loops (launch tape, BDM_GRAPH=1): every 50th step runs eagerly so that single launches
-                                  # can be timed; the profiler counts each of its launches 50 times (profiling.PROBE_WEIGHT)
-    pvd_model.eager_probe_every = model.eager_probe_every   # (the prior's replayed loop likewise: pvd.Model._gen_samples_tape)
-    from bdm_amd.profiling import KernelClassProfiler
-    prof = KernelClassProfiler(every=4).install()
+    prof = None
+    if args.full:
+        model.eager_probe_every = 50  # replayed loops (launch tape, BDM_GRAPH=1): every 50th step runs eagerly so that single launches
+                                      # can be timed; the profiler counts each of its launches 50 times (profiling.PROBE_WEIGHT)
+        pvd_model.eager_probe_every = model.eager_probe_every   # (the prior's replayed loop likewise: pvd.Model._gen_samples_tape)
+        from bdm_amd.profiling import KernelClassProfiler
+        prof = KernelClassProfiler(every=4).install()
     barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -290,8 +325,11 @@ def main():
     elapsed = max_over_ranks(mine, device)
     per_rank_s = per_rank_values(own, device)           # after the timed region: which rank was the slow one, and by how much
     per_rank_numa = per_rank_values(float(-1 if affinity.get("numa_node") is None else affinity["numa_node"]), device)
-    prof.remove()
+    if prof is not None:
+        prof.remove()
     assert torch.isfinite(out).all()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, total_shapes, rank, world, dist_backend)
 
     if rank == 0:
         pc2_f, pvd_f, fuse_f = count_forwards(cfg.aux_run.milestones, cfg.aux_run.roll_step, merging=merging)
@@ -319,140 +357,141 @@ def main():
             line["invalid"] = "smoke / custom configuration: not one of BASELINE.json's workloads"
         elif args.config != "c2":
             line["note"] = "not the headline workload (the metric is quoted on C2); same trajectory definition at this configuration's size"
-        # occupied fraction of the sparse convolutions' rows on the final clouds (after the timed region), per level
-        from bdm_amd import functional as BF, ops as bops, profiling
-        # ... on the clouds the trajectory ENDS with and on clouds like the ones it STARTS with (centred Gaussian noise): the listed
-        # fraction of the grid shrinks as the cloud condenses, the mean of the two ends prices the kernels of the whole trajectory
-        ends = [out.transpose(1, 2).contiguous(), torch.randn(out.shape[0], 3, args.points, device=out.device)]
-        ends[1] = ends[1] - ends[1].mean(dim=2, keepdim=True)
-        acc_occ, acc_dil = {}, {}
-        for pts in ends:
-            for r_, n_ in ((32, args.points), (16, 1024), (8, 256), (8, 64)):
-                if pts.shape[2] > n_:
-                    pts = BF.furthest_point_sample(pts, n_)
-                bops.clear_plan_cache()
-                plan = bops.voxel_plan(pts, r_, dilate=2 if r_ in (16, 32) else 0)
-                acc_occ.setdefault(plan.n_max, []).append(float(plan.n_occ.float().mean()) / plan.n_max)
-                if getattr(plan, "d2_tiles", None) is not None:   # once- / twice-dilated fraction of the grid: what the list convolutions compute
-                    d1 = float(plan.tile_start[:, :, 1].max(dim=1).values.float().mean()) / r_ ** 3
-                    d2 = float(plan.d2_tiles[:, :, 1].max(dim=1).values.float().mean()) / r_ ** 3
-                    acc_dil.setdefault(r_, []).append((d1, d2))
-        for k, v in acc_occ.items():
-            profiling.OCCUPANCY[k] = sum(v) / len(v)
-        for k, v in acc_dil.items():
-            profiling.DILATED[k] = (sum(a for a, _ in v) / len(v), sum(b for _, b in v) / len(v))
-            line.setdefault("dilated_fraction_final_and_initial", {})[str(k)] = [[round(a, 4), round(b, 4)] for a, b in v]
-        rows, classes = prof.table()
-        if classes:
-            # dominant class of the MAIN stream: the furthest-point sampler runs concurrently on its own stream (a chain of M - 1
-            # dependent rounds on one CU per shape: neither a bandwidth nor a matrix kernel); it is listed in roofline_table
-            top = next((c for c in classes if c["class"] != "furthest point sampling"), classes[0])
-            top_rows = [r for r in rows if r["class"] == top["class"]]
-            head = top_rows[0]
-            traffic, traffic_commit = None, None
-            try:  # HBM bytes per launch of that kernel from the committed PMC pass (separate rocprofv3 --pmc runs)
-                pm_path = next(p for p in (os.path.join(ROOT, "profiles", f) for f in ("r06_pmc_traffic.json", "r05_pmc_traffic.json", "r04_pmc_traffic.json", "r03_pmc_traffic.json", "r02_pmc_traffic.json")) if os.path.exists(p))
-                pm = json.load(open(pm_path))
-                key = f"{head['function']}{tuple(head['shape'])}"
-                ent = (pm["kernels"].get(key) or pm["kernels"].get(key.replace("_h2_gn(", "_h2("))  # same kernels + GN epilogue
-                       or pm["kernels"].get(key.replace("_gather_gn(", "_gather(")))
-                if ent:
-                    traffic, traffic_commit = ent["bytes_per_launch"], pm.get("commit")
-            except (OSError, KeyError, ValueError, StopIteration):
-                pass
-            own = profiling.row_fraction(head) or (top["bound"], top["achieved"], top["peak"], top["unit"], top["frac"])
-            line["roofline"] = {"bound": own[0], "achieved": own[1], "peak": own[2], "unit": own[3],
-                                "frac": own[4], "traffic": traffic, "traffic_commit": traffic_commit,
-                                "kernel_class": top["class"], "class_frac": top["frac"], "share_of_kernel_time": top["share"],
-                                "kernel": f"{head['function']}{tuple(head['shape'])}", "avg_launch_us": head["avg_us"],
-                                "launches_timed": sum(r["sampled"] for r in top_rows),
-                                "launches_total": sum(r["calls"] for r in top_rows),
-                                "note": "`kernel` = the heaviest (function, shape) row of the class with the largest share of kernel time; achieved / "
-                                        "frac are THAT kernel's own (its algorithmic flops per launch / its average launch duration); class_frac = the "
-                                        "whole class (list convolutions priced by the matrix work they issue: listed voxels x 27 taps); durations: (HIP events on the launching stream around every 4th launch of the eagerly run steps: every "
-                                        "50th PC2 step of the replayed loop and the PVD / fusion forwards); the sampler stream's class is excluded; for the "
-                                        "fp16x3 convolution every fp32 product is 3 fp16 MFMA products: peak = 2500 TFLOP/s / 3"}
-            line["roofline"]["sparse_rows_occupied_fraction"] = {str(k): round(v, 4) for k, v in profiling.OCCUPANCY.items()}
-            line["roofline"]["dilated_fraction_of_grid"] = {str(k): [round(v[0], 4), round(v[1], 4)] for k, v in profiling.DILATED.items()}
-            line["roofline_table"] = [{k: (round(v, 4) if isinstance(v, float) else v) for k, v in c.items()} for c in classes]
-            def _own(r):
-                f = profiling.row_fraction(r)
-                return {} if f is None else {"bound": f[0], "frac": round(f[4], 4)}
-            line["roofline_rows"] = [dict({"kernel": f"{r['function']}{tuple(r['shape'])}", "class": r["class"], "share": round(r["share"], 4),
-                                           "avg_us": round(r["avg_us"], 2), "launches": r["calls"]}, **_own(r)) for r in rows[:12]]
-            # north-star target g1 (">= 40 % of the HBM roofline on the ball-query / gather kernel"): the first set-abstraction level
-            # (n points -> 1024 centres x 32 neighbours) from the in-run events of THIS run -- the query priced against the VALU issue rate
-            # that bounds it (profiling.VALU_TESTS_PEAK) and against HBM, the grouping gather (point-major repack + gather: one ABI call,
-            # two launches) against HBM, and the pair against HBM (SURVEY.md 8d byte formula of the pair)
-            def _row(fn, pred):
-                return next((r for r in rows if r["function"] == fn and pred(r["shape"])), None)
-            bq = _row("bdm_ball_query", lambda sh: sh[1] == args.points and sh[2] == 1024)
-            sg = _row("bdm_sa_group", lambda sh: sh[2] == args.points and sh[3] == 1024)
-            fused = _row("bdm_sa_mlp2_fused", lambda sh: sh[2] == args.points and sh[3] == 1024)
-            in_path = sg is not None
-            if bq and sg is None and fused is not None:
-                # round 4: the first level's grouped MLP re-gathers the neighbours' rows inside its three passes (bdm_sa_mlp2_fused), so
-                # the standalone gather no longer runs there.  It still ships (levels 1-3, and level 0 with BDM_SA_FUSED=0): timed here
-                # OUTSIDE the timed region on the level-0 shape, 20 launches between two events on the launching stream.
-                b_, c_, n_, m_, u_ = fused["shape"][:5]
-                gq = torch.Generator().manual_seed(1)
-                pts_ = out.transpose(1, 2).contiguous()   # the final clouds of this run (the neighbourhoods the path sees)
-                fts_ = torch.randn(b_, c_, n_, generator=gq).to(device)
-                cen_ = BF.furthest_point_sample(pts_, m_)
-                idx_ = BF.ball_query(cen_, pts_, 0.1, u_)
-                for _ in range(3):
-                    bops.sa_group(pts_, cen_, fts_, idx_)
-                e0_, e1_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0_.record()
-                for _ in range(20):
-                    bops.sa_group(pts_, cen_, fts_, idx_)
-                e1_.record()
-                torch.cuda.synchronize()
-                sg = {"shape": (b_, c_, n_, m_, u_), "avg_us": e0_.elapsed_time(e1_) / 20 * 1e3}
-            if bq and sg:
-                b_, c_, n_, m_, u_ = sg["shape"][:5]
-                gather_bytes = 4.0 * b_ * ((3 + c_) * n_ + m_ * u_ + (c_ + 3) * m_ * u_)
-                query_bytes = 4.0 * b_ * (3 * n_ + 3 * m_ + m_ * u_)
-                tests = 1.0 * b_ * m_ * n_
-                line["g1_ball_query_and_grouping"] = {
-                    "level": f"SA0: {b_} x {n_} points -> {m_} centres x {u_} neighbours, {c_} feature channels",
-                    "grouping_gather": {"kernel": f"bdm_sa_group{tuple(sg['shape'])}", "avg_us": round(sg["avg_us"], 2), "in_timed_path": in_path,
-                                        "algorithmic_mb": round(gather_bytes / 2 ** 20, 1), "achieved_gbs": round(gather_bytes / sg["avg_us"] / 1e3, 1),
-                                        "hbm_frac": round(gather_bytes / sg["avg_us"] / 1e3 / profiling.HBM_PEAK_GBS, 3)},
-                    "ball_query": {"kernel": f"bdm_ball_query{tuple(bq['shape'])}", "avg_us": round(bq["avg_us"], 2),
-                                   "distance_tests_g": round(tests / 1e9, 3), "achieved_gtests_s": round(tests / bq["avg_us"] / 1e3, 1),
-                                   "valu_frac": round(tests / bq["avg_us"] / 1e3 / profiling.VALU_TESTS_PEAK, 3),
-                                   "hbm_frac": round(query_bytes / bq["avg_us"] / 1e3 / profiling.HBM_PEAK_GBS, 4)},
-                    "pair_hbm_frac": round((gather_bytes + query_bytes - 4.0 * b_ * m_ * u_) / (sg["avg_us"] + bq["avg_us"]) / 1e3 / profiling.HBM_PEAK_GBS, 3),
-                    "note": "the query is bound by VALU issue (6.7 instructions per distance test), not by its 3 MB of traffic; the gather meets "
-                            "the 40 % target on its own, the pair cannot by memory tuning (DESIGN.md 7.6)"}
-                # the pair that DOES run inside the timed region: set-abstraction level 1 (n / 4 points -> n / 16 centres), ball query on the
-                # sampler's stream + the grouping gather from LDS-staged channel rows (round 6: sa_group_lds_kernel) on the main stream
-                bq1 = _row("bdm_ball_query", lambda sh: sh[1] == args.points // 4 and sh[2] == args.points // 16)
-                sg1 = _row("bdm_sa_group", lambda sh: sh[2] == args.points // 4 and sh[3] == args.points // 16)
-                if bq1 and sg1:
-                    b1_, c1_, n1_, m1_, u1_ = sg1["shape"][:5]
-                    pair_bytes = 4.0 * b1_ * (3 * n1_ + 3 * m1_ + c1_ * n1_ + m1_ * u1_ + (c1_ + 3) * m1_ * u1_)
-                    gather1 = 4.0 * b1_ * ((3 + c1_) * n1_ + m1_ * u1_ + (c1_ + 3) * m1_ * u1_)
-                    line["g1_ball_query_and_grouping"]["in_path_pair_level1"] = {
-                        "level": f"SA1: {b1_} x {n1_} points -> {m1_} centres x {u1_} neighbours, {c1_} feature channels", "in_timed_path": True,
-                        "ball_query_us": round(bq1["avg_us"], 2), "grouping_gather_us": round(sg1["avg_us"], 2),
-                        "algorithmic_mb": round(pair_bytes / 2 ** 20, 1),
-                        "gather_hbm_frac": round(gather1 / sg1["avg_us"] / 1e3 / profiling.HBM_PEAK_GBS, 3),
-                        "pair_hbm_frac": round(pair_bytes / (bq1["avg_us"] + sg1["avg_us"]) / 1e3 / profiling.HBM_PEAK_GBS, 3),
-                        "note": "both kernels timed by the in-run events of the timed region; why the pair stays below 0.40 at every level: "
-                                "profiles/r06_g1_query_and_gather.txt (the gather alone is write-bound at 0.41 - 0.49)"}
-                if fused is not None:
-                    fb_, fc_, fn_, fm_, fu_, f1_, f2_ = fused["shape"][:7]
-                    flops_ = 2.0 * fb_ * fm_ * fu_ * ((3 + fc_) * f1_ + f1_ * f2_)
-                    line["g1_ball_query_and_grouping"]["fused_grouped_mlp"] = {
-                        "kernel": f"bdm_sa_mlp2_fused{tuple(fused['shape'])}", "avg_us": round(fused["avg_us"], 2),
-                        "algorithmic_gflop": round(flops_ / 1e9, 2), "achieved_tflops": round(flops_ / fused["avg_us"] / 1e6, 1),
-                        "fp32_mfma_frac": round(flops_ / fused["avg_us"] / 1e6 / FP32_MFMA_PEAK_TFLOPS, 3),
-                        "bytes_not_moved_mb": round(4.0 * fb_ * fm_ * fu_ * (2 * (3 + fc_) + 2 * f1_ + f2_) / 2 ** 20, 1),
-                        "note": "grouping + 2-layer SharedMLP + max over neighbours in four launches (row repack + three recompute passes): the "
-                                "grouped tensor and both layer outputs (bytes_not_moved_mb: each written once and read once by the operator chain) "
-                                "never exist; replaces sa_group + two 1x1 GEMMs + the folded max at this level (204 -> 112 us at B = 16)"}
+        if args.full:  # kernel-class profile of the timed region, roofline figures (after the timed region)
+            # occupied fraction of the sparse convolutions' rows on the final clouds (after the timed region), per level
+            from bdm_amd import functional as BF, ops as bops, profiling
+            # ... on the clouds the trajectory ENDS with and on clouds like the ones it STARTS with (centred Gaussian noise): the listed
+            # fraction of the grid shrinks as the cloud condenses, the mean of the two ends prices the kernels of the whole trajectory
+            ends = [out.transpose(1, 2).contiguous(), torch.randn(out.shape[0], 3, args.points, device=out.device)]
+            ends[1] = ends[1] - ends[1].mean(dim=2, keepdim=True)
+            acc_occ, acc_dil = {}, {}
+            for pts in ends:
+                for r_, n_ in ((32, args.points), (16, 1024), (8, 256), (8, 64)):
+                    if pts.shape[2] > n_:
+                        pts = BF.furthest_point_sample(pts, n_)
+                    bops.clear_plan_cache()
+                    plan = bops.voxel_plan(pts, r_, dilate=2 if r_ in (16, 32) else 0)
+                    acc_occ.setdefault(plan.n_max, []).append(float(plan.n_occ.float().mean()) / plan.n_max)
+                    if getattr(plan, "d2_tiles", None) is not None:   # once- / twice-dilated fraction of the grid: what the list convolutions compute
+                        d1 = float(plan.tile_start[:, :, 1].max(dim=1).values.float().mean()) / r_ ** 3
+                        d2 = float(plan.d2_tiles[:, :, 1].max(dim=1).values.float().mean()) / r_ ** 3
+                        acc_dil.setdefault(r_, []).append((d1, d2))
+            for k, v in acc_occ.items():
+                profiling.OCCUPANCY[k] = sum(v) / len(v)
+            for k, v in acc_dil.items():
+                profiling.DILATED[k] = (sum(a for a, _ in v) / len(v), sum(b for _, b in v) / len(v))
+                line.setdefault("dilated_fraction_final_and_initial", {})[str(k)] = [[round(a, 4), round(b, 4)] for a, b in v]
+            rows, classes = prof.table()
+            if classes:
+                # dominant class of the MAIN stream: the furthest-point sampler runs concurrently on its own stream (a chain of M - 1
+                # dependent rounds on one CU per shape: neither a bandwidth nor a matrix kernel); it is listed in roofline_table
+                top = next((c for c in classes if c["class"] != "furthest point sampling"), classes[0])
+                top_rows = [r for r in rows if r["class"] == top["class"]]
+                head = top_rows[0]
+                traffic, traffic_commit = None, None
+                try:  # HBM bytes per launch of that kernel from the committed PMC pass (separate rocprofv3 --pmc runs)
+                    pm_path = next(p for p in (os.path.join(ROOT, "profiles", f) for f in ("r06_pmc_traffic.json", "r05_pmc_traffic.json", "r04_pmc_traffic.json", "r03_pmc_traffic.json", "r02_pmc_traffic.json")) if os.path.exists(p))
+                    pm = json.load(open(pm_path))
+                    key = f"{head['function']}{tuple(head['shape'])}"
+                    ent = (pm["kernels"].get(key) or pm["kernels"].get(key.replace("_h2_gn(", "_h2("))  # same kernels + GN epilogue
+                           or pm["kernels"].get(key.replace("_gather_gn(", "_gather(")))
+                    if ent:
+                        traffic, traffic_commit = ent["bytes_per_launch"], pm.get("commit")
+                except (OSError, KeyError, ValueError, StopIteration):
+                    pass
+                own = profiling.row_fraction(head) or (top["bound"], top["achieved"], top["peak"], top["unit"], top["frac"])
+                line["roofline"] = {"bound": own[0], "achieved": own[1], "peak": own[2], "unit": own[3],
+                                    "frac": own[4], "traffic": traffic, "traffic_commit": traffic_commit,
+                                    "kernel_class": top["class"], "class_frac": top["frac"], "share_of_kernel_time": top["share"],
+                                    "kernel": f"{head['function']}{tuple(head['shape'])}", "avg_launch_us": head["avg_us"],
+                                    "launches_timed": sum(r["sampled"] for r in top_rows),
+                                    "launches_total": sum(r["calls"] for r in top_rows),
+                                    "note": "`kernel` = the heaviest (function, shape) row of the class with the largest share of kernel time; achieved / "
+                                            "frac are THAT kernel's own (its algorithmic flops per launch / its average launch duration); class_frac = the "
+                                            "whole class (list convolutions priced by the matrix work they issue: listed voxels x 27 taps); durations: (HIP events on the launching stream around every 4th launch of the eagerly run steps: every "
+                                            "50th PC2 step of the replayed loop and the PVD / fusion forwards); the sampler stream's class is excluded; for the "
+                                            "fp16x3 convolution every fp32 product is 3 fp16 MFMA products: peak = 2500 TFLOP/s / 3"}
+                line["roofline"]["sparse_rows_occupied_fraction"] = {str(k): round(v, 4) for k, v in profiling.OCCUPANCY.items()}
+                line["roofline"]["dilated_fraction_of_grid"] = {str(k): [round(v[0], 4), round(v[1], 4)] for k, v in profiling.DILATED.items()}
+                line["roofline_table"] = [{k: (round(v, 4) if isinstance(v, float) else v) for k, v in c.items()} for c in classes]
+                def _own(r):
+                    f = profiling.row_fraction(r)
+                    return {} if f is None else {"bound": f[0], "frac": round(f[4], 4)}
+                line["roofline_rows"] = [dict({"kernel": f"{r['function']}{tuple(r['shape'])}", "class": r["class"], "share": round(r["share"], 4),
+                                               "avg_us": round(r["avg_us"], 2), "launches": r["calls"]}, **_own(r)) for r in rows[:12]]
+                # north-star target g1 (">= 40 % of the HBM roofline on the ball-query / gather kernel"): the first set-abstraction level
+                # (n points -> 1024 centres x 32 neighbours) from the in-run events of THIS run -- the query priced against the VALU issue rate
+                # that bounds it (profiling.VALU_TESTS_PEAK) and against HBM, the grouping gather (point-major repack + gather: one ABI call,
+                # two launches) against HBM, and the pair against HBM (SURVEY.md 8d byte formula of the pair)
+                def _row(fn, pred):
+                    return next((r for r in rows if r["function"] == fn and pred(r["shape"])), None)
+                bq = _row("bdm_ball_query", lambda sh: sh[1] == args.points and sh[2] == 1024)
+                sg = _row("bdm_sa_group", lambda sh: sh[2] == args.points and sh[3] == 1024)
+                fused = _row("bdm_sa_mlp2_fused", lambda sh: sh[2] == args.points and sh[3] == 1024)
+                in_path = sg is not None
+                if bq and sg is None and fused is not None:
+                    # round 4: the first level's grouped MLP re-gathers the neighbours' rows inside its three passes (bdm_sa_mlp2_fused), so
+                    # the standalone gather no longer runs there.  It still ships (levels 1-3, and level 0 with BDM_SA_FUSED=0): timed here
+                    # OUTSIDE the timed region on the level-0 shape, 20 launches between two events on the launching stream.
+                    b_, c_, n_, m_, u_ = fused["shape"][:5]
+                    gq = torch.Generator().manual_seed(1)
+                    pts_ = out.transpose(1, 2).contiguous()   # the final clouds of this run (the neighbourhoods the path sees)
+                    fts_ = torch.randn(b_, c_, n_, generator=gq).to(device)
+                    cen_ = BF.furthest_point_sample(pts_, m_)
+                    idx_ = BF.ball_query(cen_, pts_, 0.1, u_)
+                    for _ in range(3):
+                        bops.sa_group(pts_, cen_, fts_, idx_)
+                    e0_, e1_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0_.record()
+                    for _ in range(20):
+                        bops.sa_group(pts_, cen_, fts_, idx_)
+                    e1_.record()
+                    torch.cuda.synchronize()
+                    sg = {"shape": (b_, c_, n_, m_, u_), "avg_us": e0_.elapsed_time(e1_) / 20 * 1e3}
+                if bq and sg:
+                    b_, c_, n_, m_, u_ = sg["shape"][:5]
+                    gather_bytes = 4.0 * b_ * ((3 + c_) * n_ + m_ * u_ + (c_ + 3) * m_ * u_)
+                    query_bytes = 4.0 * b_ * (3 * n_ + 3 * m_ + m_ * u_)
+                    tests = 1.0 * b_ * m_ * n_
+                    line["g1_ball_query_and_grouping"] = {
+                        "level": f"SA0: {b_} x {n_} points -> {m_} centres x {u_} neighbours, {c_} feature channels",
+                        "grouping_gather": {"kernel": f"bdm_sa_group{tuple(sg['shape'])}", "avg_us": round(sg["avg_us"], 2), "in_timed_path": in_path,
+                                            "algorithmic_mb": round(gather_bytes / 2 ** 20, 1), "achieved_gbs": round(gather_bytes / sg["avg_us"] / 1e3, 1),
+                                            "hbm_frac": round(gather_bytes / sg["avg_us"] / 1e3 / profiling.HBM_PEAK_GBS, 3)},
+                        "ball_query": {"kernel": f"bdm_ball_query{tuple(bq['shape'])}", "avg_us": round(bq["avg_us"], 2),
+                                       "distance_tests_g": round(tests / 1e9, 3), "achieved_gtests_s": round(tests / bq["avg_us"] / 1e3, 1),
+                                       "valu_frac": round(tests / bq["avg_us"] / 1e3 / profiling.VALU_TESTS_PEAK, 3),
+                                       "hbm_frac": round(query_bytes / bq["avg_us"] / 1e3 / profiling.HBM_PEAK_GBS, 4)},
+                        "pair_hbm_frac": round((gather_bytes + query_bytes - 4.0 * b_ * m_ * u_) / (sg["avg_us"] + bq["avg_us"]) / 1e3 / profiling.HBM_PEAK_GBS, 3),
+                        "note": "the query is bound by VALU issue (6.7 instructions per distance test), not by its 3 MB of traffic; the gather meets "
+                                "the 40 % target on its own, the pair cannot by memory tuning (DESIGN.md 7.6)"}
+                    # the pair that DOES run inside the timed region: set-abstraction level 1 (n / 4 points -> n / 16 centres), ball query on the
+                    # sampler's stream + the grouping gather from LDS-staged channel rows (round 6: sa_group_lds_kernel) on the main stream
+                    bq1 = _row("bdm_ball_query", lambda sh: sh[1] == args.points // 4 and sh[2] == args.points // 16)
+                    sg1 = _row("bdm_sa_group", lambda sh: sh[2] == args.points // 4 and sh[3] == args.points // 16)
+                    if bq1 and sg1:
+                        b1_, c1_, n1_, m1_, u1_ = sg1["shape"][:5]
+                        pair_bytes = 4.0 * b1_ * (3 * n1_ + 3 * m1_ + c1_ * n1_ + m1_ * u1_ + (c1_ + 3) * m1_ * u1_)
+                        gather1 = 4.0 * b1_ * ((3 + c1_) * n1_ + m1_ * u1_ + (c1_ + 3) * m1_ * u1_)
+                        line["g1_ball_query_and_grouping"]["in_path_pair_level1"] = {
+                            "level": f"SA1: {b1_} x {n1_} points -> {m1_} centres x {u1_} neighbours, {c1_} feature channels", "in_timed_path": True,
+                            "ball_query_us": round(bq1["avg_us"], 2), "grouping_gather_us": round(sg1["avg_us"], 2),
+                            "algorithmic_mb": round(pair_bytes / 2 ** 20, 1),
+                            "gather_hbm_frac": round(gather1 / sg1["avg_us"] / 1e3 / profiling.HBM_PEAK_GBS, 3),
+                            "pair_hbm_frac": round(pair_bytes / (bq1["avg_us"] + sg1["avg_us"]) / 1e3 / profiling.HBM_PEAK_GBS, 3),
+                            "note": "both kernels timed by the in-run events of the timed region; why the pair stays below 0.40 at every level: "
+                                    "profiles/r06_g1_query_and_gather.txt (the gather alone is write-bound at 0.41 - 0.49)"}
+                    if fused is not None:
+                        fb_, fc_, fn_, fm_, fu_, f1_, f2_ = fused["shape"][:7]
+                        flops_ = 2.0 * fb_ * fm_ * fu_ * ((3 + fc_) * f1_ + f1_ * f2_)
+                        line["g1_ball_query_and_grouping"]["fused_grouped_mlp"] = {
+                            "kernel": f"bdm_sa_mlp2_fused{tuple(fused['shape'])}", "avg_us": round(fused["avg_us"], 2),
+                            "algorithmic_gflop": round(flops_ / 1e9, 2), "achieved_tflops": round(flops_ / fused["avg_us"] / 1e6, 1),
+                            "fp32_mfma_frac": round(flops_ / fused["avg_us"] / 1e6 / FP32_MFMA_PEAK_TFLOPS, 3),
+                            "bytes_not_moved_mb": round(4.0 * fb_ * fm_ * fu_ * (2 * (3 + fc_) + 2 * f1_ + f2_) / 2 ** 20, 1),
+                            "note": "grouping + 2-layer SharedMLP + max over neighbours in four launches (row repack + three recompute passes): the "
+                                    "grouped tensor and both layer outputs (bytes_not_moved_mb: each written once and read once by the operator chain) "
+                                    "never exist; replaces sa_group + two 1x1 GEMMs + the folded max at this level (204 -> 112 us at B = 16)"}
         # whole-path view: algorithmic FLOPs of SURVEY.md 8d per trajectory
         tflop_per_shape = (pc2_f * 103.64 + pvd_f * 81.22) / 1e3 if args.points == 4096 and not merging else None
         if tflop_per_shape:
@@ -460,7 +499,7 @@ def main():
             line["path_frac_of_fp32_mfma_peak"] = value * tflop_per_shape / (FP32_MFMA_PEAK_TFLOPS * world)
             # against the ceiling the split-precision kernels can reach: dense 16-bit MFMA peak / 3 products per fp32 product
             line["path_frac_of_fp16x3_peak"] = value * tflop_per_shape / (BF16_MFMA_PEAK_TFLOPS / 3 * world)
-        if not args.no_cpu_baseline and world == 1 and args.config == "c2":
+        if args.full and not args.no_cpu_baseline and world == 1 and args.config == "c2":
             line["cpu_baseline"] = cpu_baseline(model, pvd_model, args.points)
             line["speedup_vs_cpu_baseline"] = value / line["cpu_baseline"]["value"]
             line["cpu_baseline"]["c1_full"] = c1_full(device)  # the reference's CPU-runnable config, run in full on both sides
