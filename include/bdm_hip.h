@@ -742,6 +742,33 @@ int bdm_tape_failed_entry(const void *tape);
 /* test hook of the argument marshalling (no GPU work): writes its arguments, converted to double, to out16 (host memory) */
 int bdm_tape_echo(int a, long long b, float c, const void *d, unsigned int e, float f, int g, void *out16);
 
+/* ------------------------------------------------------------------------------------
+ * 6. Simple point denoiser (experiments/model/simple/simple_model.py:9-34, simple_model_utils.py:158-279;
+ *    also the first half of pvcnn/pvcnn_plus_plus.py:9-42), csrc/simple_point.hip
+ *    The state x is channel-first (b, 128, n).  Every kernel that writes x leaves the per-shape pooling partials of
+ *    what it wrote (max, sum, sum of squares per 128-point slice and channel) in `partials`
+ *    (bdm_simple_partials_bytes(b, n) bytes); bdm_simple_layer_prep turns them into the layer's per-shape state
+ *    (bdm_simple_state_elems(b) floats: max[128], std[128] (unbiased), their sum, their squared deviation from their
+ *    mean, and the 1024-wide pooled share of [W1; V]).  Fixed reduction orders: a shape's results do not depend on b.
+ * ---------------------------------------------------------------------------------- */
+size_t bdm_simple_partials_bytes(int b, int n);
+size_t bdm_simple_state_elems(int b);
+/* prepare_inputs + input_projection (simple_model_utils.py:250-273): y = W [x ; posenc(x[:, 0:3])] + batch_bias[b],
+ * x (b, c_in, n), freq (10) the PositionalEncoding buffer, w_packed (ceil(K/2), 4, 64) with K = c_in + 63: element
+ * [s][o][l] = W[32 o + (l & 31)][2 s + (l >> 5)] (zero beyond K); batch_bias (b, 128) = bias + W_t t_emb. */
+int bdm_simple_input_proj(int b, int n, int c_in, const float *x, const float *freq, const float *w_packed,
+                          const float *batch_bias, float *y, void *partials, void *stream);
+/* per-shape prologue of one layer from the partials of its input; w_ms (1024, 256) = [W1; V][:, 128:384] * gamma[128:384] */
+int bdm_simple_layer_prep(int b, int n, const void *partials, const float *w_ms, float *state, void *stream);
+/* y = x + W2 (silu(W1 LN(x_in)) * V LN(x_in)), x_in = [x, max, std] (simple_model.py:27-30); y must not alias x.
+ * w1_packed / wv_packed (16, 64, 64): [k][s][l] = W[32 k + (l & 31)][s + 64 (l >> 5)] * gamma[s + 64 (l >> 5)];
+ * w2_packed (16, 4, 16, 64): [k][o][r][l] = W2[32 o + (l & 31)][32 k + (r & 3) + 8 (r >> 2) + 4 (l >> 5)];
+ * vec (4, 512) = [d1, e1, dv, ev]: d = W[:, 128:384] gamma[128:384], e = W beta. */
+int bdm_simple_layer(int b, int n, const float *x, const float *state, const float *w1_packed, const float *wv_packed,
+                     const float *w2_packed, const float *vec, float *y, void *partials, void *stream);
+/* out = a + b elementwise over n floats (PVCNN++'s residual x + PVCNN(x), pvcnn_plus_plus.py:40); out may alias a or b */
+int bdm_simple_add(long long n, const float *a, const float *b, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
