@@ -27,10 +27,20 @@ def filled(model, seed):
 
 
 def posenc(v, freq):
+    """The argument f * v is formed in fp32, as the reference module forms it, whatever the dtype of v: its fp32 rounding (up to
+    half an ulp of 512 |v| rad) belongs to the model.  sin / cos are then taken in v's dtype."""
     pe = [v]
     for f in freq:
-        pe += [torch.sin(f * v), torch.cos(f * v)]
+        a = (f.float() * v.float()).to(v.dtype)
+        pe += [torch.sin(a), torch.cos(a)]
     return torch.cat(pe, dim=-1)
+
+
+def embedf(sd, pre, t, dim):
+    """ref_net.embedf with the sinusoidal embedding (fp32, as the reference forms it) cast to the weights' dtype."""
+    w0 = sd[pre + "0.weight"]
+    h = F.linear(ref_net.timestep_embedding(t, dim).to(w0.dtype), w0, sd[pre + "0.bias"])
+    return F.linear(F.leaky_relu(h, 0.1), sd[pre + "2.weight"], sd[pre + "2.bias"])
 
 
 def feed_forward(sd, pre, x_in):
@@ -48,7 +58,7 @@ def layer(sd, pre, x):
 
 
 def input_projection(sd, pre, inputs, t, embed_dim=E):
-    temb = ref_net.embedf(sd, pre + "timestep_projection.", t, embed_dim)[:, None, :].expand(-1, inputs.shape[-1], -1)
+    temb = embedf(sd, pre + "timestep_projection.", t, embed_dim)[:, None, :].expand(-1, inputs.shape[-1], -1)
     x = inputs.transpose(-2, -1)
     x = torch.cat([x, posenc(x[:, :, :3], sd[pre + "positional_encoding.freq_bands"]), temb], dim=2)
     return F.linear(x, sd[pre + "input_projection.weight"], sd[pre + "input_projection.bias"])
@@ -66,8 +76,13 @@ def simple_forward(sd, inputs, t, pre="", num_layers=6, states=None):
     return F.linear(x, sd[pre + "output_projection.weight"], sd[pre + "output_projection.bias"]).transpose(-2, -1)
 
 
-def pvcnnpp_forward(sd, inputs, t, pre=""):
-    x = simple_forward(sd, inputs, t, pre + "simple_point_model.", num_layers=3)
+def pvcnnpp_forward(sd, inputs, t, pre="", sd64=None):
+    """sd64 (the same weights in float64): the simple-model half in float64 on inputs.double(), rounded to fp32 before the
+    PVCNN half, which runs on the fp32 oracle operators."""
+    if sd64 is None:
+        x = simple_forward(sd, inputs, t, pre + "simple_point_model.", num_layers=3)
+    else:
+        x = simple_forward(sd64, inputs.double(), t, pre + "simple_point_model.", num_layers=3).float()
     x = x + ref_net.pvcnn_forward(sd, x, t, prefix=pre + "pvcnn.")
     p = pre + "output_projection."
     h = ref_net.shared_mlp(sd, p + "0.", x)

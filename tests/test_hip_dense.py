@@ -304,6 +304,68 @@ def test_pvconv_tail_and_sa_group(ops, oracle_ops):
     assert torch.equal(ops.sa_group(pts.cuda(), ctr.cuda(), big.cuda()[:, 20:279], nb.cuda()).cpu(), ref)
 
 
+def _sa_group_case(oracle_ops, B, n, m, u, seed):
+    """Points, FPS centres and ball-query neighbour lists (fill repeats included) from the oracle."""
+    g = torch.Generator().manual_seed(seed)
+    pts = torch.randn(B, 3, n, generator=g) * 0.3
+    ctr = oracle_ops.gather_features_forward(pts, oracle_ops.furthest_point_sampling(pts, m))
+    nb = oracle_ops.ball_query(ctr, pts, 0.2, u)
+    return g, pts, ctr, nb
+
+
+def _sa_group_ref(oracle_ops, pts, ctr, f, nb):
+    xyz = oracle_ops.grouping_forward(pts, nb) - ctr.unsqueeze(-1)
+    return xyz if f.shape[1] == 0 else torch.cat([xyz, oracle_ops.grouping_forward(f.contiguous(), nb)], 1)
+
+
+# bdm_sa_group's dispatch (dense_ops.hip, bdm_sa_group): a workspace -> point-major repack; else 256 <= n <= 8192 -> LDS-staged,
+# with LDS-DMA when n % 256 == 0 and the rows are 16-byte aligned; else the plain one-load-per-element kernel.  m * u above
+# SAG_EB = 4096 spreads the elements over several LDS workgroups, the last one partial unless m * u % 4096 == 0.
+@pytest.mark.parametrize("n,m,u,path", [(64, 50, 32, "plain_small"), (255, 200, 32, "plain_below_lds"), (256, 200, 32, "lds_dma"),
+                                        (1000, 300, 32, "lds_no_dma"), (1024, 300, 32, "lds_dma"), (4096, 1024, 32, "lds_dma_8_blocks"),
+                                        (8192, 300, 32, "lds_dma_at_limit"), (8448, 300, 32, "plain_above_lds")])
+def test_sa_group_every_dispatch_path(ops, oracle_ops, n, m, u, path):
+    """Bit for bit against cat[grouping(coords) - centres, grouping(features)] (a gather and one fp32 subtraction), c in
+    {0, 1, 11, 64}, with and without the point-major repack."""
+    B = 2
+    g, pts, ctr, nb = _sa_group_case(oracle_ops, B, n, m, u, seed=n + m)
+    for c in (0, 1, 11, 64):
+        f = torch.randn(B, c, n, generator=g)
+        ref = _sa_group_ref(oracle_ops, pts, ctr, f, nb)
+        for point_major in (False, True):
+            got = ops.sa_group(pts.cuda(), ctr.cuda(), f.cuda(), nb.cuda(), point_major=point_major).cpu()
+            assert torch.equal(got, ref), (path, c, point_major)
+
+
+@pytest.mark.parametrize("layout", ["features_off_by_one_float", "coords_off_by_one_float", "aligned_channel_slice"])
+def test_sa_group_views(ops, oracle_ops, layout):
+    """n = 1024 (LDS-staged): a feature base one float off a 16-byte boundary with ld_f % 4 == 0, or misaligned coords, turn the
+    LDS-DMA off; a channel slice of a wider buffer at 16-byte-aligned strides keeps it, with bs_f != c * n."""
+    B, n, m, u, c = 2, 1024, 300, 32, 11
+    g, pts, ctr, nb = _sa_group_case(oracle_ops, B, n, m, u, seed=7)
+    f = torch.randn(B, c, n, generator=g)
+    pts_d, f_d = pts.cuda(), f.cuda()
+    if layout == "features_off_by_one_float":
+        buf = torch.zeros(B * c * n + 4, device="cuda")
+        f_d = buf[1:1 + B * c * n].view(B, c, n)
+        f_d.copy_(f)
+        assert f_d.data_ptr() % 16 == 4 and f_d.is_contiguous()
+    elif layout == "coords_off_by_one_float":
+        buf = torch.zeros(B * 3 * n + 4, device="cuda")
+        pts_d = buf[1:1 + B * 3 * n].view(B, 3, n)
+        pts_d.copy_(pts)
+        assert pts_d.data_ptr() % 16 == 4 and pts_d.is_contiguous()
+    else:
+        wide = torch.zeros(B, c + 13, n, device="cuda")
+        f_d = wide[:, 8:8 + c]
+        f_d.copy_(f)
+        assert f_d.data_ptr() % 16 == 0 and f_d.stride(0) != c * n
+    ref = _sa_group_ref(oracle_ops, pts, ctr, f, nb)
+    for point_major in (False, True):
+        got = ops.sa_group(pts_d, ctr.cuda(), f_d, nb.cuda(), point_major=point_major).cpu()
+        assert torch.equal(got, ref), (layout, point_major)
+
+
 @experimental
 @pytest.mark.parametrize("cin,cout,r,npts", [(35, 32, 32, 4096), (64, 64, 32, 4096), (128, 64, 16, 1024), (256, 256, 8, 64),
                                              (192, 128, 8, 256), (16, 8, 32, 50)])
