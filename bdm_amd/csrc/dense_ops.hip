@@ -496,6 +496,7 @@ __global__ __launch_bounds__(256) void pw_skinny_kernel(int M, int K, int N, con
 // layout only when this returns 0 -- see bdm_pointwise_conv_gn)
 static int pw_skinny_max_n() { return 64; }  // widest shape (columns) that takes the skinny kernel (wider measured slower)
 static bool pw_skinny_shape(int k, int n) { return n <= pw_skinny_max_n() && k >= 128; }
+static int pw_skinny_nb(int n) { return n <= 32 ? 1 : 2; }  // 32-column blocks per workgroup of the skinny kernel (its NB)
 
 // workgroup count below which the long-K shapes take the 64-deep K chunk
 static int pw_deep_limit() { return 1024; }
@@ -557,7 +558,7 @@ extern "C" int bdm_pointwise_conv(int b, int m, int k, int n, const float *w, in
               "pointwise_conv: one operand spans more than 2^31 elements");
   if (b == 0 || n == 0) return BDM_OK;
   if (pw_skinny_shape(k, n)) {
-    if (n <= 32)
+    if (pw_skinny_nb(n) == 1)
       hipLaunchKernelGGL((pw_skinny_kernel<1, false>), dim3(cdiv(m, 32), b, 1), dim3(256), 0, (hipStream_t)stream, m, k, n, w, ldw, x, bs_x,
                          ld_x, bias, batch_bias, ld_bb, residual, bs_r, ld_r, y, bs_y, ld_y, act, slope, PwGn{});
     else
@@ -568,6 +569,18 @@ extern "C" int bdm_pointwise_conv(int b, int m, int k, int n, const float *w, in
   pw_dispatch<false>(b, m, k, n, w, ldw, x, bs_x, ld_x, bias, batch_bias, ld_bb, residual, bs_r, ld_r, y, bs_y, ld_y, act, slope,
                      PwGn{}, (hipStream_t)stream);
   return launch_status("pointwise_conv");
+}
+
+// which kernel a shape takes (host only): 1 / 2 = pw_skinny_kernel<NB>, 0 = pw_gemm_kernel<*mi, *ni, false, *bk> -- the very
+// pw_skinny_shape / pw_skinny_nb / pw_tile the launches above call, so a test can pin the variant it means to reach
+extern "C" int bdm_pointwise_conv_variant(int b, int m, int k, int n, int *mi, int *ni, int *bk) {
+  int t[3] = {0, 0, 0};
+  const int nb = pw_skinny_shape(k, n) ? pw_skinny_nb(n) : 0;
+  if (nb == 0) pw_tile(b, m, k, n, &t[0], &t[1], &t[2]);
+  if (mi) *mi = t[0];
+  if (ni) *ni = t[1];
+  if (bk) *bk = t[2];
+  return nb;
 }
 
 // slices per (shape, group) the GroupNorm-folded convolution below writes for an (m x n) output in `groups` groups
@@ -615,8 +628,8 @@ static int pointwise_conv_gn_impl(int b, int m, int k, int n, const float *w, in
 #define SK_LAUNCH(NB, FOLD)                                                                                                       \
     hipLaunchKernelGGL((pw_skinny_kernel<NB, FOLD>), dim3(cdiv(m, 32), b, cdiv(n, 32 * NB)), dim3(256), 0, (hipStream_t)stream, m, k, n, w, ldw, x, bs_x, \
                        ld_x, bias, batch_bias, ld_bb, (const float *)nullptr, 0ll, 0, y, bs_y, ld_y, 0, 0.f, gn)
-    if (in_partial != nullptr) { if (n <= 32) SK_LAUNCH(1, true); else SK_LAUNCH(2, true); }
-    else { if (n <= 32) SK_LAUNCH(1, false); else SK_LAUNCH(2, false); }
+    if (in_partial != nullptr) { if (pw_skinny_nb(n) == 1) SK_LAUNCH(1, true); else SK_LAUNCH(2, true); }
+    else { if (pw_skinny_nb(n) == 1) SK_LAUNCH(1, false); else SK_LAUNCH(2, false); }
 #undef SK_LAUNCH
     return launch_status("pointwise_conv_gn");
   }

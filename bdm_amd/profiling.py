@@ -209,7 +209,7 @@ class _Proxy:
 
     def __getattr__(self, name):
         fn = getattr(self._h, name)
-        host_only = (not name.startswith("bdm_") or name.endswith("_bytes") or name.endswith("_elems") or name.endswith("_slices")
+        host_only = (not name.startswith("bdm_") or name.endswith("_bytes") or name.endswith("_elems") or name.endswith("_slices") or name.endswith("_variant")
                      or name in ("bdm_last_error", "bdm_abi_version") or name.startswith("bdm_tape_"))
         if host_only:
             return fn

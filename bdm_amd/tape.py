@@ -36,7 +36,7 @@ _active = None  # the LaunchTape being recorded (None: not recording)
 
 def _host_only(name):
     # (bdm_tape_*: the executor's own management calls -- e.g. another tape's __del__ running during a recording -- are never steps)
-    return (not name.startswith("bdm_") or name.endswith("_bytes") or name.endswith("_elems") or name.endswith("_slices")
+    return (not name.startswith("bdm_") or name.endswith("_bytes") or name.endswith("_elems") or name.endswith("_slices") or name.endswith("_variant")
             or name.startswith("bdm_tape_") or name in ("bdm_last_error", "bdm_abi_version"))
 
 

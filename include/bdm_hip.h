@@ -137,6 +137,11 @@ int bdm_pointwise_conv(int b, int m, int k, int n, const float *w, int ldw, cons
                        long long bs_x, int ld_x, const float *bias, const float *batch_bias,
                        int ld_bb, const float *residual, long long bs_r, int ld_r, float *y,
                        long long bs_y, int ld_y, int act, float slope, void *stream);
+/* Host only: the kernel the 1x1 convolutions (bdm_pointwise_conv, bdm_pointwise_conv_gn*) launch for this shape -- what the launch
+ * path itself decides, not a restatement.  Returns 0: the general kernel, *mi / *ni / *bk receive its tile (32 mi rows x 128 ni
+ * columns per workgroup, K chunk bk); 1 or 2: the skinny K-split kernel with that many 32-column blocks (*mi = *ni = *bk = 0).
+ * The out pointers are HOST pointers and may be NULL.  The choice depends on (b, m, k, n) only. */
+int bdm_pointwise_conv_variant(int b, int m, int k, int n, int *mi, int *ni, int *bk);
 
 /* nn.GroupNorm(groups, c) over (b, c, l) with optional residual added first and optional Swish
  * (shared_mlp.py:27-29; pvconv.py:78-86; Attention: norm(h + x) then Swish, pvconv.py:59-61).
