@@ -13,7 +13,8 @@
 //                instead of overflowing to inf)
 // Below the normal range an operand keeps an ABSOLUTE error <= 2^-25 in scaled units: 2^-25 / act_scale for
 // activations, 2^-35 max|w[co]| for weights -- under the fp32 resolution of any sum those operands take part in.
-// Measured <= 3e-7 relative L2 vs fp64 (tests/test_hip_dense.py), the same as the fp32-input MFMA kernel.
+// Measured <= 3e-7 relative L2 vs fp64 (tests/test_hip_dense.py), the same as the fp32-input MFMA kernel; every tile, elementwise
+// against float64 with the bound derived from the argument above: tests/test_hip_conv3d_h2.py.
 //
 // Layouts ("H2"): activations (B, ceil(C/8), 2, r^3, 8) fp16; weights [ceil(Cin/8)][14 tap pairs][2][2][Cout][8] fp16.
 // Geometry, staging and tap addressing are those of conv3d_s3.hip.
@@ -326,19 +327,12 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW / 4,
   }
 }
 
-static int conv3d_h2_launch(int b, int cin, int cout, int r, const void *x_h2, float x_inv_scale, const void *packed_w,
-                            const float *inv_scale, const float *bias, float *y, int gn_cg, double *gn_partial,
-                            int *slices_out, void *stream) {
-  BDM_REQUIRE(b >= 0 && cin >= 1 && cout >= 1 && inv_scale != nullptr, "conv3d_h2: bad arguments");
-  if (r != 8 && r != 16 && r != 32) {
-    set_error("conv3d_h2: resolution %d unsupported (8, 16, 32)", r);
-    return BDM_ERR_UNSUPPORTED;
-  }
-  if (b == 0) return BDM_OK;
-  const int c8 = (cin + 7) / 8;
-  // tile = TX x TY grid rows x R cells = NT * NW blocks of 16 voxels x 32 * mi output channels; 8 waves (two per SIMD) keep the
-  // matrix pipe fed while the other wave of the SIMD waits on LDS (round 2 measured 4 waves with twice the tile per wave: 2-15 % slower)
-  int tx, ty, mi;
+// The tile of a launch: conv3d_h2q_kernel<mt, nt, r, tx, ty, nw>.  tile = TX x TY grid rows x R cells = NT * NW blocks of 16 voxels x
+// 16 * mt output channels; 8 waves (two per SIMD) keep the matrix pipe fed while the other wave of the SIMD waits on LDS (round 2
+// measured 4 waves with twice the tile per wave: 2-15 % slower).  Depends on (b, cout, r) only; false: resolution unsupported.
+struct H2Tile { int mt, nt, tx, ty, nw; };
+static bool h2_tile(int b, int cout, int r, H2Tile *t) {
+  if (r != 8 && r != 16 && r != 32) return false;
   // 8^3 grids: 128-voxel tiles with 4 waves double the workgroup count; they win when the 256-voxel tiling cannot fill the chip
   // (128 -> 128 at B = 16: 40.6 -> 30.4 us) and lose when it can (256 -> 256: 96 -> 114 us).
   const bool r8_small = r == 8 && (long long)b * 2 * cdiv(cout, 32) < 256;
@@ -355,10 +349,42 @@ static int conv3d_h2_launch(int b, int cin, int cout, int r, const void *x_h2, f
   // 16^3 64 channels B = 8 66.7 / 26.6, B = 16 71.7 / 50.2; 32^3 64 channels B = 2 75.4 / 46.2, B = 4 84.2 / 89.2).  It was 128: the
   // half-filled chip of 128 big workgroups lost 30 - 60 % (C4's 16^3 levels, C2's 64-channel 16^3 layer).
   const bool small = r != 8 && cout > 32 && big_wgs < 256;
-  if (r == 32) { tx = 2; ty = 8; }
-  else if (r == 16) { tx = small ? 1 : 2; ty = 16; }
-  else { tx = r8_tiny ? 1 : (r8_small ? 2 : 4); ty = 8; }
-  mi = (cout > 32 && r != 8 && !small) ? 2 : 1;
+  const bool wide = cout > 32 && r != 8 && !small;   // 64 output channels per workgroup
+  if (r == 32) *t = wide ? H2Tile{4, 4, 2, 8, 8} : H2Tile{2, 4, 2, 8, 8};
+  else if (r == 16) *t = small ? H2Tile{2, 2, 1, 16, 8} : (wide ? H2Tile{4, 4, 2, 16, 8} : H2Tile{2, 4, 2, 16, 8});
+  else *t = r8_tiny ? H2Tile{2, 1, 1, 8, 4} : (r8_small ? H2Tile{2, 2, 2, 8, 4} : H2Tile{2, 2, 4, 8, 8});
+  return true;
+}
+
+// which instantiation a shape takes (host only): the very h2_tile the launch below calls, so a test can pin the variant it means to reach
+extern "C" int bdm_conv3d_h2_variant(int b, int cin, int cout, int r, int *mt, int *nt, int *tx, int *ty, int *nw) {
+  (void)cin;
+  H2Tile t = {0, 0, 0, 0, 0};
+  const bool ok = h2_tile(b, cout, r, &t);
+  if (mt) *mt = t.mt;
+  if (nt) *nt = t.nt;
+  if (tx) *tx = t.tx;
+  if (ty) *ty = t.ty;
+  if (nw) *nw = t.nw;
+  if (!ok) {
+    set_error("conv3d_h2: resolution %d unsupported (8, 16, 32)", r);
+    return BDM_ERR_UNSUPPORTED;
+  }
+  return BDM_OK;
+}
+
+static int conv3d_h2_launch(int b, int cin, int cout, int r, const void *x_h2, float x_inv_scale, const void *packed_w,
+                            const float *inv_scale, const float *bias, float *y, int gn_cg, double *gn_partial,
+                            int *slices_out, void *stream) {
+  BDM_REQUIRE(b >= 0 && cin >= 1 && cout >= 1 && inv_scale != nullptr, "conv3d_h2: bad arguments");
+  H2Tile t;
+  if (!h2_tile(b, cout, r, &t)) {
+    set_error("conv3d_h2: resolution %d unsupported (8, 16, 32)", r);
+    return BDM_ERR_UNSUPPORTED;
+  }
+  if (b == 0) return BDM_OK;
+  const int c8 = (cin + 7) / 8;
+  const int tx = t.tx, ty = t.ty, mi = t.mt / 2;   // 32 * mi output channels per workgroup
   const size_t smem = 16 * ((size_t)2 * (tx + 2) * (ty + 2) * (r + 2) + (size_t)H2_PAIRS * 4 * 32 * mi);
   dim3 grid((r / tx) * (r / ty), cdiv(cout, 32 * mi), b);
   hipStream_t s = (hipStream_t)stream;
@@ -368,24 +394,25 @@ static int conv3d_h2_launch(int b, int cin, int cout, int r, const void *x_h2, f
     // canonical slices (independent of the tile): 16^3 and 8^3 one per x-plane, 32^3 one per 2 x 8 tile
     if (slices_out) *slices_out = r == 16 ? 16 : (r == 8 ? 8 : (int)grid.x);
   }
-#define H2Q_LAUNCH(MT, NT, R, TX, TY, NW)                                                                       \
-  do {                                                                                                          \
-    BDM_ALLOW_LDS((conv3d_h2q_kernel<MT, NT, R, TX, TY, NW>), smem);                                            \
-    hipLaunchKernelGGL((conv3d_h2q_kernel<MT, NT, R, TX, TY, NW>), grid, dim3(NW * 64), smem, s, c8, cout,      \
-                       (const float4 *)x_h2, (const float4 *)packed_w, inv_scale, x_inv_scale, bias, y, gn_cg,  \
-                       gn_partial);                                                                             \
-  } while (0)
-  if (r == 32) { if (mi == 2) H2Q_LAUNCH(4, 4, 32, 2, 8, 8); else H2Q_LAUNCH(2, 4, 32, 2, 8, 8); }
-  else if (r == 16) {
-    if (small) H2Q_LAUNCH(2, 2, 16, 1, 16, 8);
-    else if (mi == 2) H2Q_LAUNCH(4, 4, 16, 2, 16, 8);
-    else H2Q_LAUNCH(2, 4, 16, 2, 16, 8);
-  } else {
-    if (r8_tiny) H2Q_LAUNCH(2, 1, 8, 1, 8, 4);
-    else if (r8_small) H2Q_LAUNCH(2, 2, 8, 2, 8, 4);
-    else H2Q_LAUNCH(2, 2, 8, 4, 8, 8);
+  bool launched = false;
+#define H2Q_LAUNCH(MT, NT, R, TX, TY, NW)                                                                         \
+  if (!launched && r == R && t.mt == MT && t.nt == NT && t.tx == TX && t.ty == TY && t.nw == NW) {                \
+    BDM_ALLOW_LDS((conv3d_h2q_kernel<MT, NT, R, TX, TY, NW>), smem);                                              \
+    hipLaunchKernelGGL((conv3d_h2q_kernel<MT, NT, R, TX, TY, NW>), grid, dim3(NW * 64), smem, s, c8, cout,        \
+                       (const float4 *)x_h2, (const float4 *)packed_w, inv_scale, x_inv_scale, bias, y, gn_cg,    \
+                       gn_partial);                                                                               \
+    launched = true;                                                                                              \
   }
+  H2Q_LAUNCH(4, 4, 32, 2, 8, 8)
+  H2Q_LAUNCH(2, 4, 32, 2, 8, 8)
+  H2Q_LAUNCH(2, 2, 16, 1, 16, 8)
+  H2Q_LAUNCH(4, 4, 16, 2, 16, 8)
+  H2Q_LAUNCH(2, 4, 16, 2, 16, 8)
+  H2Q_LAUNCH(2, 1, 8, 1, 8, 4)
+  H2Q_LAUNCH(2, 2, 8, 2, 8, 4)
+  H2Q_LAUNCH(2, 2, 8, 4, 8, 8)
 #undef H2Q_LAUNCH
+  BDM_REQUIRE(launched, "conv3d_h2: no kernel instance for the tile h2_tile chose");
   return launch_status("conv3d_h2");
 }
 

@@ -370,6 +370,11 @@ int bdm_group_norm_to_h2_stats_compact(int b, int c, int v, int groups, const fl
                                        unsigned int *saturated, void *stream);
 int bdm_conv3d_3x3x3_h2(int b, int cin, int cout, int r, const void *x_h2, float x_inv_scale, const void *packed_w,
                         const float *inv_scale, const float *bias, float *y, void *stream);
+/* Host only: the kernel instance conv3d_h2q_kernel<mt, nt, r, tx, ty, nw> that bdm_conv3d_3x3x3_h2 / _h2_gn launch for this shape
+ * -- what the launch path itself decides, not a restatement: a workgroup of nw waves owns 16 mt output channels x a tx x ty x r
+ * brick of voxels (nt 16-voxel blocks per wave).  Returns 0, or BDM_ERR_UNSUPPORTED (3) for a resolution other than 8, 16, 32
+ * (the outputs are then 0).  The out pointers are HOST pointers and may be NULL; no GPU call.  Depends on (b, cout, r) only. */
+int bdm_conv3d_h2_variant(int b, int cin, int cout, int r, int *mt, int *nt, int *tx, int *ty, int *nw);
 
 /* GroupNorm-folded tail of a PVConv without attention (pvconv.py:84-96): the second convolution leaves its output raw and
  * the GroupNorm(groups) statistics of that output as slice partials (layout / size: bdm_group_norm_workspace_bytes;

@@ -441,12 +441,23 @@ def test_conv3d_fp16x3_has_fp32_accuracy(ops, cin, cout, r, kind):
         assert e3 < 4 * e32 + 1e-7, (e3, e32)
 
 
+def _conv3d_h2_tile(b, cin, cout, r):
+    """the kernel instance the launch path picks (bdm_conv3d_h2_variant: host query)"""
+    import ctypes
+    from bdm_amd import _lib
+    v = [ctypes.c_int() for _ in range(5)]
+    assert _lib.lib().bdm_conv3d_h2_variant(b, cin, cout, r, *[ctypes.byref(t) for t in v]) == 0
+    return tuple(t.value for t in v)
+
+
 @pytest.mark.parametrize("cin,cout,r", [(64, 64, 32), (128, 128, 16), (64, 128, 16), (256, 256, 8)])
 def test_conv3d_fp16x3_tile_choice_does_not_change_the_bits(ops, cin, cout, r):
     """The launcher picks smaller tiles when a few shapes cannot fill the chip (conv3d_h2.hip: 32-row / 256-voxel tiles at 16^3
-    and 32^3, 128-voxel tiles at 8^3): a shape convolved alone and inside a batch of 10 gives the same bits, and the GroupNorm
-    statistics the epilogue leaves agree to fp32 rounding of the per-wave sums (a different number of slices)."""
-    B = 10
+    and 32^3, 128-voxel tiles at 8^3): a shape convolved alone and inside a batch large enough to change the tile (10 shapes, or
+    more where the launch path's own chooser says 10 keep the tile) gives the same bits, and the GroupNorm statistics the epilogue leaves agree
+    to fp32 rounding of the per-wave sums (a different number of slices)."""
+    B = max(10, next(b for b in range(2, 65) if _conv3d_h2_tile(b, cin, cout, r) != _conv3d_h2_tile(1, cin, cout, r)))
+    assert _conv3d_h2_tile(B, cin, cout, r) != _conv3d_h2_tile(1, cin, cout, r)
     g = torch.Generator().manual_seed(cin + cout + r)
     x = torch.randn(B, cin, r ** 3, generator=g).cuda()
     w = (torch.randn(cout, cin, 3, 3, 3, generator=g) / (27 * cin) ** 0.5).cuda()
