@@ -1,0 +1,187 @@
+"""Generation metrics for unconditional samples (e.g. `pvd.Model.gen_samples`): set-against-set measures built from the full
+(S, R) matrix of cloud-to-cloud distances between S generated and R reference clouds -- minimum matching distance (MMD),
+coverage (COV) and 1-nearest-neighbour accuracy (1-NNA), each under Chamfer distance (CD) and under the approximate-match earth
+mover's distance (EMD) the point-cloud generation literature reports.
+
+The distance matrices are HIP (csrc/metrics.hip: bdm_pairwise_chamfer, bdm_pairwise_emd_approx; device tensors only, no CPU path);
+the reductions over the small matrices are host-side torch and work on CPU tensors too.
+
+    python -m bdm_amd.metrics --sample gen.npy --ref ref.npy [--metrics cd,emd] [--normalize] [--batch-size N]
+"""
+import argparse
+import glob
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .io import load_pointcloud_ply
+
+
+def _clouds(t, name):
+    if t.dim() != 3 or t.shape[-1] != 3 or t.shape[1] < 1:
+        raise ValueError(f"{name}: expected (count, points >= 1, 3), got {tuple(t.shape)}")
+    return L.f32(t)
+
+
+def _chunks(r, batch_size):
+    if batch_size is None or batch_size >= r:
+        return [(0, r)]
+    if batch_size < 1:
+        raise ValueError("batch_size must be positive")
+    return [(j, min(r, j + batch_size)) for j in range(0, r, batch_size)]
+
+
+def pairwise_chamfer(a, b, batch_size=None, return_directions=False):
+    """a (S, N, 3), b (R, M, 3) on the GPU -> (S, R): mean over a_i of the squared distance to the nearest point of b_j, plus the
+    same with the roles swapped.  `return_directions=True` returns the two halves (a -> b, b -> a) instead of their sum.
+    `batch_size` bounds the references per launch; the result does not depend on it, bit for bit."""
+    a, b = _clouds(a, "a"), _clouds(b, "b")
+    S, R = a.shape[0], b.shape[0]
+    chunks = _chunks(R, batch_size)
+    ab = torch.empty(S, R, dtype=torch.float32, device=a.device)
+    ba = torch.empty(S, R, dtype=torch.float32, device=a.device)
+    for j0, j1 in chunks:
+        # one chunk (the default) writes the result itself; column chunks of a row-major matrix go through a contiguous piece
+        o_ab, o_ba = (ab, ba) if len(chunks) == 1 else (torch.empty(2, S, j1 - j0, dtype=torch.float32, device=a.device))
+        L.check(L.lib().bdm_pairwise_chamfer(S, j1 - j0, a.shape[1], b.shape[1], L.ptr(a), L.ptr(b[j0:j1]), L.ptr(o_ab), L.ptr(o_ba),
+                                             L.stream()), "pairwise_chamfer")
+        if len(chunks) > 1:
+            ab[:, j0:j1], ba[:, j0:j1] = o_ab, o_ba
+    return (ab, ba) if return_directions else ab + ba
+
+
+def pairwise_emd(a, b, batch_size=None):
+    """a (S, N, 3), b (R, N, 3) on the GPU -> (S, R): approximate-match EMD cost(a_i, b_j) / N (not symmetric in a, b)."""
+    a, b = _clouds(a, "a"), _clouds(b, "b")
+    if a.shape[1] != b.shape[1]:
+        raise ValueError(f"pairwise_emd needs equal-sized clouds, got {a.shape[1]} and {b.shape[1]} points")
+    S, R = a.shape[0], b.shape[0]
+    chunks = _chunks(R, batch_size)
+    out = torch.empty(S, R, dtype=torch.float32, device=a.device)
+    for j0, j1 in chunks:
+        o = out if len(chunks) == 1 else torch.empty(S, j1 - j0, dtype=torch.float32, device=a.device)
+        L.check(L.lib().bdm_pairwise_emd_approx(S, j1 - j0, a.shape[1], L.ptr(a), L.ptr(b[j0:j1]), L.ptr(o), L.stream()), "pairwise_emd")
+        if len(chunks) > 1:
+            out[:, j0:j1] = o
+    return out
+
+
+def mmd_cov(dist):
+    """dist (S, R), rows = samples, columns = references ->
+    mmd: mean over references of the distance to the nearest sample; mmd_smp: mean over samples of the distance to the nearest
+    reference; cov: share of the references that are some sample's nearest reference (lowest index on ties)."""
+    dist = torch.as_tensor(dist)
+    S, R = dist.shape
+    min_over_ref, min_over_smp = dist.min(dim=1).values, dist.min(dim=0).values
+    nearest_ref = _first_argmin(dist)
+    return {"mmd": float(min_over_smp.double().mean()), "mmd_smp": float(min_over_ref.double().mean()),
+            "cov": float(nearest_ref.unique().numel()) / float(R)}
+
+
+def _first_argmin(m):
+    """Index of each row's minimum, the lowest index among ties."""
+    n = m.shape[1]
+    is_min = m == m.min(dim=1, keepdim=True).values
+    idx = torch.arange(n, device=m.device).expand_as(m)
+    return torch.where(is_min, idx, torch.full_like(idx, n)).min(dim=1).values
+
+
+def one_nn_accuracy(dxx, dxy, dyy):
+    """Leave-one-out 1-NN classifier over samples (dxx (S, S)) and references (dyy (R, R)) with dxy (S, R) between them: each
+    item's nearest OTHER item (lowest index on ties; samples come first) predicts its label.  acc over all S + R items,
+    acc_sample over the samples, acc_ref over the references."""
+    dxx, dxy, dyy = torch.as_tensor(dxx), torch.as_tensor(dxy), torch.as_tensor(dyy)
+    S, R = dxy.shape
+    full = torch.cat([torch.cat([dxx, dxy], dim=1), torch.cat([dxy.t(), dyy], dim=1)], dim=0).clone()
+    full.fill_diagonal_(float("inf"))
+    nearest = _first_argmin(full)
+    pred_sample = nearest < S
+    is_sample = torch.arange(S + R, device=full.device) < S
+    correct = pred_sample == is_sample
+    return {"acc": float(correct.double().mean()), "acc_sample": float(correct[:S].double().mean()),
+            "acc_ref": float(correct[S:].double().mean())}
+
+
+def metrics_from_matrices(dxy, dxx, dyy, suffix):
+    """The six figures of one distance (`suffix` "cd" or "emd") from its three matrices."""
+    mc, nn = mmd_cov(dxy), one_nn_accuracy(dxx, dxy, dyy)
+    return {f"mmd-{suffix}": mc["mmd"], f"mmd_smp-{suffix}": mc["mmd_smp"], f"cov-{suffix}": mc["cov"],
+            f"1nna-{suffix}": nn["acc"], f"1nna_sample-{suffix}": nn["acc_sample"], f"1nna_ref-{suffix}": nn["acc_ref"]}
+
+
+def compute_all_metrics(sample, ref, metrics=("cd", "emd"), batch_size=None):
+    """sample (S, N, 3), ref (R, N, 3) on the GPU -> flat dict of floats: mmd, mmd_smp, cov, 1nna, 1nna_sample, 1nna_ref, each
+    suffixed -cd / -emd."""
+    fns = {"cd": pairwise_chamfer, "emd": pairwise_emd}
+    out = {}
+    for name in metrics:
+        if name not in fns:
+            raise ValueError(f"unknown metric {name!r}: choose from cd, emd")
+        fn = fns[name]
+        dxy, dxx, dyy = (fn(p, q, batch_size=batch_size).cpu() for p, q in ((sample, ref), (sample, sample), (ref, ref)))
+        out.update(metrics_from_matrices(dxy, dxx, dyy, name))
+    return out
+
+
+def normalize_unit_sphere(clouds):
+    """Centre every cloud on its mean and scale it so that its farthest point lies on the unit sphere."""
+    clouds = clouds - clouds.mean(axis=1, keepdims=True)
+    radius = np.sqrt((clouds ** 2).sum(axis=2)).max(axis=1)
+    return (clouds / np.maximum(radius, 1e-30)[:, None, None]).astype(np.float32)
+
+
+def load_clouds(path):
+    """A .npy of shape (count, N, 3), or a directory of .ply files (sorted by name) with equal point counts -> float32 array."""
+    if os.path.isdir(path):
+        files = sorted(glob.glob(os.path.join(path, "*.ply")))
+        if not files:
+            raise ValueError(f"{path}: no .ply files")
+        clouds = [load_pointcloud_ply(f) for f in files]
+        sizes = {c.shape[0] for c in clouds}
+        if len(sizes) != 1:
+            raise ValueError(f"{path}: clouds of different sizes {sorted(sizes)}")
+        arr = np.stack(clouds)
+    else:
+        arr = np.load(path)
+    if arr.ndim != 3 or arr.shape[2] != 3:
+        raise ValueError(f"{path}: expected (count, N, 3), got {arr.shape}")
+    return np.ascontiguousarray(arr, dtype=np.float32)
+
+
+def _to_device(array):
+    if not torch.cuda.is_available():
+        raise L.BdmHipError("bdm_amd.metrics needs a HIP device (no CPU fallback)")
+    return torch.from_numpy(array).cuda()
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m bdm_amd.metrics", description="MMD / COV / 1-NNA of generated against reference clouds")
+    ap.add_argument("--sample", required=True, help=".npy (count, N, 3) or a directory of .ply: generated clouds")
+    ap.add_argument("--ref", required=True, help=".npy (count, N, 3) or a directory of .ply: reference clouds")
+    ap.add_argument("--metrics", default="cd,emd", type=lambda s: tuple(m for m in s.split(",") if m), help="cd, emd or cd,emd")
+    ap.add_argument("--normalize", action="store_true", help="centre and scale every cloud to the unit sphere first")
+    ap.add_argument("--batch-size", type=int, default=None, help="references per launch")
+    args = ap.parse_args(argv)
+    bad = [m for m in args.metrics if m not in ("cd", "emd")]
+    if bad or not args.metrics:
+        ap.error(f"--metrics: choose from cd, emd (got {','.join(bad) or 'nothing'})")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    sample, ref = load_clouds(args.sample), load_clouds(args.ref)
+    if args.normalize:
+        sample, ref = normalize_unit_sphere(sample), normalize_unit_sphere(ref)
+    result = compute_all_metrics(_to_device(sample), _to_device(ref), metrics=args.metrics, batch_size=args.batch_size)
+    result.update(num_sample=int(sample.shape[0]), num_ref=int(ref.shape[0]), num_points=int(sample.shape[1]))
+    print(json.dumps(result))
+    return result
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

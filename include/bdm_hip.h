@@ -779,6 +779,25 @@ int bdm_simple_layer(int b, int n, const float *x, const float *state, const flo
 /* out = a + b elementwise over n floats (PVCNN++'s residual x + PVCNN(x), pvcnn_plus_plus.py:40); out may alias a or b */
 int bdm_simple_add(long long n, const float *a, const float *b, float *out, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * 7. Generation metrics: all-pairs cloud-to-cloud distance matrices (csrc/metrics.hip; bdm_amd/metrics.py reduces them to
+ *    MMD, COV and 1-NNA).  Clouds are point-major: a (s, n, 3), b (r, m, 3).  No workspace; no atomics: entry (i, j) is
+ *    reduced in a fixed order that depends on the point counts alone, so it carries the bits of the 1 x 1 call on clouds
+ *    i and j.  s = 0 or r = 0 is a no-op.
+ * ---------------------------------------------------------------------------------- */
+/* out_ab[i, j] = mean over the points p of a_i of min over the points q of b_j of |p - q|^2, out_ba[i, j] the same with the
+ * roles swapped; both (s, r), either may be NULL.  Distances in the difference form dx^2 + dy^2 + dz^2. */
+int bdm_pairwise_chamfer(int s, int r, int n, int m, const float *a, const float *b, float *out_ab, float *out_ba,
+                         void *stream);
+/* Host only: the instance pairwise_chamfer_kernel<p> with tj target clouds per workgroup that ONE direction of bdm_pairwise_chamfer
+ * launches for s source clouds of n points against r target clouds -- what the launch path itself decides (the b -> a direction is
+ * the query (r, s, m)).  p, tj are HOST pointers and may be NULL; no GPU call.  Returns 0, or 1 for sizes below 1 (outputs 0). */
+int bdm_pairwise_chamfer_variant(int s, int r, int n, int *p, int *tj);
+/* Approximate-match earth mover's distance (Fan et al., approxmatch + matchcost: ten levels exp(-4^j d^2), j = 7 .. -1, then 0;
+ * DESIGN.md section 10) between equal-sized clouds: out[i, j] = cost(a_i, b_j) / n, (s, r).  Not symmetric in (a, b).
+ * n above 2048 returns 3 (unsupported). */
+int bdm_pairwise_emd_approx(int s, int r, int n, const float *a, const float *b, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
