@@ -8,6 +8,7 @@ CONTAINERS only: their forward is never called.  Every forward below runs hand-w
 kernels through the C ABI (bdm_amd/ops.py, bdm_amd/functional).  Inference only.
 """
 import os
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -179,6 +180,29 @@ class Attention(nn.Module):
         return h.reshape(x.shape)
 
 
+class Route(NamedTuple):
+    """What one PVConv.forward runs (PVConv.route)."""
+    plan_args: tuple     # (resolution, eps) of the ops.voxel_plan forward asks for | None: it voxelises densely
+    dilate: int          # voxel lists the plan is built with ahead of time: 2 = twice-dilated (tail "lists"), 1 = once (first "dil"), 0
+    first: str           # "map" (hoisted) | "dil" (output-stationary) | "gemm" (+ gather) | "gemm_split" (small-grid gather that also splits) | "dense_s3" | "dense_fp32"
+    gemm_impl: str       # arithmetic of "gemm" / "gemm_split" after the demotion: "sparse_h2" | "sparse_s3" | "sparse" | "sparse_fused" | None
+    want_stats: bool     # the first convolution really leaves GroupNorm-1's statistics
+    compact_first: bool  # ... and its output stays on the rows of the dilated list (ops.CompactGrid)
+    takes_rows: bool     # an ops.VoxelRows offered by the previous PVConv's tail is consumed
+    tail: str            # "lists" (voxel lists) | "small" (one-launch small-grid tail) | "se_devox" | "folded" (GroupNorm-folded) | "plain"
+    head: bool           # tail "small" also leaves the next PVConv's operand (that module's route has takes_rows)
+    fold_pf: bool        # the point branch's last GroupNorm + Swish is left to the tail
+    second: str          # second convolution: "fp16x3" | "bf16x6" | "fp32"
+    temb_split: bool     # the time embedding enters as per-shape terms (never with first == "dil")
+
+
+class _VoxelBranch:
+    """The voxel branch of one PVConv.forward between its stages.  A stage REBINDS v, so a grid is released when the next one exists, not
+    when the forward returns (arguments and a caller's locals would hold it until then)."""
+    def __init__(self, v, gn1_stats, plan, norm_coords, xh=None):
+        self.v, self.gn1_stats, self.plan, self.norm_coords, self.xh, self.stats = v, gn1_stats, plan, norm_coords, xh, None
+
+
 class PVConv(nn.Module):
     """pvconv.py:65-97."""
 
@@ -265,13 +289,9 @@ class PVConv(nn.Module):
 
     def can_split_temb(self, features, temb):
         """May this module take `features` WITHOUT the concatenated embedding?  The one predicate of pvcnn.encode and of forward."""
-        c_feat = features.shape[1]
-        return (self.temb_split and features.is_cuda and ops.is_point_invariant(temb) and not ops.is_point_invariant(features)
-                and c_feat + temb.shape[1] == self.in_channels and c_feat % 8 == 0
-                and self.conv_impl in ("bf16x6", "fp16x3") and self.sparse_first_conv and self.resolution in self.sparse_resolutions
-                and self.sparse_gemm in ("sparse_h2", "sparse_s3") and len(self.point_features.layers) == 3
-                and self.point_features.layers[0].out_channels == self.voxel_layers[0].out_channels
-                and not self.wants_dilated_plan(features.shape[0], features.shape[2]))
+        B, c_feat, n = features.shape
+        return (ops.is_point_invariant(temb) and not ops.is_point_invariant(features) and c_feat + temb.shape[1] == self.in_channels
+                and self.route(B, n, cuda=features.is_cuda, temb_split=True, c_feat=c_feat).temb_split)
 
     def _temb_split_terms(self, features, temb):
         """-> (col_bias (B, 27 * cout), point-branch bias (B, cout)) views"""
@@ -285,64 +305,101 @@ class PVConv(nn.Module):
     # The point branch (1x1 conv + GroupNorm + Swish on the N points) does not depend on the voxel branch: it is enqueued on
     # a second stream and joined before the devoxelisation adds it, so its small, latency-bound kernels run beside the
     # voxel convolutions instead of after them (point_stream = False: serial).
-    se_in_devox = False  # SE block's FC layers inside the devoxelisation kernel: measured slower (DESIGN.md negative results)
+    se_in_devox = False  # SE block's FC layers inside the devoxelisation kernel: every workgroup re-reads w1 / w2 -- measured slower (B=16: devoxelisation 325 -> 650 us for 100 us of se_fc saved; DESIGN.md negative results)
     fold_gn1 = True  # GroupNorm-1 statistics from the sparse gather's epilogue
     fold_pf = True  # point branch's GroupNorm folded into the devoxelisation kernel
     point_stream = True  # the point branch of a PVConv on its own stream (False: inline; tests and tools/coresidency/two_proc_race.py flip it)
     point_stream_min = int(os.environ.get("BDM_POINT_STREAM_MIN", "8192"))  # B * N below which the branch stays on the main stream
     _streams = {}
 
-    def voxel_plan_args(self):
-        """(resolution, eps) of the ops.voxel_plan this module's forward will ask for, or None when it voxelises densely."""
-        if self.conv_impl in ("bf16x6", "fp16x3") and self.sparse_first_conv and self.resolution in self.sparse_resolutions:
-            return self.resolution, self.voxelization.eps
-        return None
-
-    def wants_dilated_plan(self, batch, n_points):
-        """Will this module's first convolution run in the compact output-stationary form for (batch, n_points)?  (the side-stream
-        planner then builds the dilated list with the plan, off the main stream)"""
-        conv1 = self.voxel_layers[0]
-        return (self.sparse_conv == "dil" and self.resolution in self.sparse_dil_resolutions and self.conv_impl == "fp16x3"
-                and self.sparse_gemm == "sparse_h2" and not getattr(self, "h2_saturated", False) and self.sparse_first_conv
-                and (self.sparse_dil_always or ops.sparse_dil_pays(batch, n_points, self.resolution, conv1.out_channels)))
-
     # The whole voxel branch on voxel lists (pvconv_compact.hip): second convolution on the twice-dilated list, SE means and
     # devoxelisation from its rows + 27 class constants -- no dense grid is written.  "1": where ops.compact_tail_pays; "always"; "0".
     compact_tail = os.environ.get("BDM_COMPACT_TAIL", "1")
     compact_tail_resolutions = {int(v) for v in os.environ.get("BDM_COMPACT_TAIL_R", "32,16").split(",") if v}
 
-    def wants_compact_tail(self, batch, n_points):
-        conv2 = self.voxel_layers[4] if isinstance(self.voxel_layers[3], nn.Dropout) else self.voxel_layers[3]
-        if not isinstance(conv2, nn.Conv3d):
-            conv2 = next(m for m in list(self.voxel_layers)[1:] if isinstance(m, nn.Conv3d))
-        c = conv2.out_channels
-        has_att = any(isinstance(m, Attention) for m in self.voxel_layers)
-        has_se = any(isinstance(m, SE3d) for m in self.voxel_layers)
-        return (self.compact_tail != "0" and self.resolution in self.compact_tail_resolutions and self.conv_impl == "fp16x3"
-                and self.sparse_first_conv and self.fold_gn1 and self.fold_gn2 and not self.se_in_devox and not has_att and has_se
-                and not getattr(self, "h2_saturated", False) and c % 4 == 0 and c <= 256 and (c // 8) in (4, 8, 16, 32)
-                and (self.compact_tail == "always" or ops.compact_tail_pays(batch, n_points, self.resolution, c)))
-
     _cond = None  # ops.Conditioning of this forward when the input is the raw conditioned cloud (set by PVCNN2Base.forward)
-    _next_pv = None  # the PVConv that consumes this one's output inside the same nn.Sequential (pvcnn.run_blocks), else None
+    _next_pv = None  # the PVConv that consumes this one's output inside the same nn.Sequential (pvcnn.link_pvconvs), else None
 
-    def accepts_rows(self, plan, channels, batch):
-        """Will this module's first convolution take the fp16x3 GEMM over the occupied rows of `plan` (so that the previous PVConv's
-        tail may leave it the operand, ops.VoxelRows)?  Mirrors the route choice in forward."""
-        conv1 = self.voxel_layers[0]
-        return (ops.SMALL_GLUE and self.conv_impl == "fp16x3" and self.sparse_first_conv and self.resolution == plan.r
-                and self.resolution in self.sparse_resolutions and self.sparse_gemm == "sparse_h2" and plan.n_max <= 256
-                and conv1.in_channels == channels and channels % 8 == 0 and not getattr(self, "h2_saturated", False)
-                and not self.wants_dilated_plan(batch, plan.n))
+    def _parts(self):
+        """(conv1, gn1, conv2, gn2, attention | None, SE | None) of voxel_layers"""
+        layers = list(self.voxel_layers)
+        rest = [m for m in layers[2:] if isinstance(m, (nn.Conv3d, nn.GroupNorm, Attention, SE3d))]
+        return (layers[0], layers[1], rest[0], rest[1], next((m for m in rest if isinstance(m, Attention)), None),
+                next((m for m in rest if isinstance(m, SE3d)), None))
 
-    def _head_for_next(self, plan, gn2, batch, device):
-        """(plan, power-of-two scale, saturation word) for bdm_pvconv_tail_small's head, or None: the next PVConv of the Sequential runs on
-        the same voxel plan (same coordinates, same resolution) and takes the operand."""
+    def route(self, batch, n_points, *, cuda=True, hoisted=False, temb_split=False, c_feat=None, rows_offered=False):
+        """Which kernels forward runs for `batch` shapes of `n_points` points: THE statement of every choice (forward only executes it;
+        pvcnn.plan_sampling_chain and the previous PVConv's tail read it ahead of time).  Pure arithmetic on the sizes, the class knobs,
+        ops.SMALL_GLUE* and the saturation flag -- no tensor, no device.  hoisted: the input is the conditioned cloud whose maps are hoisted
+        (_hoisted); temb_split + c_feat: the input arrives as c_feat channels without the time embedding; rows_offered: the previous
+        PVConv's tail would leave (or has left) an ops.VoxelRows."""
+        r = self.resolution
+        conv1, gn1, conv2, gn2, att, se = self._parts()
+        c1, c2 = conv1.out_channels, conv2.out_channels
+        n_max = min(n_points, r ** 3)
+        two_term = self.conv_impl in ("bf16x6", "fp16x3")
+        h2 = self.conv_impl == "fp16x3" and not getattr(self, "h2_saturated", False)   # (ops.poll_h2_saturation sends a layer to bf16x6)
+        sparse = two_term and self.sparse_first_conv and r in self.sparse_resolutions   # conv1 on the occupied cells of a voxel plan
+        dil = (sparse and self.sparse_conv == "dil" and r in self.sparse_dil_resolutions and h2 and self.sparse_gemm == "sparse_h2"
+               and (self.sparse_dil_always or ops.sparse_dil_pays(batch, n_points, r, c1)))
+        split = (temb_split and self.temb_split and cuda and sparse and not dil and c_feat is not None and c_feat % 8 == 0
+                 and self.sparse_gemm in ("sparse_h2", "sparse_s3") and len(self.point_features.layers) == 3
+                 and self.point_features.layers[0].out_channels == c1)
+        cg2, tile = c2 // gn2.num_groups, (64 if (c2 > 32 and r != 8) else 32)
+        folded = h2 and self.fold_gn2 and att is None and se is not None and cg2 in (4, 8, 16, 32) and tile % cg2 == 0
+
+        impl, stats = None, False
+        if not sparse:
+            first = "dense_s3" if two_term else "dense_fp32"
+        else:
+            # the fp16x3 GEMM (half the matrix work) wins on the small grids, where the GEMM is matrix-bound and 64-row tiles cut the
+            # padding; on the 16^3 / 32^3 levels the batched GEMM is bound by its 27x-expanded output and the extra operand split costs
+            # more than it saves (measured: tools/sparse_bench.py)
+            impl = self.sparse_gemm
+            wide16 = n_max <= 1024 and (c_feat if split else conv1.in_channels) >= 128 and c1 >= 128  # 108 vs 121 us at 16^3
+            if impl == "sparse_h2" and n_max > 256 and not wide16:
+                impl = "sparse_s3"
+            # with the fp16x3 second convolution the first one also leaves GroupNorm-1's statistics (no pass over the grid for them)
+            stats = self.fold_gn1 and h2 and impl != "sparse_fused"
+            if hoisted and not split and 27 * c1 <= 1024:   # hoisted map instead of feature gather + K = 390 GEMM
+                first, stats = "map", stats and ops.gather_gn_ok(c1, gn1.num_groups)
+            elif dil:   # (with the statistics in its epilogue the output stays compact: the dense fp32 grid is never written)
+                first, stats = "dil", stats and ops.sparse_os_gn_ok(c1, gn1.num_groups, r)
+            elif (impl == "sparse_h2" and stats and folded and n_max <= 256 and not split
+                  and ops.small_grid_gather_ok(r, c1, gn1.num_groups)):
+                # small grid: GroupNorm-1 + Swish + the second convolution's operand split in the gather's epilogue (one workgroup
+                # per (shape, group)): no dense fp32 grid, no statistics hand-off, no to_h2 launch (pvconv_small.hip)
+                first, stats = "gemm_split", False
+            else:
+                first, stats = "gemm", stats and ops.gather_gn_ok(c1, gn1.num_groups)
+        gemm = first in ("gemm", "gemm_split")
+        takes_rows = (rows_offered and ops.SMALL_GLUE and h2 and gemm and impl == "sparse_h2" and n_max <= 256
+                      and conv1.in_channels % 8 == 0 and not split)
+        head = False
+        if (stats and folded and self.compact_tail != "0" and r in self.compact_tail_resolutions and not self.se_in_devox
+                and c2 % 4 == 0 and c2 <= 256 and (c2 // 8) in (4, 8, 16, 32)
+                and (self.compact_tail == "always" or ops.compact_tail_pays(batch, n_points, r, c2))):
+            tail = "lists"
+        elif not folded:
+            tail = "plain"
+        elif (ops.small_grid_tail_ok(r, c2, n_points) and se.fc[0].out_features <= 256
+              and ((head := self._feeds_next(batch, n_points, cuda, sparse)) or not ops.SMALL_GLUE_TAIL_ONLY)):
+            tail = "small"   # (one launch; where the next PVConv shares the plan it also leaves that module's operand: head)
+        else:
+            tail = "se_devox" if (self.se_in_devox and se.fc[0].out_features <= 64) else "folded"
+        return Route(plan_args=(r, self.voxelization.eps) if sparse else None, dilate=2 if tail == "lists" else int(first == "dil"),
+                     first=first, gemm_impl=impl if gemm else None, want_stats=bool(stats), compact_first=bool(first == "dil" and stats),
+                     takes_rows=bool(takes_rows), tail=tail, head=head, fold_pf=bool(folded and self.fold_pf and not self.se_in_devox),
+                     second="fp16x3" if h2 else ("bf16x6" if two_term else "fp32"), temb_split=bool(split))
+
+    def _feeds_next(self, batch, n_points, cuda, sparse):
+        """Does the next PVConv of the Sequential run on the same voxel plan (same coordinates, same resolution) and take the operand?"""
         nxt = self._next_pv
-        if nxt is None or plan is None or not nxt.accepts_rows(plan, self.out_channels, batch):
-            return None
-        pf_gn = self.point_features.layers[-2]
-        return plan, ops.h2_sum_scale([gn2, pf_gn]), ops.saturation_slot(nxt, device)
+        return bool(ops.SMALL_GLUE and nxt is not None and sparse and nxt.resolution == self.resolution and nxt.in_channels == self.out_channels
+                    and nxt.route(batch, n_points, cuda=cuda, rows_offered=True).takes_rows)
+
+    def wants_compact_tail(self, batch, n_points):
+        return self.route(batch, n_points).tail == "lists"
 
     def _hoisted(self, features):
         """The handle, if `features` IS the conditioned input it describes (first PVConv of the PC^2 denoiser)."""
@@ -406,177 +463,162 @@ class PVConv(nn.Module):
 
     def forward(self, inputs):
         features, coords, temb = inputs
-        r = self.resolution
-        layers = list(self.voxel_layers)
-        conv1, gn1 = layers[0], layers[1]
-        rest = [m for m in layers[2:] if isinstance(m, (nn.Conv3d, nn.GroupNorm, Attention, SE3d))]
-        conv2, gn2 = rest[0], rest[1]
-        att = next((m for m in rest if isinstance(m, Attention)), None)
-        se = next((m for m in rest if isinstance(m, SE3d)), None)
-
         rows_in = getattr(features, "_bdm_rows", None)   # first-convolution operand left by the previous PVConv's tail (ops.VoxelRows)
         features = ops.materialize(features)
-        col_bias, pb_bias, cin1 = None, None, None
-        if features.shape[1] != self.in_channels:   # the caller (pvcnn.encode) left the time embedding out: it enters as per-shape terms
+        B, c_feat, n = features.shape
+        split = c_feat != self.in_channels   # the caller (pvcnn.encode) left the time embedding out: it enters as per-shape terms
+        col_bias, pb_bias = None, None
+        if split:
             if not self.can_split_temb(features, temb):
-                raise ValueError(f"PVConv expects {self.in_channels} input channels, got {features.shape[1]} "
+                raise ValueError(f"PVConv expects {self.in_channels} input channels, got {c_feat} "
                                  f"(and the time embedding cannot enter as a per-shape term here)")
             col_bias, pb_bias = self._temb_split_terms(features, temb)
-            cin1 = features.shape[1]
-        gn1_stats, plan, xh_ready = None, None, None
-        cg2_, tile_ = conv2.out_channels // gn2.num_groups, (64 if (conv2.out_channels > 32 and r != 8) else 32)
-        folded_tail = (self.conv_impl == "fp16x3" and not getattr(self, "h2_saturated", False) and self.fold_gn2 and att is None
-                       and se is not None and cg2_ in (4, 8, 16, 32) and tile_ % cg2_ == 0)
-        # with the folded tail the branch's GroupNorm + Swish is applied by the devoxelisation kernel (one launch less)
-        pf, pf_ready, pf_pending = self._point_branch(features, fold=folded_tail and self.fold_pf and not self.se_in_devox, temb_bias=pb_bias)
-        if self.conv_impl in ("bf16x6", "fp16x3"):
-            if self.sparse_first_conv and r in self.sparse_resolutions:
-                # conv1 sees the freshly voxelised cloud: evaluate it on the occupied cells only (sparse_conv.hip);
-                # the (coords, r) plan is shared by the PVConvs of one level
-                plan = ops.voxel_plan(coords, r, self.voxelization.eps)
-                norm_coords = plan.norm_coords
-                # the fp16x3 GEMM (half the matrix work) wins on the small grids, where the GEMM is matrix-bound and
-                # 64-row tiles cut the padding; on the 16^3 / 32^3 levels the batched GEMM is bound by its 27x-expanded
-                # output and the extra operand split costs more than it saves (measured: tools/sparse_bench.py)
-                impl = self.sparse_gemm
-                wide16 = plan.n_max <= 1024 and (cin1 or conv1.in_channels) >= 128 and conv1.out_channels >= 128  # 108 vs 121 us at 16^3
-                if impl == "sparse_h2" and plan.n_max > 256 and not wide16:
-                    impl = "sparse_s3"
-                # with the fp16x3 second convolution the gather also leaves GroupNorm-1's statistics (no pass over the grid for them)
-                want_stats = (self.fold_gn1 and self.conv_impl == "fp16x3" and not getattr(self, "h2_saturated", False)
-                              and impl != "sparse_fused")
-                cond = self._hoisted(features) if col_bias is None else None
-                if not (cond is not None and 27 * conv1.out_channels <= 1024):
-                    self._need_features(features)
-                if cond is not None and 27 * conv1.out_channels <= 1024:  # hoisted map instead of feature gather + K = 390 GEMM
-                    v = ops.sparse_first_conv_from_map(cond, plan, conv1, conv1.out_channels, gn_groups=gn1.num_groups if want_stats else None)
-                elif col_bias is None and self.wants_dilated_plan(features.shape[0], plan.n):
-                    # one output-stationary implicit GEMM with tap skipping over the dilated voxel list: no 27x intermediate; with the
-                    # statistics in its epilogue the output stays COMPACT (rows of the dilated voxels) and the operand split of the
-                    # second convolution reads it through the plan's index -- the dense fp32 grid is never written (sparse_conv_os.hip)
-                    want_stats = want_stats and ops.sparse_os_gn_ok(conv1.out_channels, gn1.num_groups, r)
-                    v = ops.sparse_first_conv_os(features, plan, self._packed_weight(conv1, "fp16x3"), conv1.bias, conv1.out_channels,
-                                                 gn_groups=gn1.num_groups if want_stats else None, compact=want_stats)
-                else:
-                    if rows_in is not None and not (impl == "sparse_h2" and rows_in.plan is plan and rows_in.channels == conv1.in_channels
-                                                    and col_bias is None):
-                        rows_in = None
-                    if (impl == "sparse_h2" and want_stats and folded_tail and plan.n_max <= 256 and col_bias is None
-                            and ops.small_grid_gather_ok(r, conv1.out_channels, gn1.num_groups)):
-                        # small grid: GroupNorm-1 + Swish + the second convolution's operand split in the gather's epilogue (one
-                        # workgroup per (shape, group)): no dense fp32 grid, no statistics hand-off, no to_h2 launch (pvconv_small.hip)
-                        xh_ready = ops.sparse_first_conv_planned(features, plan, self._packed_weight(conv1, impl), conv1.bias, conv1.out_channels,
-                                                                 rows=rows_in, h2_out=(gn1, ops.h2_activation_scale(gn1),
-                                                                                       ops.saturation_slot(self, features.device)))
-                        v, want_stats = None, False
-                    else:
-                        v = ops.sparse_first_conv_planned(features, plan, self._packed_weight(conv1, impl, cin=cin1), conv1.bias, conv1.out_channels,
-                                                          gn_groups=gn1.num_groups if want_stats else None, rows=rows_in, col_bias=col_bias)
-                if want_stats:
-                    v, gn1_stats = v
-            else:
-                assert col_bias is None
-                self._need_features(features)
+        route = self.route(B, n, cuda=features.is_cuda, hoisted=not split and self._hoisted(features) is not None, temb_split=split,
+                           c_feat=c_feat, rows_offered=rows_in is not None)
+        # (fold_pf: the branch's GroupNorm + Swish is applied by the devoxelisation kernel -- one launch less)
+        pf, pf_ready, pf_pending = self._point_branch(features, fold=route.fold_pf, temb_bias=pb_bias)
+        vb = self._first_conv(route, features, coords, col_bias, rows_in)
+        if route.tail != "lists":
+            self._second_conv(route, vb)
+        return getattr(self, "_tail_" + route.tail)(route, vb, pf, pf_ready, pf_pending), coords, temb
+
+    def _first_conv(self, route, features, coords, col_bias, rows_in):
+        """-> _VoxelBranch(grid | ops.CompactGrid | None, GroupNorm-1 statistics | None, voxel plan | None, normalised coordinates, second
+        convolution's operand ("gemm_split" only))"""
+        r = self.resolution
+        conv1, gn1 = self.voxel_layers[0], self.voxel_layers[1]
+        cout = conv1.out_channels
+        if route.plan_args is None:
+            assert col_bias is None
+            self._need_features(features)
+            if route.first == "dense_s3":
                 norm_coords, vox_coords = ops.voxel_coords(coords, r, self.voxelization.eps)
                 x3 = ops.avg_voxelize_s3(features, vox_coords, r)
-                v = ops.conv3d_s3(x3, self._packed_weight(conv1, "bf16x6"), conv1.bias, conv1.in_channels,
-                                  conv1.out_channels, r)
-            if gn1_stats is not None and folded_tail and self.wants_compact_tail(features.shape[0], features.shape[2]):
-                # the rest of the branch on voxel lists: operand split on the once-dilated rows, second convolution on the
-                # twice-dilated list, SE means and devoxelisation from its rows + the 27 class constants (pvconv_compact.hip)
-                sat = ops.saturation_slot(self, features.device)
-                rows_h2, const_h2, const_f32, inv_s = ops.to_h2_rows(v, plan, gn1, gn1_stats, saturated=sat, bias=conv1.bias)
-                y2, cvals, st2 = ops.second_conv_rows(rows_h2, const_h2, const_f32, inv_s, plan, self._packed_weight(conv2, "fp16x3"),
-                                                      self._packed_weight(conv2, "class"), conv2.bias, conv2.in_channels,
-                                                      conv2.out_channels, gn2.num_groups)
-                w1, w2 = se.fc[0].weight, se.fc[2].weight
-                if pf_pending is not None:
-                    if pf_ready is not None:
-                        tape.wait_event(pf_ready)  # the branch's statistics are read by the SE kernel
-                    gate, coef, pf_coef = ops.se_gate_gn_rows(y2, cvals, plan, st2, gn2, w1, w2, pf=pf_pending, n_points=pf.shape[2])
-                    return ops.devoxelize_gn_gate_add_rows(norm_coords, y2, cvals, plan, coef, gate=gate, add=pf, add_coef=pf_coef), coords, temb
-                gate, coef = ops.se_gate_gn_rows(y2, cvals, plan, st2, gn2, w1, w2)
-                if pf_ready is not None:
-                    tape.wait_event(pf_ready)
-                return ops.devoxelize_gn_gate_add_rows(norm_coords, y2, cvals, plan, coef, gate=gate, add=pf), coords, temb
-            # GroupNorm + Swish fused into the operand split of the second conv
-            if self.conv_impl == "fp16x3" and not getattr(self, "h2_saturated", False):
-                # saturation guard: to_h2 raises this layer's sticky device word when a scaled activation leaves fp16's
-                # range; ops.poll_h2_saturation() (once per trajectory) then routes the layer to bf16x6 and warns
-                if xh_ready is not None:
-                    xh = xh_ready
-                else:
-                    sat = ops.saturation_slot(self, v.device) if v.is_cuda else None
-                    xh = ops.to_h2(v, gn1, swish=True, saturated=sat, stats=gn1_stats)
-                cg2, tile = conv2.out_channels // gn2.num_groups, (64 if (conv2.out_channels > 32 and r != 8) else 32)
-                if self.fold_gn2 and att is None and se is not None and cg2 in (4, 8, 16, 32) and tile % cg2 == 0:
-                    # GroupNorm-folded tail: the convolution leaves the statistics of its output, SE and the devoxelisation
-                    # normalise + Swish on the fly -- the grid is written once (by the convolution) and never rewritten
-                    v, stats = ops.conv3d_h2_gn(xh, self._packed_weight(conv2, "fp16x3"), conv2.bias, conv2.in_channels,
-                                                conv2.out_channels, r, gn2.num_groups)
-                    w1, w2 = se.fc[0].weight, se.fc[2].weight
-                    head = self._head_for_next(plan, gn2, features.shape[0], features.device) if ops.SMALL_GLUE else None
-                    if ops.small_grid_tail_ok(r, conv2.out_channels, features.shape[2]) and w1.shape[0] <= 256 and (head is not None or not ops.SMALL_GLUE_TAIL_ONLY):
-                        # small grid: SE's FC layers + GroupNorm-2 + Swish + gate + devoxelisation + point branch in one launch of
-                        # per-shape workgroups, which also leave the NEXT PVConv's first-convolution operand when it shares the plan
-                        if pf_ready is not None:
-                            tape.wait_event(pf_ready)
-                        pf_coef = None
-                        if pf_pending is not None:
-                            mean, coef, pf_coef = ops.se_means_gn(v, stats, gn2, pf=pf_pending, n_points=pf.shape[2])
-                        else:
-                            mean, coef = ops.se_means_gn(v, stats, gn2)
-                        out, rows = ops.pvconv_tail_small(norm_coords, v, coef, mean, w1, w2, r, add=pf, add_coef=pf_coef, head=head)
-                        if rows is not None:
-                            out._bdm_rows = rows
-                        return out, coords, temb
-                    if self.se_in_devox and w1.shape[0] <= 64:
-                        # SE block's FC layers inside the devoxelisation kernel: one launch less, but every workgroup re-reads
-                        # w1 / w2 (measured at B=16: devoxelisation 325 -> 650 us per forward for 100 us of se_fc saved), so
-                        # this is only worth it where the forward is launch-bound (PVConv.se_in_devox, off)
-                        mean, coef = ops.se_means_gn(v, stats, gn2)
-                        if pf_ready is not None:
-                            tape.wait_event(pf_ready)
-                        return ops.devoxelize_gn_se_add(norm_coords, v, coef, r, mean, w1, w2, add=pf), coords, temb
-                    if pf_pending is not None:
-                        if pf_ready is not None:
-                            tape.wait_event(pf_ready)  # the branch's statistics are read by the SE kernel
-                        gate, coef, pf_coef = ops.se_gate_gn(v, stats, gn2, w1, w2, pf=pf_pending, n_points=pf.shape[2])
-                        return ops.devoxelize_gn_gate_add(norm_coords, v, coef, r, gate=gate, add=pf, add_coef=pf_coef), coords, temb
-                    gate, coef = ops.se_gate_gn(v, stats, gn2, w1, w2)
-                    if pf_ready is not None:
-                        tape.wait_event(pf_ready)
-                    return ops.devoxelize_gn_gate_add(norm_coords, v, coef, r, gate=gate, add=pf), coords, temb
-                v = ops.conv3d_h2(xh, self._packed_weight(conv2, "fp16x3"), conv2.bias, conv2.in_channels, conv2.out_channels, r)
+                return _VoxelBranch(ops.conv3d_s3(x3, self._packed_weight(conv1, "bf16x6"), conv1.bias, conv1.in_channels, cout, r), None, None, norm_coords)
+            # the input is the freshly voxelised cloud: on the 32^3 grids (<= 12.5 % occupied cells) the occupancy-skipping variant
+            # wins (measured 1.3-1.4x); on 16^3 / 8^3 the dense kernel is as fast or faster
+            vox, norm_coords = self.voxelization(features, coords, with_row_occupancy=r >= 32)
+            vox, rowocc = vox if r >= 32 else (vox, None)
+            return _VoxelBranch(ops.conv3d(vox, self._packed_weight(conv1, "fp32"), conv1.bias, r, rowocc=rowocc), None, None, norm_coords)
+        # conv1 sees the freshly voxelised cloud: evaluate it on the occupied cells only (sparse_conv.hip); the (coords, r) plan is
+        # shared by the PVConvs of one level
+        plan = ops.voxel_plan(coords, *route.plan_args)
+        groups = gn1.num_groups if route.want_stats else None
+        if route.first == "map":
+            v = ops.sparse_first_conv_from_map(self._hoisted(features), plan, conv1, cout, gn_groups=groups)
+        else:
+            self._need_features(features)
+            if route.first == "dil":
+                v = ops.sparse_first_conv_os(features, plan, self._packed_weight(conv1, "fp16x3"), conv1.bias, cout, gn_groups=groups,
+                                             compact=route.compact_first)
             else:
-                v = ops.conv3d_s3(ops.to_s3(v, gn1, swish=True), self._packed_weight(conv2, "bf16x6"), conv2.bias,
-                                  conv2.in_channels, conv2.out_channels, r)
-            ops.group_norm_(v, gn2.weight, gn2.bias, 8, gn2.eps, swish=(att is None))
-            if att is not None:
-                v = att(v)
-            gate = se.gate(v) if se is not None else None
+                impl = route.gemm_impl
+                rows = rows_in if (route.takes_rows and rows_in.plan is plan and rows_in.channels == conv1.in_channels) else None
+                if route.first == "gemm_split":
+                    xh = ops.sparse_first_conv_planned(features, plan, self._packed_weight(conv1, impl), conv1.bias, cout, rows=rows, impl=impl,
+                                                       h2_out=(gn1, ops.h2_activation_scale(gn1), ops.saturation_slot(self, features.device)))
+                    return _VoxelBranch(None, None, plan, plan.norm_coords, xh)
+                cin = features.shape[1] if col_bias is not None else None
+                v = ops.sparse_first_conv_planned(features, plan, self._packed_weight(conv1, impl, cin=cin), conv1.bias, cout,
+                                                  gn_groups=groups, rows=rows, col_bias=col_bias, impl=impl)
+        return _VoxelBranch(*(v if groups else (v, None)), plan, plan.norm_coords)
+
+    def _second_conv(self, route, vb):
+        """GroupNorm-1 + Swish + the second convolution: vb.v becomes its grid, vb.stats its GroupNorm-2 statistics (folded tails)"""
+        r = self.resolution
+        _, gn1, conv2, gn2, _, _ = self._parts()
+        cin, cout = conv2.in_channels, conv2.out_channels
+        if route.second == "fp32":
+            ops.group_norm_(vb.v, gn1.weight, gn1.bias, 8, gn1.eps, swish=True)
+            vb.v = ops.conv3d(vb.v, self._packed_weight(conv2, "fp32"), conv2.bias, r)
+        elif route.second == "bf16x6":
+            vb.v = ops.conv3d_s3(ops.to_s3(vb.v, gn1, swish=True), self._packed_weight(conv2, "bf16x6"), conv2.bias, cin, cout, r)
+        else:
+            if vb.xh is None:
+                # GroupNorm + Swish fused into the operand split.  Saturation guard: to_h2 raises this layer's sticky device word when a
+                # scaled activation leaves fp16's range; ops.poll_h2_saturation() (once per trajectory) then routes the layer to bf16x6
+                sat = ops.saturation_slot(self, vb.v.device) if vb.v.is_cuda else None
+                vb.xh = ops.to_h2(vb.v, gn1, swish=True, saturated=sat, stats=vb.gn1_stats)
+            if route.tail == "plain":
+                vb.v = ops.conv3d_h2(vb.xh, self._packed_weight(conv2, "fp16x3"), conv2.bias, cin, cout, r)
+            else:
+                # GroupNorm-folded tails: the convolution leaves the statistics of its output, SE and the devoxelisation normalise +
+                # Swish on the fly -- the grid is written once (by the convolution) and never rewritten
+                vb.v, vb.stats = ops.conv3d_h2_gn(vb.xh, self._packed_weight(conv2, "fp16x3"), conv2.bias, cin, cout, r, gn2.num_groups)
+
+    def _tail_lists(self, route, vb, pf, pf_ready, pf_pending):
+        """The rest of the branch on voxel lists: operand split on the once-dilated rows, second convolution on the twice-dilated list,
+        SE means and devoxelisation from its rows + the 27 class constants (pvconv_compact.hip)"""
+        conv1, gn1, conv2, gn2, _, se = self._parts()
+        plan, norm_coords = vb.plan, vb.norm_coords
+        sat = ops.saturation_slot(self, pf.device)
+        rows_h2, const_h2, const_f32, inv_s = ops.to_h2_rows(vb.v, plan, gn1, vb.gn1_stats, saturated=sat, bias=conv1.bias)
+        y2, cvals, st2 = ops.second_conv_rows(rows_h2, const_h2, const_f32, inv_s, plan, self._packed_weight(conv2, "fp16x3"),
+                                              self._packed_weight(conv2, "class"), conv2.bias, conv2.in_channels,
+                                              conv2.out_channels, gn2.num_groups)
+        w1, w2 = se.fc[0].weight, se.fc[2].weight
+        if pf_pending is not None:
             if pf_ready is not None:
-                tape.wait_event(pf_ready)  # the current stream waits for the point branch
-            return ops.devoxelize_gate_add(norm_coords, v, r, gate=gate, add=pf), coords, temb
-        # the first conv's input is the freshly voxelised cloud: on the 32^3 grids (<= 12.5 % occupied cells) the
-        # occupancy-skipping variant wins (measured 1.3-1.4x); on 16^3 / 8^3 the dense kernel is as fast or faster
-        sparse = r >= 32
-        self._need_features(features)
-        vox, norm_coords = self.voxelization(features, coords, with_row_occupancy=sparse)
-        rowocc = None
-        if sparse:
-            vox, rowocc = vox
-        v = ops.conv3d(vox, self._packed_weight(conv1, "fp32"), conv1.bias, r, rowocc=rowocc)
-        ops.group_norm_(v, gn1.weight, gn1.bias, 8, gn1.eps, swish=True)
-        v = ops.conv3d(v, self._packed_weight(conv2, "fp32"), conv2.bias, r)
-        ops.group_norm_(v, gn2.weight, gn2.bias, 8, gn2.eps, swish=(att is None))
-        if att is not None:
-            v = att(v)
-        gate = se.gate(v) if se is not None else None
+                tape.wait_event(pf_ready)  # the branch's statistics are read by the SE kernel
+            gate, coef, pf_coef = ops.se_gate_gn_rows(y2, cvals, plan, st2, gn2, w1, w2, pf=pf_pending, n_points=pf.shape[2])
+            return ops.devoxelize_gn_gate_add_rows(norm_coords, y2, cvals, plan, coef, gate=gate, add=pf, add_coef=pf_coef)
+        gate, coef = ops.se_gate_gn_rows(y2, cvals, plan, st2, gn2, w1, w2)
         if pf_ready is not None:
             tape.wait_event(pf_ready)
-        fused = ops.devoxelize_gate_add(norm_coords, v, r, gate=gate, add=pf)
-        return fused, coords, temb
+        return ops.devoxelize_gn_gate_add_rows(norm_coords, y2, cvals, plan, coef, gate=gate, add=pf)
+
+    def _tail_small(self, route, vb, pf, pf_ready, pf_pending):
+        """SE's FC layers + GroupNorm-2 + Swish + gate + devoxelisation + point branch in one launch (pvconv_small.hip); with route.head it
+        also leaves the next PVConv's operand: head = (plan, power-of-two scale, that module's saturation word)"""
+        _, _, conv2, gn2, _, se = self._parts()
+        head = None
+        if route.head:
+            head = vb.plan, ops.h2_sum_scale([gn2, self.point_features.layers[-2]]), ops.saturation_slot(self._next_pv, pf.device)
+        if pf_ready is not None:
+            tape.wait_event(pf_ready)
+        pf_coef = None
+        if pf_pending is not None:
+            mean, coef, pf_coef = ops.se_means_gn(vb.v, vb.stats, gn2, pf=pf_pending, n_points=pf.shape[2])
+        else:
+            mean, coef = ops.se_means_gn(vb.v, vb.stats, gn2)
+        out, rows = ops.pvconv_tail_small(vb.norm_coords, vb.v, coef, mean, se.fc[0].weight, se.fc[2].weight, self.resolution, add=pf, add_coef=pf_coef,
+                                          head=head)
+        if rows is not None:
+            out._bdm_rows = rows
+        return out
+
+    def _tail_se_devox(self, route, vb, pf, pf_ready, pf_pending):
+        """SE block's FC layers inside the devoxelisation kernel (PVConv.se_in_devox, off)"""
+        _, _, _, gn2, _, se = self._parts()
+        mean, coef = ops.se_means_gn(vb.v, vb.stats, gn2)
+        if pf_ready is not None:
+            tape.wait_event(pf_ready)
+        return ops.devoxelize_gn_se_add(vb.norm_coords, vb.v, coef, self.resolution, mean, se.fc[0].weight, se.fc[2].weight, add=pf)
+
+    def _tail_folded(self, route, vb, pf, pf_ready, pf_pending):
+        _, _, _, gn2, _, se = self._parts()
+        w1, w2 = se.fc[0].weight, se.fc[2].weight
+        v, stats, norm_coords = vb.v, vb.stats, vb.norm_coords
+        if pf_pending is not None:
+            if pf_ready is not None:
+                tape.wait_event(pf_ready)  # the branch's statistics are read by the SE kernel
+            gate, coef, pf_coef = ops.se_gate_gn(v, stats, gn2, w1, w2, pf=pf_pending, n_points=pf.shape[2])
+            return ops.devoxelize_gn_gate_add(norm_coords, v, coef, self.resolution, gate=gate, add=pf, add_coef=pf_coef)
+        gate, coef = ops.se_gate_gn(v, stats, gn2, w1, w2)
+        if pf_ready is not None:
+            tape.wait_event(pf_ready)
+        return ops.devoxelize_gn_gate_add(norm_coords, v, coef, self.resolution, gate=gate, add=pf)
+
+    def _tail_plain(self, route, vb, pf, pf_ready, pf_pending):
+        _, _, _, gn2, att, se = self._parts()
+        ops.group_norm_(vb.v, gn2.weight, gn2.bias, 8, gn2.eps, swish=(att is None))
+        if att is not None:
+            vb.v = att(vb.v)   # (rebound in the record: the convolution's grid is released here, not when the forward returns)
+        gate = se.gate(vb.v) if se is not None else None
+        if pf_ready is not None:
+            tape.wait_event(pf_ready)  # the current stream waits for the point branch
+        return ops.devoxelize_gate_add(vb.norm_coords, vb.v, self.resolution, gate=gate, add=pf)
+
 
 
 class BallQuery(nn.Module):

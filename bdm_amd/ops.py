@@ -41,6 +41,15 @@ def _bcl(t):
     return t, B, C, l, bs, ld
 
 
+def _addend_strides(add):
+    """(batch stride, row stride) of an optional addend that a kernel reads in place ((0, 0) without one)"""
+    if add is None:
+        return 0, 0
+    aa, _, _, _, bs, ld = _bcl(add)
+    assert aa.data_ptr() == add.data_ptr()
+    return bs, ld
+
+
 _ws_cache = {}
 
 
@@ -432,11 +441,7 @@ def devoxelize_gate_add(norm_coords, grid, r, gate=None, add=None, out=None):
     if out is None:
         out = torch.empty(B, C, n, dtype=torch.float32, device=grid.device)
     _, _, _, _, bs_o, ld_o = _bcl(out)
-    if add is not None:
-        aa, _, _, _, bs_a, ld_a = _bcl(add)
-        assert aa.data_ptr() == add.data_ptr()
-    else:
-        bs_a, ld_a = 0, 0
+    bs_a, ld_a = _addend_strides(add)
     L.check(L.lib().bdm_devoxelize_gate_add(B, C, n, int(r), L.ptr(norm_coords), L.ptr(grid), L.ptr(gate), L.ptr(add),
                                             L.c_ll(bs_a), ld_a, L.ptr(out), L.c_ll(bs_o), ld_o, L.stream()),
             "devoxelize_gate_add")
@@ -770,11 +775,7 @@ def devoxelize_gn_se_add(norm_coords, grid, coef, r, mean, w1, w2, add=None):
     n = norm_coords.shape[2]
     out = torch.empty(B, C, n, dtype=torch.float32, device=grid.device)
     _, _, _, _, bs_o, ld_o = _bcl(out)
-    if add is not None:
-        aa, _, _, _, bs_a, ld_a = _bcl(add)
-        assert aa.data_ptr() == add.data_ptr()
-    else:
-        bs_a, ld_a = 0, 0
+    bs_a, ld_a = _addend_strides(add)
     L.check(L.lib().bdm_devoxelize_gn_se_add(B, C, n, int(r), L.ptr(norm_coords), L.ptr(grid), L.ptr(coef), L.ptr(mean), w1.shape[0],
                                              L.ptr(w1), L.ptr(w2), L.ptr(add), bs_a, ld_a, L.ptr(out), bs_o, ld_o, L.stream()),
             "devoxelize_gn_se_add")
@@ -786,11 +787,7 @@ def devoxelize_gn_gate_add(norm_coords, grid, coef, r, gate=None, add=None, add_
     n = norm_coords.shape[2]
     out = torch.empty(B, C, n, dtype=torch.float32, device=grid.device)
     _, _, _, _, bs_o, ld_o = _bcl(out)
-    if add is not None:
-        aa, _, _, _, bs_a, ld_a = _bcl(add)
-        assert aa.data_ptr() == add.data_ptr()
-    else:
-        bs_a, ld_a = 0, 0
+    bs_a, ld_a = _addend_strides(add)
     if add_coef is not None:  # add is the point branch's raw convolution output; its GroupNorm + Swish is applied in the kernel
         L.check(L.lib().bdm_devoxelize_gn_gate_add_pf(B, C, n, int(r), L.ptr(norm_coords), L.ptr(grid), L.ptr(coef), L.ptr(gate),
                                                       L.ptr(add), bs_a, ld_a, L.ptr(add_coef), L.ptr(out), bs_o, ld_o, L.stream()),
@@ -853,27 +850,19 @@ def pvconv_tail_small(norm_coords, grid, coef, mean, w1, w2, r, add=None, add_co
     n = norm_coords.shape[2]
     out = torch.empty(B, C, n, dtype=torch.float32, device=grid.device)
     _, _, _, _, bs_o, ld_o = _bcl(out)
-    if add is not None:
-        aa, _, _, _, bs_a, ld_a = _bcl(add)
-        assert aa.data_ptr() == add.data_ptr()
-    else:
-        bs_a, ld_a = 0, 0
-    rows = None
+    bs_a, ld_a = _addend_strides(add)
+    rows, head_args = None, (None, None, None, None, 0, 0.0, None, None, None)
     if head is not None:
         plan, x_scale, saturated = head
         xh = torch.empty(B, C // 8, 2, plan.n_max, 8, dtype=torch.float16, device=grid.device)
         amax = torch.empty(B, dtype=torch.float32, device=grid.device)
         rows = VoxelRows(plan, xh, amax, C)
-        L.check(L.lib().bdm_pvconv_tail_small(B, C, n, int(r), w1.shape[0], L.ptr(norm_coords), L.ptr(grid), L.ptr(coef), L.ptr(mean),
-                                              L.ptr(w1), L.ptr(w2), L.ptr(add), bs_a, ld_a, L.ptr(add_coef), L.ptr(out), bs_o, ld_o,
-                                              L.ptr(plan.cnt), L.ptr(plan.ws), L.ptr(plan.occ_list), L.ptr(plan.n_occ), plan.n_max,
-                                              L.c_float(x_scale), L.ptr(xh), L.ptr(amax), L.ptr(saturated), L.stream()), "pvconv_tail_small")
-        return out, rows
+        head_args = (L.ptr(plan.cnt), L.ptr(plan.ws), L.ptr(plan.occ_list), L.ptr(plan.n_occ), plan.n_max, L.c_float(x_scale), L.ptr(xh),
+                     L.ptr(amax), L.ptr(saturated))
     L.check(L.lib().bdm_pvconv_tail_small(B, C, n, int(r), w1.shape[0], L.ptr(norm_coords), L.ptr(grid), L.ptr(coef), L.ptr(mean),
                                           L.ptr(w1), L.ptr(w2), L.ptr(add), bs_a, ld_a, L.ptr(add_coef), L.ptr(out), bs_o, ld_o,
-                                          L.ptr(None), L.ptr(None), L.ptr(None), L.ptr(None), 0, L.c_float(0.0), L.ptr(None), L.ptr(None),
-                                          L.ptr(None), L.stream()), "pvconv_tail_small")
-    return out, None
+                                          *head_args, L.stream()), "pvconv_tail_small")
+    return out, rows
 
 
 # ---- sparse first convolution of a PVConv (csrc/sparse_conv.hip) ----------------------------------------------------
@@ -964,6 +953,22 @@ class VoxelPlan:
                  "ready", "stream", "dil_list", "dil_index", "plane_start", "tile_start", "n_dil_max",
                  "d2_list", "d2_index", "d2_tiles", "d2_class_count", "tile", "d2_tile")
 
+    def __init__(self, vox_coords, r, norm_coords=None, coords=None):
+        """The buffers of the plan of (B, 3, n) integer voxel coordinates; the caller launches the kernels that fill them."""
+        B, _, n = vox_coords.shape
+        dev, r3 = vox_coords.device, r ** 3
+        self.ready = self.stream = None
+        self.r, self.n, self.n_max = int(r), n, min(n, r3)
+        self.coords, self.norm_coords, self.vox_coords = coords, norm_coords, vox_coords
+        self.ind = torch.empty(B, n, dtype=torch.int32, device=dev)
+        self.cnt = torch.empty(B, r3, dtype=torch.int32, device=dev)
+        self.ws = torch.empty(L.lib().bdm_voxelize_workspace_bytes(B, n, r), dtype=torch.uint8, device=dev)
+        self.occ_index = torch.empty(B, r3, dtype=torch.int32, device=dev)
+        self.occ_list = torch.empty(B, self.n_max, dtype=torch.int32, device=dev)
+        self.n_occ = torch.empty(B, dtype=torch.int32, device=dev)
+        self.rowocc = torch.empty(B, r * r, dtype=torch.uint8, device=dev)
+        self.dil_list = self.d2_list = None
+
 
 _plan_cache = {}
 
@@ -986,29 +991,17 @@ def voxel_plan(coords, r, eps=0.0, dilate=False):
         return p
     lib = L.lib()
     B, _, n = coords.shape
-    dev = coords.device
-    r3 = r ** 3
-    p = VoxelPlan()
-    p.ready = None
-    p.r, p.n, p.n_max = int(r), n, min(n, r3)
-    p.coords = coords   # (the contiguous (B, 3, n) tensor the plan describes: consumers that need the xyz rows again take them from here)
-    p.norm_coords, p.vox_coords = voxel_coords(coords, r, eps)
-    p.ind = torch.empty(B, n, dtype=torch.int32, device=dev)
-    p.cnt = torch.empty(B, r3, dtype=torch.int32, device=dev)
-    p.ws = torch.empty(lib.bdm_voxelize_workspace_bytes(B, n, r), dtype=torch.uint8, device=dev)
-    p.occ_index = torch.empty(B, r3, dtype=torch.int32, device=dev)
-    p.occ_list = torch.empty(B, p.n_max, dtype=torch.int32, device=dev)
-    p.n_occ = torch.empty(B, dtype=torch.int32, device=dev)
-    p.rowocc = torch.empty(B, r * r, dtype=torch.uint8, device=dev)
+    norm_coords, vox_coords = voxel_coords(coords, r, eps)
+    # (coords: the contiguous (B, 3, n) tensor the plan describes -- consumers that need the xyz rows again take them from there)
+    p = VoxelPlan(vox_coords, r, norm_coords, coords)
     L.check(lib.bdm_voxelize_plan_full(B, n, r, p.n_max, L.ptr(p.vox_coords), L.ptr(p.ind), L.ptr(p.cnt), L.ptr(p.ws),
                                        L.ptr(p.occ_index), L.ptr(p.occ_list), L.ptr(p.n_occ), L.ptr(p.rowocc), L.stream()),
             "voxelize_plan_full")
-    p.dil_list = p.d2_list = None
     if dilate:
         plan_dilation(p)
         if dilate == 2:
             plan_dilation2(p)
-    p.stream = torch.cuda.current_stream(dev) if coords.is_cuda else None
+    p.stream = torch.cuda.current_stream(coords.device) if coords.is_cuda else None
     _plan_cache[key] = p
     return p
 
@@ -1198,12 +1191,7 @@ def sparse_first_conv_from_map(cond, plan, conv, cout, gn_groups=None):
                                               L.ptr(plan.cnt), L.ptr(plan.ws), L.ptr(plan.occ_list), L.ptr(plan.n_occ), L.ptr(y), L.stream()),
             "sparse_conv_rows_from_map")
     out = torch.empty(B, cout, r ** 3, dtype=torch.float32, device=dev)
-    gn, stats = None, None
-    if gn_groups and gather_gn_ok(cout, gn_groups):
-        partial = torch.empty(B, gn_groups, r * r, 2, dtype=torch.float64, device=dev)
-        gn, stats = (partial, int(gn_groups)), (partial, r * r, int(gn_groups))
-    _gather(lib, B, cout, r, plan, 0, y, conv.bias, out, gn)
-    return (out, stats) if gn_groups else out
+    return _gather_groups(plan, B, cout, conv.bias, gn_groups, None, B, y, out)
 
 
 def gather_gn_ok(cout, groups):
@@ -1223,115 +1211,142 @@ def _gather(lib, nb, cout, r, plan, b0, y, bias, out, gn):
                 "sparse_conv_gather_gn")
 
 
-def sparse_first_conv_planned(features, plan, wt, bias, cout, gn_groups=None, rows=None, h2_out=None, col_bias=None):
+def _gather_groups(plan, B, cout, bias, gn_groups, gemm, gb, y, out):
+    """The rows -> grid half of every occupied-row first convolution: per group of `gb` shapes gemm(nb, b0) fills the shared Y, the
+    gather scatters it into `out`; with gn_groups (and gather_gn_ok) it also leaves the GroupNorm partials -> (out, stats | None)."""
+    lib, r = L.lib(), plan.r
+    gn, stats = None, None
+    if gn_groups and gather_gn_ok(cout, gn_groups):
+        partial = torch.empty(B, gn_groups, r * r, 2, dtype=torch.float64, device=out.device)
+        gn, stats = (partial, int(gn_groups)), (partial, r * r, int(gn_groups))
+    for b0 in range(0, B, gb):
+        nb = min(gb, B - b0)
+        if gemm is not None:
+            gemm(nb, b0)
+        _gather(lib, nb, cout, r, plan, b0, y, bias, out, gn)
+    return (out, stats) if gn_groups else out
+
+
+def _y_buffer(plan, B, cout, dev):
+    """-> (shapes per group, Y).  The 27x-expanded intermediate Y (n_occ x 27*cout fp32 per shape) is written by the GEMM and read once
+    by the gather.  Shapes are processed in groups whose Y stays within SPARSE_Y_BYTES (256 MiB, about the memory-side cache),
+    reusing ONE Y buffer.  Measured (tools/sparse_bench.py): two groups of 8 at the 64 -> 64 / 32^3 layer: 287 -> 261 us;
+    smaller groups lose more to the extra launches than they gain."""
+    gb = max(1, min(B, SPARSE_Y_BYTES // max(plan.n_max * 27 * cout * 4, 1)))
+    return gb, torch.empty(gb, plan.n_max, 27 * cout, dtype=torch.float32, device=dev)
+
+
+# The occupied cells' mean features as the GEMM operand of one weight format (features = the (f, B, C, n, bs_f, ld_f) of _bcl)
+def _records_f32(features, plan, extra=0):
+    """fp32 records (B, C/8, n_max, 8) + one activation-scale maximum per shape (a shape's result does not depend on its batch-mates;
+    `extra` further zeroed slots behind them)"""
+    f, B, C, n, bs_f, ld_f = features
+    xr = torch.empty(B, (C + 7) // 8, plan.n_max, 8, dtype=torch.float32, device=f.device)
+    amax = amax_slots(f.device, B + extra)
+    L.check(L.lib().bdm_sparse_voxel_features_f32(B, C, n, plan.r, plan.n_max, L.ptr(f), bs_f, ld_f, L.ptr(plan.cnt), L.ptr(plan.ws),
+                                                  L.ptr(plan.occ_list), L.ptr(plan.n_occ), L.ptr(xr), L.ptr(amax), L.stream()),
+            "sparse_voxel_features_f32")
+    return xr, amax
+
+
+def _operand_h2(features, plan):
+    """fp16x3: two-term fp16 records scaled by the shape's maximum -> (xh, amax, the fp32 records they were split from)"""
+    xr, amax = _records_f32(features, plan)
+    _, B, C = features[:3]
+    xh = torch.empty(B, (C + 7) // 8, 2, plan.n_max, 8, dtype=torch.float16, device=xr.device)
+    L.check(L.lib().bdm_sparse_split_h2(B, C, plan.n_max, L.ptr(xr), L.ptr(amax), L.ptr(xh), L.stream()), "sparse_split_h2")
+    return xh, amax, xr
+
+
+def _operand_s3(features, plan):
+    """bf16x6: exact 3-way bf16 split (the weights are pre-split: sparse_conv_pack_s3)"""
+    f, B, C, n, bs_f, ld_f = features
+    xs = torch.empty(B, (C + 7) // 8, 3, plan.n_max, 8, dtype=torch.bfloat16, device=f.device)
+    L.check(L.lib().bdm_sparse_voxel_features_s3(B, C, n, plan.r, plan.n_max, L.ptr(f), bs_f, ld_f, L.ptr(plan.cnt),
+                                                 L.ptr(plan.ws), L.ptr(plan.occ_list), L.ptr(plan.n_occ), L.ptr(xs), L.stream()),
+            "sparse_voxel_features_s3")
+    return xs
+
+
+def _operand_f32(features, plan):
+    f, B, C, n, bs_f, ld_f = features
+    xs = torch.empty(B, C, plan.n_max, dtype=torch.float32, device=f.device)
+    L.check(L.lib().bdm_sparse_voxel_features(B, C, n, plan.r, plan.n_max, L.ptr(f), bs_f, ld_f, L.ptr(plan.cnt),
+                                              L.ptr(plan.ws), L.ptr(plan.occ_list), L.ptr(plan.n_occ), L.ptr(xs), L.stream()),
+            "sparse_voxel_features")
+    return xs
+
+
+def packed_format(wt):
+    """The PVConv.sparse_gemm name of a packed first-convolution weight, for callers that hold only the pack (tests, tools)."""
+    if isinstance(wt, tuple):
+        return {"h2": "sparse_h2", "fused": "sparse_fused"}[wt[0]]
+    return "sparse_s3" if wt.dtype == torch.bfloat16 else "sparse"
+
+
+def sparse_first_conv_planned(features, plan, wt, bias, cout, gn_groups=None, rows=None, h2_out=None, col_bias=None, impl=None):
     """Conv3d(k3, p1)(avg_voxelize(features)) on the occupied voxels of `plan`: (B, cout, r^3) fp32.
+    impl: the format of `wt` and the GEMM's arithmetic, "sparse_h2" (fp16x3: the default) | "sparse_s3" (bf16x6) | "sparse" (fp32) |
+    "sparse_fused" (one launch, no intermediate), as PVConv.route names it (None: packed_format(wt)).
     gn_groups: also return the GroupNorm(gn_groups) statistics of the output as (partial, slices = r*r, groups) -> (out, stats).
     rows (fp16x3 GEMM only): a VoxelRows the previous PVConv's tail left for this very plan -- the feature pass and the split are skipped.
     h2_out = (gn, act_scale, saturated) (fp16x3 GEMM on a small grid, small_grid_gather_ok): GroupNorm + Swish + the second convolution's
     operand split in the gather's epilogue -> ((B, cout/8, 2, r^3, 8) fp16, 1 / act_scale); the dense fp32 grid is not written.
     col_bias (B, 27 * cout) (fp16x3 / bf16x6 GEMM): per-shape addend of every occupied row's columns -- the share of input channels that are
     constant over a shape (the time embedding; `features` and `wt` then hold the other channels only: bdm_sparse_conv_gemm_s3_cb)."""
-    f, B, C, n, bs_f, ld_f = _bcl(features)
+    features = _bcl(features)
+    f, B, C = features[:3]
     dev, lib, r = f.device, L.lib(), plan.r
+    impl = impl or packed_format(wt)
     if col_bias is not None:
-        assert tuple(col_bias.shape) == (B, 27 * cout) and col_bias.stride(1) == 1 and h2_out is None
-
-    def gemm_h2(nb, b0, xh, amax, packed, inv_scale, y):
-        if col_bias is None:
-            L.check(lib.bdm_sparse_conv_gemm_h2(nb, plan.n_max, C, cout, L.ptr(xh[b0:]), L.ptr(amax[b0:]), L.ptr(packed), L.ptr(inv_scale),
-                                                L.ptr(plan.n_occ[b0:]), L.ptr(y), L.stream()), "sparse_conv_gemm_h2")
-        else:
-            L.check(lib.bdm_sparse_conv_gemm_h2_cb(nb, plan.n_max, C, cout, L.ptr(xh[b0:]), L.ptr(amax[b0:]), L.ptr(packed), L.ptr(inv_scale),
-                                                   L.ptr(plan.n_occ[b0:]), L.ptr(col_bias[b0:]), L.c_ll(col_bias.stride(0)), L.ptr(y), L.stream()), "sparse_conv_gemm_h2_cb")
-    if isinstance(wt, tuple) and wt[0] == "h2":  # fp16x3 GEMM (sparse_conv_pack_h2) + gather: the default
+        assert tuple(col_bias.shape) == (B, 27 * cout) and col_bias.stride(1) == 1 and h2_out is None and impl in ("sparse_h2", "sparse_s3")
+    if impl == "sparse_fused":  # GEMM + scatter in one launch (sparse_conv_pack_fused)
+        _, packed, inv_scale = wt
+        xr, amax = _records_f32(features, plan)
+        out = torch.empty(B, cout, r ** 3, dtype=torch.float32, device=dev)
+        L.check(L.experimental("bdm_sparse_conv_fused")(B, C, cout, r, plan.n_max, L.ptr(xr), L.ptr(amax), L.ptr(packed), L.ptr(inv_scale),
+                                          L.ptr(plan.occ_list), L.ptr(plan.n_occ), L.ptr(bias), L.ptr(out), L.stream()),
+                "sparse_conv_fused")
+        return (out, None) if gn_groups else out
+    if impl == "sparse_h2":  # (sparse_conv_pack_h2)
         _, packed, inv_scale = wt
         if rows is not None:
             assert rows.plan is plan and rows.channels == C
             xh, amax = rows.xh, rows.amax
         else:
-            xr = torch.empty(B, (C + 7) // 8, plan.n_max, 8, dtype=torch.float32, device=dev)
-            amax = amax_slots(dev, B)  # one activation scale per shape: a shape's result does not depend on its batch-mates
-            L.check(lib.bdm_sparse_voxel_features_f32(B, C, n, r, plan.n_max, L.ptr(f), bs_f, ld_f, L.ptr(plan.cnt), L.ptr(plan.ws),
-                                                      L.ptr(plan.occ_list), L.ptr(plan.n_occ), L.ptr(xr), L.ptr(amax), L.stream()),
-                    "sparse_voxel_features_f32")
-            xh = torch.empty(B, (C + 7) // 8, 2, plan.n_max, 8, dtype=torch.float16, device=dev)
-            L.check(lib.bdm_sparse_split_h2(B, C, plan.n_max, L.ptr(xr), L.ptr(amax), L.ptr(xh), L.stream()), "sparse_split_h2")
-        per_shape = plan.n_max * 27 * cout * 4
-        gb = max(1, min(B, SPARSE_Y_BYTES // max(per_shape, 1)))
-        y = torch.empty(gb, plan.n_max, 27 * cout, dtype=torch.float32, device=dev)
+            xh, amax, _ = _operand_h2(features, plan)   # (_: the fp32 records, which stay allocated while Y is)
+        gb, y = _y_buffer(plan, B, cout, dev)
+
+        def gemm(nb, b0):
+            if col_bias is None:
+                L.check(lib.bdm_sparse_conv_gemm_h2(nb, plan.n_max, C, cout, L.ptr(xh[b0:]), L.ptr(amax[b0:]), L.ptr(packed), L.ptr(inv_scale),
+                                                    L.ptr(plan.n_occ[b0:]), L.ptr(y), L.stream()), "sparse_conv_gemm_h2")
+            else:
+                L.check(lib.bdm_sparse_conv_gemm_h2_cb(nb, plan.n_max, C, cout, L.ptr(xh[b0:]), L.ptr(amax[b0:]), L.ptr(packed), L.ptr(inv_scale),
+                                                       L.ptr(plan.n_occ[b0:]), L.ptr(col_bias[b0:]), L.c_ll(col_bias.stride(0)), L.ptr(y), L.stream()), "sparse_conv_gemm_h2_cb")
         if h2_out is not None:
             gn1, act_scale, saturated = h2_out
             x2 = torch.empty(B, cout // 8, 2, r ** 3, 8, dtype=torch.float16, device=dev)
             for b0 in range(0, B, gb):
                 nb = min(gb, B - b0)
-                L.check(lib.bdm_sparse_conv_gemm_h2(nb, plan.n_max, C, cout, L.ptr(xh[b0:]), L.ptr(amax[b0:]), L.ptr(packed), L.ptr(inv_scale),
-                                                    L.ptr(plan.n_occ[b0:]), L.ptr(y), L.stream()), "sparse_conv_gemm_h2")
+                gemm(nb, b0)
                 L.check(L.experimental("bdm_sparse_conv_gather_h2_small")(nb, cout, r, plan.n_max, L.ptr(y), L.ptr(plan.occ_index[b0:]), L.ptr(bias),
                                                             gn1.num_groups, L.ptr(gn1.weight), L.ptr(gn1.bias), L.c_float(gn1.eps),
                                                             L.c_float(act_scale), L.ptr(x2[b0:]), L.ptr(saturated), L.stream()),
                         "sparse_conv_gather_h2_small")
             return x2, 1.0 / act_scale
         out = torch.empty(B, cout, r ** 3, dtype=torch.float32, device=dev)
-        gn, stats = None, None
-        if gn_groups and gather_gn_ok(cout, gn_groups):
-            partial = torch.empty(B, gn_groups, r * r, 2, dtype=torch.float64, device=dev)
-            gn, stats = (partial, int(gn_groups)), (partial, r * r, int(gn_groups))
-        for b0 in range(0, B, gb):
-            nb = min(gb, B - b0)
-            gemm_h2(nb, b0, xh, amax, packed, inv_scale, y)
-            _gather(lib, nb, cout, r, plan, b0, y, bias, out, gn)
-        return (out, stats) if gn_groups else out
-    if isinstance(wt, tuple):  # fused kernel (sparse_conv_pack_fused): GEMM + scatter in one launch, no intermediate
-        assert col_bias is None
-        _, packed, inv_scale = wt
-        xr = torch.empty(B, (C + 7) // 8, plan.n_max, 8, dtype=torch.float32, device=dev)
-        amax = amax_slots(dev, B)  # one activation scale per shape: a shape's result does not depend on its batch-mates
-        L.check(lib.bdm_sparse_voxel_features_f32(B, C, n, r, plan.n_max, L.ptr(f), bs_f, ld_f, L.ptr(plan.cnt), L.ptr(plan.ws),
-                                                  L.ptr(plan.occ_list), L.ptr(plan.n_occ), L.ptr(xr), L.ptr(amax), L.stream()),
-                "sparse_voxel_features_f32")
-        out = torch.empty(B, cout, r ** 3, dtype=torch.float32, device=dev)
-        L.check(L.experimental("bdm_sparse_conv_fused")(B, C, cout, r, plan.n_max, L.ptr(xr), L.ptr(amax), L.ptr(packed), L.ptr(inv_scale),
-                                          L.ptr(plan.occ_list), L.ptr(plan.n_occ), L.ptr(bias), L.ptr(out), L.stream()),
-                "sparse_conv_fused")
-        return (out, None) if gn_groups else out
-    out = torch.empty(B, cout, r ** 3, dtype=torch.float32, device=dev)
-    # The 27x-expanded intermediate Y (n_occ x 27*cout fp32 per shape) is written by the GEMM and read once by the gather.
-    # Shapes are processed in groups whose Y stays within SPARSE_Y_BYTES (256 MiB, about the memory-side cache),
-    # reusing ONE Y buffer.  Measured (tools/sparse_bench.py): two groups of 8 at the 64 -> 64 / 32^3 layer: 287 -> 261 us;
-    # smaller groups lose more to the extra launches than they gain.
-    per_shape = plan.n_max * 27 * cout * 4
-    gb = max(1, min(B, SPARSE_Y_BYTES // max(per_shape, 1)))
-    y = torch.empty(gb, plan.n_max, 27 * cout, dtype=torch.float32, device=dev)
-    s3 = wt.dtype == torch.bfloat16  # bf16x6: pre-split operands (sparse_conv_pack_s3)
-    G8 = (C + 7) // 8
-    if s3:
-        xs = torch.empty(B, G8, 3, plan.n_max, 8, dtype=torch.bfloat16, device=dev)
-        L.check(lib.bdm_sparse_voxel_features_s3(B, C, n, r, plan.n_max, L.ptr(f), bs_f, ld_f, L.ptr(plan.cnt),
-                                                 L.ptr(plan.ws), L.ptr(plan.occ_list), L.ptr(plan.n_occ), L.ptr(xs), L.stream()),
-                "sparse_voxel_features_s3")
     else:
-        xs = torch.empty(B, C, plan.n_max, dtype=torch.float32, device=dev)
-        L.check(lib.bdm_sparse_voxel_features(B, C, n, r, plan.n_max, L.ptr(f), bs_f, ld_f, L.ptr(plan.cnt),
-                                              L.ptr(plan.ws), L.ptr(plan.occ_list), L.ptr(plan.n_occ), L.ptr(xs), L.stream()),
-                "sparse_voxel_features")
-    gn, stats = None, None
-    if gn_groups and gather_gn_ok(cout, gn_groups):
-        partial = torch.empty(B, gn_groups, r * r, 2, dtype=torch.float64, device=dev)
-        gn, stats = (partial, int(gn_groups)), (partial, r * r, int(gn_groups))
-    for b0 in range(0, B, gb):
-        nb = min(gb, B - b0)
-        if s3 and col_bias is not None:
-            L.check(lib.bdm_sparse_conv_gemm_s3_cb(nb, plan.n_max, C, 27 * cout, L.ptr(xs[b0:]), L.ptr(wt), L.ptr(plan.n_occ[b0:]),
-                                                   L.ptr(col_bias[b0:]), L.c_ll(col_bias.stride(0)), L.ptr(y), L.stream()), "sparse_conv_gemm_s3_cb")
-        elif s3:
-            L.check(lib.bdm_sparse_conv_gemm_s3(nb, plan.n_max, C, 27 * cout, L.ptr(xs[b0:]), L.ptr(wt), L.ptr(plan.n_occ[b0:]),
-                                                L.ptr(y), L.stream()), "sparse_conv_gemm_s3")
-        else:
-            assert col_bias is None
-            L.check(lib.bdm_sparse_conv_gemm(nb, plan.n_max, C, 27 * cout, L.ptr(xs[b0:]), L.ptr(wt), L.ptr(plan.n_occ[b0:]),
-                                             L.ptr(y), L.stream()), "sparse_conv_gemm")
-        _gather(lib, nb, cout, r, plan, b0, y, bias, out, gn)
-    return (out, stats) if gn_groups else out
+        out = torch.empty(B, cout, r ** 3, dtype=torch.float32, device=dev)
+        gb, y = _y_buffer(plan, B, cout, dev)
+        xs = (_operand_s3 if impl == "sparse_s3" else _operand_f32)(features, plan)
+        name = {"sparse_s3": "bdm_sparse_conv_gemm_s3", "sparse": "bdm_sparse_conv_gemm"}[impl] + ("" if col_bias is None else "_cb")
+        fn = getattr(lib, name)
+
+        def gemm(nb, b0):
+            cb = () if col_bias is None else (L.ptr(col_bias[b0:]), L.c_ll(col_bias.stride(0)))
+            L.check(fn(nb, plan.n_max, C, 27 * cout, L.ptr(xs[b0:]), L.ptr(wt), L.ptr(plan.n_occ[b0:]), *cb, L.ptr(y), L.stream()), name[4:])
+    return _gather_groups(plan, B, cout, bias, gn_groups, gemm, gb, y, out)
 
 
 def sparse_conv_pack_os(weight, form="dil"):
@@ -1371,12 +1386,8 @@ def sparse_first_conv_os(features, plan, packed, bias, cout, gn_groups=None, com
     f, B, C, n, bs_f, ld_f = _bcl(features)
     dev, lib, r = f.device, L.lib(), plan.r
     packed_w, inv_scale = packed
-    xr = torch.empty(B, (C + 7) // 8, plan.n_max, 8, dtype=torch.float32, device=dev)
-    slots = amax_slots(dev, B + 1)            # B activation-scale maxima + the convolution's work counter (zero bits = int 0)
+    xr, slots = _records_f32((f, B, C, n, bs_f, ld_f), plan, extra=1)   # B activation-scale maxima + the convolution's work counter (zero bits = int 0)
     amax, counter = slots[:B], slots[B:]
-    L.check(lib.bdm_sparse_voxel_features_f32(B, C, n, r, plan.n_max, L.ptr(f), bs_f, ld_f, L.ptr(plan.cnt), L.ptr(plan.ws),
-                                              L.ptr(plan.occ_list), L.ptr(plan.n_occ), L.ptr(xr), L.ptr(amax), L.stream()),
-            "sparse_voxel_features_f32")
     if compact:
         y = torch.empty(B, plan.n_dil_max, cout, dtype=torch.float32, device=dev)
         out = CompactGrid(y, plan, bias, cout)
@@ -1479,11 +1490,7 @@ def devoxelize_gn_gate_add_rows(norm_coords, rows, class_vals, plan, coef, gate=
     n = norm_coords.shape[2]
     out = torch.empty(B, C, n, dtype=torch.float32, device=rows.device)
     _, _, _, _, bs_o, ld_o = _bcl(out)
-    if add is not None:
-        aa, _, _, _, bs_a, ld_a = _bcl(add)
-        assert aa.data_ptr() == add.data_ptr()
-    else:
-        bs_a, ld_a = 0, 0
+    bs_a, ld_a = _addend_strides(add)
     lib = L.lib()
     args = (B, C, n, plan.r, L.ptr(norm_coords), L.ptr(rows), plan.n_dil_max, L.ptr(plan.d2_index), L.ptr(class_vals), L.ptr(coef), L.ptr(gate),
             L.ptr(add), bs_a, ld_a)
@@ -1556,23 +1563,12 @@ def sparse_first_conv(features, vox_coords, r, wt, bias, cout):
     """Conv3d(k3, p1)(avg_voxelize(features, vox_coords, r)) evaluated on the occupied voxels: (B, cout, r^3) fp32.
     Builds a one-off plan from integer voxel coordinates (the modules share cached plans: voxel_plan)."""
     B, _, n = vox_coords.shape
-    dev, lib, r3 = vox_coords.device, L.lib(), r ** 3
-    p = VoxelPlan()
-    p.ready = None
-    p.r, p.n, p.n_max = int(r), n, min(n, r3)
-    p.norm_coords, p.vox_coords = None, vox_coords
-    p.ind = torch.empty(B, n, dtype=torch.int32, device=dev)
-    p.cnt = torch.empty(B, r3, dtype=torch.int32, device=dev)
-    p.ws = torch.empty(lib.bdm_voxelize_workspace_bytes(B, n, r), dtype=torch.uint8, device=dev)
+    lib = L.lib()
+    p = VoxelPlan(vox_coords, r)
     L.check(lib.bdm_voxelize_plan(B, n, r, L.ptr(vox_coords), L.ptr(p.ind), L.ptr(p.cnt), L.ptr(p.ws), L.stream()), "voxelize_plan")
-    p.occ_index = torch.empty(B, r3, dtype=torch.int32, device=dev)
-    p.occ_list = torch.empty(B, p.n_max, dtype=torch.int32, device=dev)
-    p.n_occ = torch.empty(B, dtype=torch.int32, device=dev)
-    p.rowocc = torch.empty(B, r * r, dtype=torch.uint8, device=dev)
     L.check(lib.bdm_voxel_compact(B, r, p.n_max, L.ptr(p.cnt), L.ptr(p.occ_index), L.ptr(p.occ_list), L.ptr(p.n_occ), L.stream()),
             "voxel_compact")
     L.check(lib.bdm_voxel_row_occupancy(B, r, L.ptr(p.cnt), L.ptr(p.rowocc), L.stream()), "voxel_row_occupancy")
-    p.dil_list = None
     if isinstance(wt, tuple) and wt[0] in ("dil", "dil_compact"):
         out = sparse_first_conv_os(features, plan_dilation(p), wt[1:], bias, cout, compact=wt[0] == "dil_compact")
         return out.dense() if wt[0] == "dil_compact" else out

@@ -98,14 +98,20 @@ def create_classifier(in_channels, dropout, num_classes, width_multiplier=1):
 def run_blocks(blocks, inputs):
     """nn.Sequential protocol of the reference: every block maps a tuple to a tuple."""
     if isinstance(blocks, nn.Sequential):
-        mods = list(blocks)
-        for i, blk in enumerate(mods):
-            if isinstance(blk, PVConv):
-                # (not a submodule registration: the successor is only looked at, PVConv._head_for_next)
-                blk.__dict__["_next_pv"] = mods[i + 1] if i + 1 < len(mods) and isinstance(mods[i + 1], PVConv) else None
+        link_pvconvs(blocks)
+        for blk in blocks:
             inputs = blk(inputs)
         return inputs
     return blocks(inputs)
+
+
+def link_pvconvs(blocks):
+    """Every PVConv of a Sequential learns its successor (PVConv.route: the tail may leave it its first-convolution operand)."""
+    mods = list(blocks)
+    for i, blk in enumerate(mods):
+        if isinstance(blk, PVConv):
+            # (not a submodule registration: the successor is only looked at)
+            blk.__dict__["_next_pv"] = mods[i + 1] if i + 1 < len(mods) and isinstance(mods[i + 1], PVConv) else None
 
 
 def run_classifier(classifier, features):
@@ -198,33 +204,26 @@ def plan_sampling_chain(sa_layers, coords, early=None, fp_layers=None):
         # the voxel plan of the NEXT level's PVConvs (sort of the centres into cells, occupied-cell lists) is geometry
         # too: one single-workgroup-per-shape kernel that would otherwise sit on the main stream's critical path
         nxt = sa_layers[li + 1] if li + 1 < len(sa_layers) else None
-        pv = nxt[0] if isinstance(nxt, nn.Sequential) and hasattr(nxt[0], "voxel_plan_args") else None
-        args = pv.voxel_plan_args() if (pv is not None and SIDE_PLAN) else None
-        if args is not None:
-            plan = ops.voxel_plan(centers, *args, dilate=2 if pv.wants_compact_tail(centers.shape[0], centers.shape[2]) else
-                                  (1 if pv.wants_dilated_plan(centers.shape[0], centers.shape[2]) else 0))
+        if SIDE_PLAN and isinstance(nxt, nn.Sequential) and isinstance(nxt[0], PVConv):
+            plan_ahead(nxt[0], centers)
+        return centers
+
+    def plan_ahead(pv, points, unless_cached=False):
+        """(side stream) the voxel plan of `pv` on `points`, with the voxel lists its route will want"""
+        route = pv.route(points.shape[0], points.shape[2])
+        if route.plan_args is not None and not (unless_cached and ops.has_voxel_plan(points, route.plan_args[0])):
+            plan = ops.voxel_plan(points, *route.plan_args, dilate=route.dilate)
             plan.ready = torch.cuda.Event()
             tape.record_event(plan.ready, side)
-        return centers
 
     # voxel plans of the DECODER's PVConvs: an FP stage's points are an encoder level's points (coords_list), so its plan is usually the
     # one an encoder PVConv of the same resolution already made; where there is none (FP0: the 64 points SA3 reads, which has no PVConv)
     # the two launches (voxel coordinates + plan) would sit on the main stream's critical path: they are geometry, planned here
     wanted = {}
     for i, blk in enumerate(fp_layers if fp_layers is not None else ()):
-        pv = next((m for m in blk if hasattr(m, "voxel_plan_args")), None) if isinstance(blk, nn.Sequential) else None
-        args = pv.voxel_plan_args() if (pv is not None and SIDE_PLAN and DECODER_PLAN) else None
-        if args is not None:
-            wanted[i] = (pv, args)
-
-    def decoder_plan(points, fp_index):
-        """(side stream) the plan of FP stage fp_index, whose points these are, unless the cache holds it already"""
-        pv, args = wanted.get(fp_index, (None, None))
-        if pv is not None and not ops.has_voxel_plan(points, args[0]):
-            plan = ops.voxel_plan(points, *args, dilate=2 if pv.wants_compact_tail(points.shape[0], points.shape[2]) else
-                                  (1 if pv.wants_dilated_plan(points.shape[0], points.shape[2]) else 0))
-            plan.ready = torch.cuda.Event()
-            tape.record_event(plan.ready, side)
+        pv = next((m for m in blk if isinstance(m, PVConv)), None) if isinstance(blk, nn.Sequential) else None
+        if pv is not None and SIDE_PLAN and DECODER_PLAN:
+            wanted[i] = pv
 
     def remaining(c):
         with torch.cuda.stream(side):
@@ -233,7 +232,8 @@ def plan_sampling_chain(sa_layers, coords, early=None, fp_layers=None):
                 c = level(li, c, None)
                 cents.append(c)
                 if li + 1 < len(sa_layers):   # these centres are level li + 1's points = FP stage (L - 2 - li)'s points (decode: coords_list[-1 - i])
-                    decoder_plan(c, len(sa_layers) - 2 - li)
+                    if len(sa_layers) - 2 - li in wanted:   # (unless the cache holds that stage's plan already)
+                        plan_ahead(wanted[len(sa_layers) - 2 - li], c, unless_cached=True)
             # the 3-NN searches of the feature-propagation modules are geometry too (level i's points against level i + 1's
             # centres): four launches that leave the main stream's critical path; an FP module finds its pair in NN_PLANS
             if SIDE_NN:
@@ -426,14 +426,12 @@ class PVCNN2Base(nn.Module):
 
     def _hoist_complete(self, hoisted, cond, inputs):
         """True when NO layer of this forward reads rows 3.. of the conditioned input: its three readers -- the point branch and the
-        first convolution of the first PVConv, the skip input of the last FP module -- all take the hoisted maps (the conditions of
-        PVConv._point_branch, PVConv.forward and PointNetFPModule.forward, restated)."""
+        first convolution of the first PVConv, the skip input of the last FP module -- all take the hoisted maps (PVConv._point_branch,
+        PVConv.route and PointNetFPModule.forward)."""
         if len(hoisted) != 2 or cond.x_cf.data_ptr() != inputs.data_ptr():
             return False
         first, last = hoisted
-        conv1 = first.voxel_layers[0]
-        return (len(first.point_features.layers) == 3 and isinstance(conv1, nn.Conv3d) and 27 * conv1.out_channels <= 1024
-                and first.conv_impl in ("bf16x6", "fp16x3") and first.sparse_first_conv and first.resolution in first.sparse_resolutions
+        return (len(first.point_features.layers) == 3 and first.route(inputs.shape[0], inputs.shape[2], hoisted=True).first == "map"
                 and getattr(last, "two_source", False) and inputs.shape[1] - 3 == cond.C)
 
     def _hoist_targets(self, cond, inputs):
