@@ -27,6 +27,8 @@ class RunConfig:  # structured.py:14-56
     freeze_feature_model: bool = True
     interact_timestep: Optional[List] = None
     max_fusion_steps: int = 20000
+    coloring_training_noise_std: float = 0.0  # structured.py:45-46
+    coloring_sample_dir: Optional[str] = None
     save_dir: Optional[str] = None
     # not in the reference: "reference" = its draws (CPU generator for the initial cloud and the blend masks, the device's
     # global generator for DDPM / PVD noise, seeded seed + rank); "per_shape" = Philox streams keyed by (seed, global
@@ -72,6 +74,32 @@ class PointCloudDiffusionModelConfig:  # structured.py:73-111
 
     def as_kwargs(self):
         return asdict(self)
+
+
+@dataclass
+class PointCloudColoringModelConfig:  # structured.py:114-124 on PointCloudProjectionModelConfig (73-98); stored as model=coloring_model
+    image_size: int = 224
+    image_feature_model: str = "vit_small_patch16_224_msn"
+    use_local_colors: bool = True
+    use_local_features: bool = True
+    use_global_features: bool = False
+    use_mask: bool = False
+    use_distance_transform: bool = False
+    scale_factor: float = 1.0
+    colors_mean: float = 0.5
+    colors_std: float = 0.5
+    color_channels: int = 3
+    predict_shape: bool = False
+    predict_color: bool = True
+    point_cloud_model: str = "pvcnn"
+    point_cloud_model_layers: int = 1
+    point_cloud_model_embed_dim: int = 64
+
+    def as_kwargs(self):
+        return asdict(self)
+
+
+MODEL_GROUPS = {"diffusion_model": PointCloudDiffusionModelConfig, "coloring_model": PointCloudColoringModelConfig}  # structured.py:303-306
 
 
 @dataclass
@@ -137,6 +165,10 @@ def parse_overrides(argv, cfg: Optional[ProjectConfig] = None) -> ProjectConfig:
         if len(parts) == 1:
             if parts[0] == "dataset":  # config-group selection: dataset=shapenet_r2n2 | pix3d | synthetic
                 cfg.dataset.type = str(value)
+                continue
+            if parts[0] == "model" and value == "coloring_model":  # config-group selection; any other name keeps the diffusion model
+                if not isinstance(cfg.model, PointCloudColoringModelConfig):
+                    cfg.model = PointCloudColoringModelConfig()
                 continue
             if parts[0] in _IGNORED_GROUPS or parts[0] == "model":
                 continue

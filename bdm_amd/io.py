@@ -21,8 +21,41 @@ def save_pointcloud_ply(points, path, binary=True):
             np.savetxt(f, pts, fmt="%.9g")
 
 
-def load_pointcloud_ply(path):
-    """(n, 3) float32 from an ASCII or binary-little-endian PLY whose vertex element starts with float x, y, z."""
+def save_pointcloud_ply_rgb(points, colors, path):
+    """Binary little-endian PLY with float32 x, y, z and uchar red, green, blue per vertex (what pytorch3d's save_pointcloud writes
+    for a coloured cloud with colors_as_uint8=True); colours in [0, 1] are stored as round(255 c)."""
+    pts = np.asarray(points, dtype="<f4").reshape(-1, 3)
+    col = np.asarray(colors, dtype=np.float64).reshape(-1, 3)
+    if col.shape[0] != pts.shape[0]:
+        raise ValueError(f"{pts.shape[0]} points but {col.shape[0]} colours")
+    rec = np.empty(pts.shape[0], dtype=[("xyz", "<f4", 3), ("rgb", "u1", 3)])
+    rec["xyz"] = pts
+    rec["rgb"] = np.rint(np.clip(col, 0.0, 1.0) * 255.0).astype(np.uint8)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    header = (f"ply\nformat binary_little_endian 1.0\nelement vertex {pts.shape[0]}\nproperty float x\nproperty float y\n"
+              "property float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(rec.tobytes())
+
+
+def _ply_colors(props, column):
+    """Per-vertex colours in [0, 1] from the red / green / blue properties (uchar: / 255; float: as stored); column(i) -> the
+    values of property i as a numpy array."""
+    names = [p[2] for p in props]
+    if not all(c in names for c in ("red", "green", "blue")):
+        raise ValueError("the PLY has no red / green / blue vertex properties")
+    cols = []
+    for c in ("red", "green", "blue"):
+        i = names.index(c)
+        v = column(i).astype(np.float32)
+        cols.append(v / np.float32(255.0) if props[i][1] in ("uchar", "uint8") else v)
+    return np.stack(cols, axis=1)
+
+
+def load_pointcloud_ply(path, with_colors=False):
+    """(n, 3) float32 from an ASCII or binary-little-endian PLY whose vertex element starts with float x, y, z.
+    with_colors=True: (points, colors), colors (n, 3) float32 in [0, 1] from its red / green / blue properties."""
     with open(path, "rb") as f:
         raw = f.read()
     end = raw.index(b"end_header\n") + len(b"end_header\n")
@@ -32,7 +65,11 @@ def load_pointcloud_ply(path):
     props = [l.split() for l in head if l.startswith("property")]
     if fmt == "ascii":
         rows = raw[end:].decode("ascii").split("\n")[:n]
-        return np.array([[float(v) for v in r.split()[:3]] for r in rows], dtype=np.float32).reshape(-1, 3)
+        pts = np.array([[float(v) for v in r.split()[:3]] for r in rows], dtype=np.float32).reshape(-1, 3)
+        if not with_colors:
+            return pts
+        table = np.array([[float(v) for v in r.split()] for r in rows], dtype=np.float64).reshape(n, -1)
+        return pts, _ply_colors(props, lambda i: table[:, i])
     if fmt != "binary_little_endian":
         raise ValueError(f"{path}: unsupported PLY format {fmt}")
     sizes = {"float": 4, "float32": 4, "double": 8, "float64": 8, "uchar": 1, "uint8": 1, "int": 4, "int32": 4}
@@ -40,7 +77,15 @@ def load_pointcloud_ply(path):
     if [p[1] for p in props[:3]] not in (["float"] * 3, ["float32"] * 3):
         raise ValueError(f"{path}: vertex element must start with float x, y, z")
     body = np.frombuffer(raw, dtype=np.uint8, count=n * stride, offset=end).reshape(n, stride)
-    return np.ascontiguousarray(body[:, :12]).view("<f4").reshape(n, 3).astype(np.float32)
+    pts = np.ascontiguousarray(body[:, :12]).view("<f4").reshape(n, 3).astype(np.float32)
+    if not with_colors:
+        return pts
+    offs = np.cumsum([0] + [sizes[p[1]] for p in props])
+    kinds = {"float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8", "uchar": "u1", "uint8": "u1", "int": "<i4", "int32": "<i4"}
+
+    def column(i):
+        return np.ascontiguousarray(body[:, offs[i]:offs[i + 1]]).view(kinds[props[i][1]]).reshape(n)
+    return pts, _ply_colors(props, column)
 
 
 def save_image_png(image_chw, path):

@@ -141,8 +141,10 @@ class PointCloudProjectionModel(_DeviceMixin, nn.Module):
         self.predict_shape, self.predict_color, self.process_color = predict_shape, predict_color, process_color
         self.image_color_channels, self.color_channels = image_color_channels, color_channels
         self.colors_mean, self.colors_std = colors_mean, colors_std
-        if use_global_features or predict_color or process_color:
-            raise NotImplementedError("global features / colour prediction are not used by the BDM recipes (config/structured.py:80-90)")
+        if use_global_features or process_color or (predict_color and predict_shape):
+            # predict_color alone (with predict_shape off) is the colouring model's configuration (config/structured.py:115-124)
+            raise NotImplementedError("global features / colour as an input / joint shape and colour prediction are not used by the "
+                                      "BDM recipes (config/structured.py:80-90)")
         if use_distance_transform and not use_mask:
             raise ValueError("No mask for distance transform?")  # projection_model.py:119-120
         if raster_points_per_pixel != 1:
@@ -153,7 +155,7 @@ class PointCloudProjectionModel(_DeviceMixin, nn.Module):
         self.in_channels = 3 + (image_color_channels if use_local_colors else 0) + \
             (self.feature_model.feature_dim if use_local_features else 0) + \
             ((2 if use_distance_transform else 1) if use_mask else 0)  # projection_model.py:67-77
-        self.out_channels = 3
+        self.out_channels = (3 if predict_shape else 0) + (color_channels if predict_color else 0)  # projection_model.py:80-84
         self.raster_point_radius = raster_point_radius
         self._cond_cache = None
 
@@ -233,13 +235,22 @@ class PointCloudProjectionModel(_DeviceMixin, nn.Module):
         return pix
 
     def point_cloud_to_tensor(self, pc, normalize=False, scale=False):
+        """projection_model.py:159-168: with colours if and only if predict_color and the cloud carries them."""
         if isinstance(pc, torch.Tensor):
             return pc
-        return pc.points_padded() * (self.scale_factor if scale else 1)
+        points = pc.points_padded() * (self.scale_factor if scale else 1)
+        if self.predict_color and pc.features_padded() is not None:
+            colors = self.normalize(pc.features_padded()) if normalize else pc.features_padded()
+            return torch.cat((points, colors), dim=2)
+        return points
 
     def tensor_to_point_cloud(self, x, denormalize=False, unscale=False):
+        """projection_model.py:170-177."""
+        points = x[:, :, :3] / (self.scale_factor if unscale else 1)
+        if self.predict_color:
+            return Pointclouds(points=points, features=self.denormalize(x[:, :, 3:]) if denormalize else x[:, :, 3:])
         assert x.shape[2] == 3
-        return Pointclouds(points=x[:, :, :3] / (self.scale_factor if unscale else 1))
+        return Pointclouds(points=points)
 
     @torch.no_grad()
     def get_input_with_conditioning(self, x_t, camera, image_rgb, mask, t, lazy=False):
@@ -530,9 +541,48 @@ class PointCloudFusionModel(PointCloudProjectionModel):
         return scheduler.step(noise_pred, t, pred_from_recon).prev_sample
 
 
+class PointCloudColoringModel(PointCloudProjectionModel):
+    """model_coloring.py:13-81: one feed-forward pass that paints a cloud from the image it was reconstructed from.  The projection
+    conditioning of the (optionally jittered) points goes through a PointCloudTransformerModel (bdm_amd/transformer.py), whose
+    forward_colors ends in the colour head, the denormalisation and its clamp.  Inference only."""
+
+    def __init__(self, point_cloud_model: str, point_cloud_model_layers: int, point_cloud_model_embed_dim: int, **kwargs):
+        super().__init__(**kwargs)
+        if self.predict_shape or not self.predict_color:
+            raise NotImplementedError("Must predict color, not shape, for coloring")
+        from .transformer import PointCloudTransformerModel
+        self.point_cloud_model = PointCloudTransformerModel(num_layers=point_cloud_model_layers, model_type=point_cloud_model,
+                                                            embed_dim=point_cloud_model_embed_dim, in_channels=self.in_channels,
+                                                            out_channels=self.out_channels)
+
+    @torch.no_grad()
+    def _forward(self, pc, camera, image_rgb: Optional[Tensor], mask: Optional[Tensor], return_point_cloud: bool = False,
+                 noise_std: float = 0.0):
+        if not return_point_cloud:  # the colour regression loss (model_coloring.py:67-69)
+            raise NotImplementedError("training is out of scope for the MI355X sampling path")
+        x = self.point_cloud_to_tensor(pc, normalize=True, scale=True)
+        x_points = x[:, :, :3]
+        x_input = x_points + torch.randn_like(x_points) * noise_std if noise_std else x_points
+        x_input = self.get_input_with_conditioning(x_input, camera=camera, image_rgb=image_rgb, mask=mask, t=None)
+        colors = self.point_cloud_model.forward_colors(x_input, self.colors_mean, self.colors_std)   # denormalised, clamped
+        return Pointclouds(points=x_points / self.scale_factor, features=colors)
+
+    def forward(self, batch, **kwargs):
+        if isinstance(batch, dict):
+            from .data import FrameData
+            batch = FrameData(**batch)
+        return self._forward(pc=batch.sequence_point_cloud, camera=batch.camera, image_rgb=batch.image_rgb,
+                             mask=batch.fg_probability, **kwargs)
+
+
 def get_model(cfg):
     """model/__init__.py:7-11."""
     return ConditionalPointCloudDiffusionModel(**cfg.model.as_kwargs())
+
+
+def get_coloring_model(cfg):
+    """model/__init__.py:14-18."""
+    return PointCloudColoringModel(**cfg.model.as_kwargs())
 
 
 def get_fusion_model(cfg, pvd_model, pc2_model):

@@ -798,6 +798,29 @@ int bdm_pairwise_chamfer_variant(int s, int r, int n, int *p, int *tj);
  * n above 2048 returns 3 (unsupported). */
 int bdm_pairwise_emd_approx(int s, int r, int n, const float *a, const float *b, float *out, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * 8. PC^2 colouring model (experiments/model/model_coloring.py, point_cloud_transformer_model.py:13-80 with
+ *    use_attn = False), csrc/color_block.hip.  Tokens are channel-first (b, e, n); e = 64 is the only width the
+ *    configuration reaches, any other returns 3 (unsupported) and writes nothing.  A point's results depend on that
+ *    point alone: not on b, n or the tile it falls in.
+ * ---------------------------------------------------------------------------------- */
+/* floats of the packed fc1 / fc2 record of one block (0 for an unsupported e) */
+size_t bdm_color_block_packed_elems(int e);
+/* fc1_w (4e, e), fc2_w (e, 4e) row-major (timm Mlp) -> packed: first [k][s][l] = fc1_w[32 k + (l & 31)][s + 32 (l >> 5)]
+ * (k < 8, s < 32, l < 64), then [k][o][r][l] = fc2_w[32 o + (l & 31)][32 k + (r & 3) + 8 (r >> 2) + 4 (l >> 5)] (o < 2, r < 16). */
+int bdm_color_block_pack_weights(int e, const float *fc1_w, const float *fc2_w, float *packed, void *stream);
+/* Second half of one PointCloudModelBlock, per point: r = h + p (p: the block's PVCNN output), y = r + fc2(gelu(fc1(LN(r))))
+ * with LN = LayerNorm(e) (norm2: biased variance, eps inside the root) and the exact (erf) GELU; y (b, e, n) is always written
+ * and must not alias h or p.  At most one of:
+ *   ln_next (b, e, n) = LayerNorm(y) with next_w / next_b / next_eps (the next block's norm0);
+ *   colors (b, n, 3) point-major = clamp((out_w y + out_b) * colors_std + colors_mean, 0, 1), out_w (3, e) row-major
+ * selected by a non-NULL pointer.  fp32 arithmetic, fp32-input MFMA contractions; the 4e-wide hidden vector is never stored. */
+int bdm_color_block_tail(int b, int e, int n, const float *h, const float *p, const float *norm2_w,
+                         const float *norm2_b, float norm2_eps, const float *w_packed, const float *fc1_b,
+                         const float *fc2_b, float *y, const float *next_w, const float *next_b, float next_eps,
+                         float *ln_next, const float *out_w, const float *out_b, float colors_mean,
+                         float colors_std, float *colors, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
