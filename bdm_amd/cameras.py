@@ -13,6 +13,7 @@ class PerspectiveCameras:
     """in_ndc=False (screen-space intrinsics + image_size (H, W), as dataset/pix3d.py:152-159 builds them) is converted
     to NDC at construction with pytorch3d's rule (docs/notes/cameras.md, restated; unpinned: pytorch3d is absent):
         s = min(W, H);  focal_ndc = focal_screen * 2 / s;  principal_ndc = -(principal_screen - (W, H) / 2) * 2 / s"""
+    orthographic = False   # (OrthographicCameras below: the same fields, projected without the division by depth)
 
     def __init__(self, focal_length=1.0, principal_point=((0.0, 0.0),), R=None, T=None, device="cpu", in_ndc=True,
                  image_size=None):
@@ -22,6 +23,8 @@ class PerspectiveCameras:
                 v = v.view(1, 1).expand(n, 2)
             elif v.dim() == 1:
                 v = v.view(-1, 1).expand(-1, 2) if v.shape[0] == n and n != 2 else v.view(1, -1).expand(n, -1)
+            elif v.shape[0] == 1:
+                v = v.expand(n, -1)   # one row for n cameras (the default principal point with batched R, T)
             return v.contiguous()
         R = torch.eye(3)[None] if R is None else torch.as_tensor(R, dtype=torch.float32)
         T = torch.zeros(1, 3) if T is None else torch.as_tensor(T, dtype=torch.float32)
@@ -48,21 +51,51 @@ class PerspectiveCameras:
         return self.R.device
 
     def clone(self):
-        return PerspectiveCameras(self.focal_length.clone(), self.principal_point.clone(), self.R.clone(), self.T.clone(),
-                                  device=self.R.device)
+        return type(self)(self.focal_length.clone(), self.principal_point.clone(), self.R.clone(), self.T.clone(),
+                          device=self.R.device)
 
     def to(self, device):
-        return PerspectiveCameras(self.focal_length, self.principal_point, self.R, self.T, device=device)
+        return type(self)(self.focal_length, self.principal_point, self.R, self.T, device=device)
 
     def packed(self):
         """(n, 16) float32: R row-major, T, focal, principal point -- the layout bdm_rasterize_points takes."""
         return torch.cat([self.R.reshape(-1, 9), self.T, self.focal_length, self.principal_point], dim=1).contiguous()
 
 
+class OrthographicCameras(PerspectiveCameras):
+    """pytorch3d's OrthographicCameras (restated; unpinned: pytorch3d is absent): the same constructor, fields and packed() layout as
+    PerspectiveCameras, without the division by the view depth: ndc.xy = focal * X_view.xy + principal_point.  Only the renderer
+    (bdm_amd/render.py) takes one: the projection conditioning of the models is perspective."""
+    orthographic = True
+
+
+def look_at_view_transform(dist=1.0, elev=0.0, azim=0.0, degrees=True, device="cpu"):
+    """R (n, 3, 3), T (n, 3) of cameras at distance `dist`, elevation `elev` and azimuth `azim` looking at the world origin with
+    +Y up, by pytorch3d's construction (renderer/cameras.py look_at_view_transform, restated; unpinned: pytorch3d is absent):
+        C = dist * (cos e sin a, sin e, cos e cos a);  z = normalize(-C), x = normalize(cross(up, z)), y = normalize(cross(z, x));
+        R has x, y, z as COLUMNS (row-vector convention X_view = X_world R + T);  T = -R^T C.
+    Scalars, lists or tensors, broadcast against each other.  Where the view direction is parallel to `up` (elev = +-90), x is
+    replaced by normalize(cross(y, z)) as pytorch3d does."""
+    dist, elev, azim = torch.broadcast_tensors(*[torch.as_tensor(v, dtype=torch.float32).reshape(-1) for v in (dist, elev, azim)])
+    if degrees:
+        elev, azim = elev * (math.pi / 180.0), azim * (math.pi / 180.0)
+    C = torch.stack([dist * torch.cos(elev) * torch.sin(azim), dist * torch.sin(elev), dist * torch.cos(elev) * torch.cos(azim)], dim=1)
+    normalize = lambda v: v / v.norm(dim=1, keepdim=True).clamp_min(1e-5)  # noqa: E731  (F.normalize's eps of pytorch3d's call)
+    up = torch.tensor([[0.0, 1.0, 0.0]]).expand_as(C)
+    z = normalize(-C)
+    x = normalize(torch.cross(up, z, dim=1))
+    y = normalize(torch.cross(z, x, dim=1))
+    degenerate = torch.isclose(x, torch.zeros(()), atol=5e-3).all(dim=1, keepdim=True)
+    x = torch.where(degenerate, normalize(torch.cross(y, z, dim=1)), x)
+    R = torch.stack([x, y, z], dim=2)
+    T = -torch.bmm(R.transpose(1, 2), C[:, :, None])[:, :, 0]
+    return R.to(device), T.to(device)
+
+
 def join_cameras(cameras):
     """The datasets collate to a python LIST of single cameras (dataset/shapenet_r2n2.py:601-612)."""
     if isinstance(cameras, (list, tuple)):
-        return PerspectiveCameras(torch.cat([c.focal_length for c in cameras]), torch.cat([c.principal_point for c in cameras]),
+        return type(cameras[0])(torch.cat([c.focal_length for c in cameras]), torch.cat([c.principal_point for c in cameras]),
                                   torch.cat([c.R for c in cameras]), torch.cat([c.T for c in cameras]), device=cameras[0].device)
     return cameras
 

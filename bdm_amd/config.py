@@ -29,6 +29,10 @@ class RunConfig:  # structured.py:14-56
     max_fusion_steps: int = 20000
     coloring_training_noise_std: float = 0.0  # structured.py:45-46
     coloring_sample_dir: Optional[str] = None
+    # not in the reference (it renders inside its sample job, main.py:418-430): main_render.py's input tree, and the number of
+    # orbit frames it adds per predicted cloud (1 = none; must divide 360)
+    render_sample_dir: Optional[str] = None
+    render_num_frames: int = 1
     save_dir: Optional[str] = None
     # not in the reference: "reference" = its draws (CPU generator for the initial cloud and the blend masks, the device's
     # global generator for DDPM / PVD noise, seeded seed + rank); "per_shape" = Philox streams keyed by (seed, global

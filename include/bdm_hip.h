@@ -688,6 +688,22 @@ int bdm_blend_select(long long num_points, const float *recon, const float *prio
 size_t bdm_rasterize_workspace_bytes(int b, int h, int w);
 int bdm_rasterize_points(int b, int n, int h, int w, float radius, const float *points,
                          const float *cameras, int *pix_of_point, void *workspace, void *stream);
+/* Point-cloud rendering (render.hip; experiments/diffusion_utils.py:185-295 renders with pytorch3d's PointsRasterizer and its
+ * NormWeighted / Alpha compositors, restated here: pytorch3d is absent, parity unpinned).  Projection and pixel centres as
+ * bdm_rasterize_points (ortho = 1 drops the division by the view depth: ndc = focal * X_view.xy + pp); for h != w each axis spans
+ * [-1, 1] (this project's convention, not pytorch3d's aspect-scaled one).  A point is a candidate of a pixel when
+ * dx*dx + dy*dy < radius*radius and z >= 0; the pixel keeps the k candidates with the smallest (z, point index), ascending.
+ *   frag_idx / frag_z / frag_d2 (b,h,w,k): point index WITHIN its cloud (0 .. n-1; pytorch3d stores the index into the packed
+ *     batch), view depth, squared NDC distance; -1 in unused slots.  Any of the three may be NULL (not stored).
+ *   image (b,h,w,c), may be NULL: with w_j = 1 - d2_j / radius^2 over the used slots in slot order,
+ *     compositor 0 (norm_weighted) sum_j w_j f_j / max(sum_j w_j, 1e-4);  compositor 1 (alpha) sum_j f_j w_j prod_{i<j} (1 - w_i);
+ *     a pixel whose slot 0 is empty takes background (c) unchanged.  features (b,n,c) or NULL = zeros.
+ * Limits: 1 <= k <= 16, 1 <= c <= 4, radius * max(h,w) / 2 <= 8 (pixel pitches).  Deterministic: no atomics, the result does not
+ * depend on execution order.  workspace: bdm_render_workspace_bytes(b, n, h, w, radius) bytes. */
+size_t bdm_render_workspace_bytes(int b, int n, int h, int w, float radius);
+int bdm_render_points(int b, int n, int h, int w, int k, int c, float radius, int ortho, int compositor,
+                      const float *points, const float *cameras, const float *features, const float *background,
+                      int *frag_idx, float *frag_z, float *frag_d2, float *image, void *workspace, void *stream);
 /* get_input_with_conditioning's output (projection_model.py:179-231):
  * out (b, n, 3+c) = cat[x_t, feature_image[pix_of_point]] with zeros for points owning no pixel;
  * feature_image is stored pixel-major (b, h*w, c). */

@@ -1,0 +1,112 @@
+"""Rendering entry point: turns the clouds a sample_* job (and main_coloring.py) wrote into pictures, each from the camera of its
+dataset entry -- what the reference does inside its sample job (experiments/main.py:418-430, diffusion_utils.py:185-295).  Same
+`group.key=value` overrides as the other entry points.
+
+Reads  ${run.render_sample_dir}/{gt,pred,colored}/<category>/<name>.ply  (also <name>-<k>.ply when run.num_samples > 1; `colored`
+only where main_coloring.py has written it), looks every <name> up in the dataset, and writes
+${run.render_sample_dir}/renders/{gt,pred,colored}/<category>/<stem>.png.  With run.render_num_frames = F > 1 it also writes the
+orbiting orthographic view of every predicted cloud (the coloured one where it exists) as renders/orbit/<category>/<stem>-<f>.png.
+
+    python main_blending.py run.job=sample_bdm_blending dataset=synthetic run.num_samples=1 dataset.max_points=1024
+    python main_render.py dataset=synthetic run.render_sample_dir=<the directory the first command printed>
+"""
+import sys
+from pathlib import Path
+
+import torch
+
+from main_blending import get_dataloader
+
+KINDS = ("gt", "pred", "colored")
+
+
+def parse_args(argv):
+    from bdm_amd.config import parse_overrides
+    cfg = parse_overrides(argv)
+    if not cfg.run.render_sample_dir:
+        raise ValueError("run.render_sample_dir=<directory holding pred/<category>/<name>.ply> is required")
+    if cfg.run.render_num_frames < 1 or 360 % cfg.run.render_num_frames:
+        raise ValueError("run.render_num_frames must divide 360")
+    return cfg
+
+
+def clouds_of(sample_dir, kind, category, name):
+    """The clouds of one dataset entry under <sample_dir>/<kind>: <name>.ply and <name>-<k>.ply, sorted."""
+    d = Path(sample_dir) / kind / category
+    hits = [d / f"{name}.ply"] if (d / f"{name}.ply").exists() else []
+    hits += sorted(p for p in d.glob(f"{name}-*.ply") if p.stem[len(name) + 1:].isdigit())
+    return hits
+
+
+def render_tree(cfg, batches, render_fn, orbit_fn=None, device="cpu"):
+    """Walk the dataset, render every cloud found under the sample directory, write renders/<kind>/<category>/<stem>.png; returns
+    the paths written.  render_fn(cameras (list of single cameras), points (B, n, 3), colours (B, n, 3) or None) -> images
+    (B, H, W, 3) in [0, 1]: one call per batch, kind and distinct point count.  orbit_fn(points (1, n, 3), colours or None,
+    path of <stem>.png, num_frames) -> the paths it wrote: called per predicted cloud when run.render_num_frames > 1."""
+    from bdm_amd.io import load_pointcloud_ply, save_image_png
+    root, written = Path(cfg.run.render_sample_dir), []
+    for batch_idx, batch in enumerate(batches):
+        if cfg.run.num_sample_batches is not None and batch_idx >= cfg.run.num_sample_batches:
+            break
+        batch = batch.to(device)
+        cam = batch.camera   # a list of single cameras (the datasets' collation), or one batched camera
+        cameras = list(cam) if isinstance(cam, (list, tuple)) else [
+            type(cam)(cam.focal_length[i:i + 1], cam.principal_point[i:i + 1], cam.R[i:i + 1], cam.T[i:i + 1], device=cam.device)
+            for i in range(len(cam))]
+        groups = {}   # (kind, point count) -> [(row of the batch, path, points, colours or None)]
+        for i, (name, cat) in enumerate(zip(batch.sequence_name, batch.sequence_category)):
+            for kind in KINDS:
+                for path in clouds_of(root, kind, cat, name):
+                    if kind == "colored":
+                        pts, col = load_pointcloud_ply(path, with_colors=True)
+                        col = torch.from_numpy(col)
+                    else:
+                        pts, col = load_pointcloud_ply(path), None
+                    groups.setdefault((kind, pts.shape[0]), []).append((i, path, torch.from_numpy(pts), col))
+        for (kind, _), items in sorted(groups.items()):
+            points = torch.stack([it[2] for it in items]).to(device)
+            colors = torch.stack([it[3] for it in items]).to(device) if kind == "colored" else None
+            images = render_fn([cameras[it[0]] for it in items], points, colors)
+            for (i, path, _, _), image in zip(items, images):
+                out = root / "renders" / kind / batch.sequence_category[i] / f"{path.stem}.png"
+                save_image_png(image.detach().cpu().permute(2, 0, 1).numpy(), out)
+                written.append(out)
+        if cfg.run.render_num_frames > 1 and orbit_fn is not None:
+            for (kind, _), items in sorted(groups.items()):
+                for i, path, pts, col in items:
+                    cat = batch.sequence_category[i]
+                    if kind == "gt" or (kind == "pred" and (root / "colored" / cat / path.name).exists()):
+                        continue   # the orbit shows each prediction once, coloured where a coloured copy exists
+                    out = root / "renders" / "orbit" / cat / f"{path.stem}.png"
+                    written += [Path(p) for p in orbit_fn(pts[None].to(device), None if col is None else col[None].to(device), out,
+                                                          cfg.run.render_num_frames)]
+    return written
+
+
+def main(argv=None):
+    from bdm_amd.cameras import Pointclouds
+    from bdm_amd.distributed import barrier, gpu_turn, init_from_env
+    from bdm_amd.render import render_pointcloud_batch_pytorch3d, visualize_pointcloud_batch_pytorch3d
+    cfg = parse_args(sys.argv[1:] if argv is None else argv)
+    rank, local_rank, world = init_from_env()
+    device = torch.device("cuda", local_rank)
+    torch.cuda.set_device(device)
+
+    def render_fn(cameras, points, colors):
+        with gpu_turn(device):
+            return render_pointcloud_batch_pytorch3d(cameras, Pointclouds(points, colors)).cpu()
+
+    def orbit_fn(points, colors, path, num_frames):
+        with gpu_turn(device):
+            visualize_pointcloud_batch_pytorch3d(Pointclouds(points, colors), output_file_image=str(path), num_frames=num_frames,
+                                                 scale_factor=cfg.model.scale_factor)
+        return [path.with_name(f"{path.stem}-{f}.png") for f in range(num_frames)]
+
+    written = render_tree(cfg, get_dataloader(cfg, rank, world), render_fn, orbit_fn, device)
+    barrier()
+    print(f"rank {rank}: rendered {len(written)} images under {(Path(cfg.run.render_sample_dir) / 'renders').absolute()}")
+    return written
+
+
+if __name__ == "__main__":
+    main()
