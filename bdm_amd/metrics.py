@@ -6,13 +6,19 @@ mover's distance (EMD) the point-cloud generation literature reports.
 The distance matrices are HIP (csrc/metrics.hip: bdm_pairwise_chamfer, bdm_pairwise_emd_approx; device tensors only, no CPU path);
 the reductions over the small matrices are host-side torch and work on CPU tensors too.
 
-    python -m bdm_amd.metrics --sample gen.npy --ref ref.npy [--metrics cd,emd] [--normalize] [--batch-size N]
+The Jensen-Shannon divergence (JSD) between the occupancy-grid distributions of the two sets, and the mean occupancy entropy of a
+set, come from per-cell histograms (csrc/occupancy.hip: bdm_occupancy_grid; device tensors only); the function names are those of
+the reference's experiments/pvd/utils/metrics.py, and the float64 arithmetic on the histograms works on CPU tensors and arrays.
+
+    python -m bdm_amd.metrics --sample gen.npy --ref ref.npy [--metrics cd,emd] [--normalize] [--batch-size N] [--jsd] [--jsd-resolution R]
 """
 import argparse
+import functools
 import glob
 import json
 import os
 import sys
+import warnings
 
 import numpy as np
 import torch
@@ -127,6 +133,119 @@ def compute_all_metrics(sample, ref, metrics=("cd", "emd"), batch_size=None):
     return out
 
 
+# ---- occupancy grid: JSD and occupancy entropy -------------------------------------------------------------------------------
+def unit_cube_grid_point_cloud(resolution, clip_sphere=False):
+    """Centres of the resolution^3 cells of a grid over the unit cube [-0.5, 0.5]^3, float32 (resolution, resolution, resolution, 3),
+    and the spacing 1 / (resolution - 1).  `clip_sphere` drops the cells whose centre lies outside radius 0.5 and returns (kept, 3)
+    in row-major cell order.  Coordinate i is float32(i * spacing - 0.5) with the arithmetic in double."""
+    spacing = 1.0 / float(resolution - 1)
+    axis = (np.arange(resolution) * spacing - 0.5).astype(np.float32)
+    grid = np.stack(np.meshgrid(axis, axis, axis, indexing="ij"), axis=-1)
+    if clip_sphere:
+        cells = grid.reshape(-1, 3)
+        return cells[_centre_in_sphere(cells)], spacing
+    return grid, spacing
+
+
+def _centre_in_sphere(cells):
+    """cells (M, 3) float32 -> bool (M): the float32 norm of the centre is at most 0.5."""
+    return np.linalg.norm(cells, axis=1) <= 0.5
+
+
+@functools.lru_cache(maxsize=8)
+def _device_grid(resolution, in_sphere, device):
+    """axis (r) float32, cell mask (r^3) uint8 and the flat indices of the kept cells, on `device`."""
+    grid, _ = unit_cube_grid_point_cloud(resolution)
+    flat = grid.reshape(-1, 3)
+    mask = _centre_in_sphere(flat) if in_sphere else np.ones(len(flat), dtype=bool)
+    axis = np.ascontiguousarray(grid[:, 0, 0, 0])
+    return (torch.from_numpy(axis).to(device), torch.from_numpy(mask.astype(np.uint8)).to(device),
+            torch.from_numpy(np.flatnonzero(mask)).to(device))
+
+
+def occupancy_grid(clouds, resolution=28, in_sphere=True):
+    """clouds (S, N, 3) on the GPU -> (hits, active), int64 over the kept cells of the resolution^3 grid in row-major order (with
+    `in_sphere` the cells whose centre lies within radius 0.5, else all): hits[c] = points of all clouds whose nearest kept cell is
+    c, active[c] = clouds with at least one such point.  Integer sums: the sum over any split of the clouds equals the whole."""
+    if not torch.is_tensor(clouds) or not clouds.is_cuda:
+        raise L.BdmHipError("occupancy_grid runs on a HIP device only; got a host array (no CPU fallback)")
+    clouds = _clouds(clouds, "clouds")
+    if resolution < 2:
+        raise ValueError(f"occupancy_grid: resolution must be at least 2, got {resolution}")
+    S, N = clouds.shape[0], clouds.shape[1]
+    bound = 0.5 + 10e-4
+    if S > 0:
+        if abs(float(clouds.max())) > bound or abs(float(clouds.min())) > bound:
+            warnings.warn("Point-clouds are not in unit cube.")
+        if in_sphere and float((clouds ** 2).sum(dim=2).sqrt().max()) > bound:
+            warnings.warn("Point-clouds are not in unit sphere.")
+    axis, mask, kept = _device_grid(int(resolution), bool(in_sphere), clouds.device)
+    out = torch.empty(2, int(resolution) ** 3, dtype=torch.int32, device=clouds.device)
+    L.check(L.lib().bdm_occupancy_grid(S, N, int(resolution), L.ptr(clouds), L.ptr(axis), L.ptr(mask), L.ptr(out[0]), L.ptr(out[1]),
+                                       L.stream()), "occupancy_grid")
+    return out[0][kept].long(), out[1][kept].long()
+
+
+def _host_f64(v):
+    return v.detach().cpu().numpy().astype(np.float64) if torch.is_tensor(v) else np.asarray(v, dtype=np.float64)
+
+
+def _xlogx(p, log=np.log):
+    """p log p elementwise with 0 log 0 = 0."""
+    out = np.zeros_like(p)
+    pos = p > 0
+    out[pos] = p[pos] * log(p[pos])
+    return out
+
+
+def _occupancy_entropy(active, num_clouds):
+    """Mean over the cells of the entropy in nats of the Bernoulli variable "a cloud hits this cell", whose probability is
+    active / num_clouds; cells that no cloud or every cloud hits add 0."""
+    p = _host_f64(active) / float(num_clouds)
+    return float(-(_xlogx(p) + _xlogx(1.0 - p)).sum() / p.size)
+
+
+def entropy_of_occupancy_grid(pclouds, grid_resolution, in_sphere=False):
+    """pclouds (S, N, 3), a GPU tensor or a host array (copied to the GPU) -> (mean occupancy entropy in nats, hits per kept cell as
+    a float64 array)."""
+    if not torch.is_tensor(pclouds):
+        pclouds = _to_device(np.ascontiguousarray(pclouds, dtype=np.float32))
+    hits, active = occupancy_grid(pclouds, grid_resolution, in_sphere)
+    return _occupancy_entropy(active, pclouds.shape[0]), _host_f64(hits)
+
+
+def _jsd_kl_form(p, q, mix):
+    """JSD in bits of two distributions as the mean of their Kullback-Leibler divergences from their mixture `mix`."""
+    def kl_from_mix(a):
+        pos = a > 0   # mix >= a / 2 > 0 there
+        return float((a[pos] * np.log2(a[pos] / mix[pos])).sum())
+    return 0.5 * (kl_from_mix(p) + kl_from_mix(q))
+
+
+def jensen_shannon_divergence(P, Q):
+    """JSD in base 2 (0 .. 1) between the distributions P / sum(P) and Q / sum(Q); float64 on the host, any array or tensor.
+    Returned in the entropy form H(mix) - (H(p) + H(q)) / 2; the Kullback-Leibler form is evaluated beside it and a warning is
+    raised when the two are more than 10e-5 apart."""
+    counts = [_host_f64(P), _host_f64(Q)]
+    if any((c < 0).any() for c in counts):
+        raise ValueError("Negative values.")
+    if len(counts[0]) != len(counts[1]):
+        raise ValueError("Non equal size.")
+    p, q = (c / c.sum() for c in counts)
+    mix = 0.5 * (p + q)
+    bits = lambda d: float(-_xlogx(d, np.log2).sum())
+    jsd = bits(mix) - 0.5 * (bits(p) + bits(q))
+    if abs(jsd - _jsd_kl_form(p, q, mix)) > 10e-5:
+        warnings.warn("Numerical values of two JSD methods don't agree.")
+    return jsd
+
+
+def jsd_between_point_cloud_sets(sample_pcs, ref_pcs, resolution=28):
+    """JSD between the occupancy-grid distributions (sphere-clipped resolution^3 grid) of two sets of clouds (S, N, 3), (R, M, 3)."""
+    hits = [entropy_of_occupancy_grid(clouds, resolution, in_sphere=True)[1] for clouds in (sample_pcs, ref_pcs)]
+    return jensen_shannon_divergence(*hits)
+
+
 def normalize_unit_sphere(clouds):
     """Centre every cloud on its mean and scale it so that its farthest point lies on the unit sphere."""
     clouds = clouds - clouds.mean(axis=1, keepdims=True)
@@ -159,12 +278,15 @@ def _to_device(array):
 
 
 def parse_args(argv=None):
-    ap = argparse.ArgumentParser(prog="python -m bdm_amd.metrics", description="MMD / COV / 1-NNA of generated against reference clouds")
+    ap = argparse.ArgumentParser(prog="python -m bdm_amd.metrics", description="MMD / COV / 1-NNA (and JSD) of generated against reference clouds")
     ap.add_argument("--sample", required=True, help=".npy (count, N, 3) or a directory of .ply: generated clouds")
     ap.add_argument("--ref", required=True, help=".npy (count, N, 3) or a directory of .ply: reference clouds")
     ap.add_argument("--metrics", default="cd,emd", type=lambda s: tuple(m for m in s.split(",") if m), help="cd, emd or cd,emd")
     ap.add_argument("--normalize", action="store_true", help="centre and scale every cloud to the unit sphere first")
     ap.add_argument("--batch-size", type=int, default=None, help="references per launch")
+    ap.add_argument("--jsd", action="store_true", help="also report the occupancy-grid JSD and the two sets' occupancy entropies; the grid spans radius 0.5, so pass clouds that lie "
+                    "inside it (--normalize scales to radius 1: most points would then snap to the cells at the sphere's surface)")
+    ap.add_argument("--jsd-resolution", type=int, default=28, help="cells per axis of the occupancy grid")
     args = ap.parse_args(argv)
     bad = [m for m in args.metrics if m not in ("cd", "emd")]
     if bad or not args.metrics:
@@ -177,7 +299,12 @@ def main(argv=None):
     sample, ref = load_clouds(args.sample), load_clouds(args.ref)
     if args.normalize:
         sample, ref = normalize_unit_sphere(sample), normalize_unit_sphere(ref)
-    result = compute_all_metrics(_to_device(sample), _to_device(ref), metrics=args.metrics, batch_size=args.batch_size)
+    sample_dev, ref_dev = _to_device(sample), _to_device(ref)
+    result = compute_all_metrics(sample_dev, ref_dev, metrics=args.metrics, batch_size=args.batch_size)
+    if args.jsd:
+        (ent_s, hits_s), (ent_r, hits_r) = (entropy_of_occupancy_grid(c, args.jsd_resolution, True) for c in (sample_dev, ref_dev))
+        result.update({"jsd": float(jensen_shannon_divergence(hits_s, hits_r)), "occupancy_entropy_sample": float(ent_s),
+                       "occupancy_entropy_ref": float(ent_r)})
     result.update(num_sample=int(sample.shape[0]), num_ref=int(ref.shape[0]), num_points=int(sample.shape[1]))
     print(json.dumps(result))
     return result

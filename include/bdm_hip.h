@@ -837,6 +837,23 @@ int bdm_color_block_tail(int b, int e, int n, const float *h, const float *p, co
                          float *ln_next, const float *out_w, const float *out_b, float colors_mean,
                          float colors_std, float *colors, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * 9. Occupancy-grid histograms of a set of clouds (csrc/occupancy.hip; bdm_amd/metrics.py reduces them to the JSD between two
+ *    sets and to the mean occupancy entropy; experiments/pvd/utils/metrics.py:13-31, 142-232).  DESIGN.md section 13.
+ * ---------------------------------------------------------------------------------- */
+/* clouds (s, n, 3) point-major; axis: the r ascending, evenly spaced coordinates every grid axis shares; cell_mask (r^3 bytes,
+ * cell (i, j, k) at (i r + j) r + k with centre (axis[i], axis[j], axis[k])): non-zero = the cell is kept.
+ * A point belongs to the kept cell that minimises (x - gx)^2 + (y - gy)^2 + (z - gz)^2 in fp32 (unfused, in that order); a point
+ * with a NaN or infinite coordinate belongs to none.  Equal fp32 distances: when the cell the point rounds to is kept, each axis
+ * index is the lowest among that axis's equal squared differences (two cells whose sums round to the same value although one axis
+ * differs are not told apart by flat index); otherwise the lowest flat index among the kept cells.
+ * hits[c] = points of all clouds that belong to cell c; active[c] = clouds with at least one such point; both r^3 ints, zeroed
+ * by the call (cells with cell_mask 0 stay 0), either may be NULL.  Integer sums: the same bits for any order, and the sum over any
+ * split of the clouds into several calls equals the one call.  s = 0 only zeroes.  Returns 1 without launching for s < 0, n < 1,
+ * r < 2, r > 32 (the r^3 histogram and a 32-bit mask word per column live in one workgroup's LDS) or s n >= 2^31. */
+int bdm_occupancy_grid(int s, int n, int r, const float *clouds, const float *axis, const unsigned char *cell_mask,
+                       int *hits, int *active, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
