@@ -888,7 +888,7 @@ extern "C" int bdm_group_norm_stats(int b, int c, int l, int groups, const float
   *slices_out = S;
   if (b == 0) return BDM_OK;
   hipStream_t s = (hipStream_t)stream;
-  const bool packed = (l % 4 == 0) && ((((uintptr_t)x) & 15) == 0) && (bs_x % 4 == 0) && total < (1ll << 30);
+  const bool packed = bdm_group_norm_route(c, l, groups, x, bs_x, l, nullptr, 0, 0, x, bs_x, l) != 2;  // rows of x are dense
   if (packed)
     hipLaunchKernelGGL(gn_stats_vec_kernel, dim3(S, b * groups), dim3(256), 0, s, cg, l, x, bs_x, (const float *)nullptr,
                        0ll, groups, (double *)workspace);
@@ -900,6 +900,19 @@ extern "C" int bdm_group_norm_stats(int b, int c, int l, int groups, const float
 
 extern "C" size_t bdm_group_norm_workspace_bytes(int b, int groups) {
   return sizeof(double) * 2 * (size_t)b * groups * GN_MAX_SLICES;
+}
+
+// Host only: which of the kernels above bdm_group_norm launches -- 0 gn_onepass_kernel, 1 gn_stats_vec + gn_apply_vec,
+// 2 gn_stats + gn_apply (the scalar pair: any row stride, length and alignment).  The one definition of the choice.
+extern "C" int bdm_group_norm_route(int c, int l, int groups, const float *x, long long bs_x, int ld_x, const float *residual,
+                                    long long bs_r, int ld_r, const float *y, long long bs_y, int ld_y) {
+  const long long total = (long long)(c / groups) * l;
+  auto al16 = [](const void *p) { return (((uintptr_t)p) & 15) == 0; };
+  const bool packed = ld_x == l && ld_y == l && (!residual || ld_r == l) && (l % 4 == 0) && al16(x) && al16(y) &&
+                      (!residual || al16(residual)) && (bs_x % 4 == 0) && (bs_y % 4 == 0) && (!residual || bs_r % 4 == 0) &&
+                      total < (1ll << 30);
+  if (!packed) return 2;
+  return total <= 4ll * 1024 * GN1_MAXV ? 0 : 1;
 }
 
 extern "C" int bdm_group_norm(int b, int c, int l, int groups, const float *x, long long bs_x, int ld_x,
@@ -914,11 +927,9 @@ extern "C" int bdm_group_norm(int b, int c, int l, int groups, const float *x, l
   const int cg = c / groups;
   const long long total = (long long)cg * l;
   double *partial = (double *)workspace;
-  auto al16 = [](const void *p) { return (((uintptr_t)p) & 15) == 0; };
-  const bool packed = ld_x == l && ld_y == l && (!residual || ld_r == l) && (l % 4 == 0) && al16(x) && al16(y) &&
-                      (!residual || al16(residual)) && (bs_x % 4 == 0) && (bs_y % 4 == 0) && (!residual || bs_r % 4 == 0) &&
-                      total < (1ll << 30);
-  if (packed && total <= 4ll * 1024 * GN1_MAXV) {
+  const int route = bdm_group_norm_route(c, l, groups, x, bs_x, ld_x, residual, bs_r, ld_r, y, bs_y, ld_y);
+  const bool packed = route != 2;
+  if (route == 0) {
     hipLaunchKernelGGL(gn_onepass_kernel, dim3(b * groups), dim3(1024), 0, s, cg, l, x, bs_x, residual, bs_r, groups, gamma,
                        beta, eps, act, y, bs_y);
     return launch_status("gn_onepass");
@@ -957,7 +968,7 @@ __global__ void max_u_kernel(int c, int m, int u, const float *__restrict__ x, f
   for (int ci = blockIdx.y; ci < c; ci += gridDim.y) {
     const float *row = x + (((size_t)bi * c + ci) * m + j) * u;
     float v = row[0];
-    if ((u & 3) == 0) {
+    if ((u & 3) == 0 && (reinterpret_cast<size_t>(x) & 15) == 0) {  // (rows are u floats apart: the base decides for every row)
       const float4 *r4 = reinterpret_cast<const float4 *>(row);
       for (int q = 0; q < u / 4; ++q) {
         const float4 t = r4[q];
@@ -1019,6 +1030,12 @@ __global__ void max_u_gn_kernel(int c, int m, int u, int lpr, int G, int S, cons
   }
 }
 
+// Host only: lanes per row (lpr) of max_u_gn_kernel for rows of u floats at x -- u / 4 (a power of two up to 64) when a row splits
+// into 16-byte pieces, otherwise 1 (one lane walks the row).  The one definition of the choice.
+extern "C" int bdm_max_over_neighbors_gn_lanes(int u, const float *x) {
+  return ((u & 3) == 0 && u <= 256 && ((u / 4) & (u / 4 - 1)) == 0 && ((reinterpret_cast<size_t>(x) & 15) == 0)) ? u / 4 : 1;
+}
+
 extern "C" int bdm_max_over_neighbors_gn(int b, int c, int m, int u, const float *x, const void *in_partial, int in_slices,
                                          int groups, const float *gamma, const float *beta, float eps, float *y, long long bs_y,
                                          int ld_y, void *stream) {
@@ -1026,7 +1043,7 @@ extern "C" int bdm_max_over_neighbors_gn(int b, int c, int m, int u, const float
   BDM_REQUIRE(in_partial != nullptr && in_slices >= 1 && groups >= 1 && c % groups == 0 && gamma && beta,
               "max_over_neighbors_gn: bad GroupNorm arguments");
   if (b == 0) return BDM_OK;
-  const int lpr = ((u & 3) == 0 && u <= 256 && ((u / 4) & (u / 4 - 1)) == 0 && ((reinterpret_cast<size_t>(x) & 15) == 0)) ? u / 4 : 1;
+  const int lpr = bdm_max_over_neighbors_gn_lanes(u, x);
   BDM_REQUIRE(lpr == 1 || (u & 3) == 0, "max_over_neighbors_gn: internal");
   dim3 grid(cdiv(m, 64), c < 256 ? c : 256, b);
   hipLaunchKernelGGL(max_u_gn_kernel, grid, dim3(64), 0, (hipStream_t)stream, c, m, u, lpr, groups, in_slices, x,
@@ -1773,6 +1790,19 @@ __global__ __launch_bounds__(1024) void devox_gn_lds_kernel(int c, int n, int r,
   }
 }
 
+// Host only: the kernel the folded devoxelisations launch -- 0 devox_gn_fused_kernel (global-memory gather), 1 devox_gn_lds_kernel.
+// with_se_mean: the SE layers are evaluated in the kernel (bdm_devoxelize_gn_se_add; global form only).  The one definition of
+// the choice; reads BDM_STAGING at every call.
+extern "C" int bdm_devoxelize_gn_route(int b, int c, int r, const float *grid, int with_se_mean) {
+  const int lsel = bdm_staging_choice();  // BDM_STAGING=0 keeps the global-memory gather, =1 forces the LDS form (common.h)
+  const int r3 = r * r * r;
+  // measured per shape at B = 16 (tools/forward_rows.py): the LDS form wins at 16^3 (29.5 -> 21.9 us) and at 32^3 with >= 64
+  // channels (70.5 -> 64.8 us); at 8^3 and for the 32-channel 32^3 layers it has too few workgroups and loses.
+  const bool lds_fits = !with_se_mean && (r3 & 3) == 0 && r3 <= 32768 && ((reinterpret_cast<size_t>(grid) & 15) == 0);
+  const bool lds_pays = r == 16 || (r == 32 && (long long)b * c >= 1024);
+  return (lds_fits && lsel != 0 && (lds_pays || lsel == 1)) ? 1 : 0;
+}
+
 static int devox_gn_launch(int b, int c, int n, int r, const float *coords, const float *grid, const float *coef,
                            const float *gate, const float *se_mean, int hidden, const float *w1, const float *w2,
                            const float *add, long long bs_a, int ld_a, const float *add_coef, float *out, long long bs_o, int ld_o,
@@ -1780,13 +1810,8 @@ static int devox_gn_launch(int b, int c, int n, int r, const float *coords, cons
   BDM_REQUIRE(b >= 0 && c >= 1 && n >= 1 && r >= 1 && coef != nullptr, "devoxelize_gn_gate_add: bad arguments");
   BDM_REQUIRE(se_mean == nullptr || (hidden >= 1 && hidden <= 64 && c <= 1024 && w1 != nullptr && w2 != nullptr), "devoxelize_gn_se_add: bad SE arguments");
   if (b == 0) return BDM_OK;
-  const int lsel = bdm_staging_choice();  // BDM_STAGING=0 keeps the global-memory gather, =1 forces the LDS form (common.h)
   const int r3 = r * r * r;
-  // measured per shape at B = 16 (tools/forward_rows.py): the LDS form wins at 16^3 (29.5 -> 21.9 us) and at 32^3 with >= 64
-  // channels (70.5 -> 64.8 us); at 8^3 and for the 32-channel 32^3 layers it has too few workgroups and loses.
-  const bool lds_fits = se_mean == nullptr && (r3 & 3) == 0 && r3 <= 32768 && ((reinterpret_cast<size_t>(grid) & 15) == 0);
-  const bool lds_pays = r == 16 || (r == 32 && (long long)b * c >= 1024);
-  if (lds_fits && lsel != 0 && (lds_pays || lsel == 1)) {
+  if (bdm_devoxelize_gn_route(b, c, r, grid, se_mean != nullptr) == 1) {
     int cpw = 8192 / r3;  // channels per workgroup: 32 KB of LDS for the small grids, one channel (128 KB) at 32^3
     cpw = cpw < 1 ? 1 : (cpw > c ? c : cpw);
     const size_t smem = sizeof(float) * (size_t)cpw * r3;

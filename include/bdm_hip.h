@@ -151,6 +151,12 @@ int bdm_group_norm(int b, int c, int l, int groups, const float *x, long long bs
                    const float *residual, long long bs_r, int ld_r, const float *gamma,
                    const float *beta, float eps, int act, float *y, long long bs_y, int ld_y,
                    void *workspace, void *stream);
+/* Host only: the kernels bdm_group_norm launches for these sizes, strides and pointers -- what the launch path itself decides, not a
+ * restatement.  0: one pass (a (shape, group) chunk of at most 65536 floats kept in registers), 1: the float4 two-pass pair, 2: the
+ * scalar two-pass pair (rows not dense, l % 4 != 0, or a base / batch stride off 16 bytes).  Only the ADDRESSES of x, residual
+ * (may be NULL) and y are looked at; no GPU call.  bdm_group_norm_stats takes 1 or 2 by the same rule with residual = NULL, y = x. */
+int bdm_group_norm_route(int c, int l, int groups, const float *x, long long bs_x, int ld_x, const float *residual,
+                         long long bs_r, int ld_r, const float *y, long long bs_y, int ld_y);
 
 /* features.max(dim=-1) over the neighbour axis (pointnet.py:86): x (b,c,m,u) -> y (b,c,m) strided. */
 /* SharedMLP = [Conv k=1 -> GroupNorm(8) -> Swish]* (modules/shared_mlp.py:25-30) without a pass per GroupNorm.
@@ -211,6 +217,9 @@ int bdm_pointwise_conv_gn_s3(int b, int m, int k, int n, const void *packed_w, c
 int bdm_max_over_neighbors_gn(int b, int c, int m, int u, const float *x, const void *in_partial, int in_slices, int groups,
                               const float *gamma, const float *beta, float eps, float *y, long long bs_y, int ld_y,
                               void *stream);
+/* Host only: lanes that share a row of u floats in bdm_max_over_neighbors_gn (the launch path's own choice): u / 4 when u % 4 == 0,
+ * u <= 256, u / 4 is a power of two and x is 16-byte aligned, else 1.  Only the ADDRESS of x is looked at; no GPU call. */
+int bdm_max_over_neighbors_gn_lanes(int u, const float *x);
 int bdm_max_over_neighbors(int b, int c, int m, int u, const float *x, float *y, long long bs_y,
                            int ld_y, void *stream);
 
@@ -407,6 +416,10 @@ int bdm_devoxelize_gn_gate_add_pf(int b, int c, int n, int r, const float *coord
 int bdm_devoxelize_gn_se_add(int b, int c, int n, int r, const float *coords, const float *grid, const float *coef,
                              const float *se_mean, int hidden, const float *w1, const float *w2, const float *add,
                              long long bs_a, int ld_a, float *out, long long bs_o, int ld_o, void *stream);
+/* Host only: the kernel the three bdm_devoxelize_gn_* entry points launch (the launch path's own choice): 0 the global-memory gather,
+ * 1 the LDS-cached form.  with_se_mean != 0: bdm_devoxelize_gn_se_add (always 0).  Honours BDM_STAGING (0: never LDS, 1: LDS wherever
+ * it fits), read at every call.  Only the ADDRESS of grid is looked at; no GPU call. */
+int bdm_devoxelize_gn_route(int b, int c, int r, const float *grid, int with_se_mean);
 
 /* ---- PVConv tail on the SMALL voxel grids (8^3 levels; csrc/pvconv_small.hip) -- per-shape workgroups, no hand-off between them ----
  * bdm_pvconv_tail_small: SE gate (both FC layers of se.py:8-19, from se_mean (b, c) = bdm_se_gate_gn(w1 = NULL)'s channel means)
