@@ -3,14 +3,15 @@
 coverage (COV) and 1-nearest-neighbour accuracy (1-NNA), each under Chamfer distance (CD) and under the approximate-match earth
 mover's distance (EMD) the point-cloud generation literature reports.
 
-The distance matrices are HIP (csrc/metrics.hip: bdm_pairwise_chamfer, bdm_pairwise_emd_approx; device tensors only, no CPU path);
+The distance matrices are HIP (csrc/metrics.hip: bdm_pairwise_chamfer, bdm_pairwise_emd_approx for clouds of up to 2048 points;
+csrc/metrics_emd_large.hip: bdm_pairwise_emd_large for any size, all pairs or paired; device tensors only, no CPU path);
 the reductions over the small matrices are host-side torch and work on CPU tensors too.
 
 The Jensen-Shannon divergence (JSD) between the occupancy-grid distributions of the two sets, and the mean occupancy entropy of a
 set, come from per-cell histograms (csrc/occupancy.hip: bdm_occupancy_grid; device tensors only); the function names are those of
 the reference's experiments/pvd/utils/metrics.py, and the float64 arithmetic on the histograms works on CPU tensors and arrays.
 
-    python -m bdm_amd.metrics --sample gen.npy --ref ref.npy [--metrics cd,emd] [--normalize] [--batch-size N] [--jsd] [--jsd-resolution R]
+    python -m bdm_amd.metrics --sample gen.npy --ref ref.npy [--metrics cd,emd] [--num-points K] [--normalize] [--batch-size N] [--jsd] [--jsd-resolution R]
 """
 import argparse
 import functools
@@ -76,6 +77,62 @@ def pairwise_emd(a, b, batch_size=None):
     return out
 
 
+EMD_SMALL_MAX_POINTS = 2048   # what bdm_pairwise_emd_approx holds in one workgroup; compute_all_metrics routes above it
+
+
+def _emd_large_call(a, b, paired, mode, out):
+    """One bdm_pairwise_emd_large launch on a (S, N, 3), b (R, N, 3) into out ((S, R), or (S,) when paired), with its workspace."""
+    S, R, n = a.shape[0], b.shape[0], a.shape[1]
+    pairs = S if paired else S * R
+    if pairs == 0:
+        return out
+    if pairs >= 2 ** 31:
+        raise ValueError(f"pairwise_emd_large: {S} x {R} pairs exceed one launch; pass a batch_size")
+    nbytes = int(L.lib().bdm_pairwise_emd_large_workspace_bytes(pairs, n))
+    ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=a.device)   # 0 bytes (n out of range): the call reports it
+    L.check(L.lib().bdm_pairwise_emd_large(S, R, n, int(paired), int(mode), L.ptr(a), L.ptr(b), L.ptr(ws), nbytes, L.ptr(out),
+                                           L.stream()), "pairwise_emd_large")
+    return out
+
+
+def _equal_sized(a, b, what):
+    a, b = _clouds(a, "a"), _clouds(b, "b")
+    if a.shape[1] != b.shape[1]:
+        raise ValueError(f"{what} needs equal-sized clouds, got {a.shape[1]} and {b.shape[1]} points")
+    return a, b
+
+
+def pairwise_emd_large(a, b, batch_size=None, mode=0):
+    """a (S, N, 3), b (R, N, 3) on the GPU, any N >= 1 -> (S, R): approximate-match EMD cost(a_i, b_j) / N (not symmetric in a, b).
+    The same measure as `pairwise_emd` on another kernel (csrc/metrics_emd_large.hip); its bits are its own.  `mode` 0 lets the
+    library choose between its resident (N <= 4096) and streamed forms, 1 / 2 force them: all give the same bits, and so does any
+    `batch_size` (references per launch)."""
+    a, b = _equal_sized(a, b, "pairwise_emd_large")
+    S, R = a.shape[0], b.shape[0]
+    chunks = _chunks(R, batch_size)
+    out = torch.empty(S, R, dtype=torch.float32, device=a.device)
+    for j0, j1 in chunks:
+        o = out if len(chunks) == 1 else torch.empty(S, j1 - j0, dtype=torch.float32, device=a.device)
+        _emd_large_call(a, b[j0:j1], False, mode, o)
+        if len(chunks) > 1:
+            out[:, j0:j1] = o
+    return out
+
+
+def paired_emd(a, b, mode=0):
+    """a, b (P, N, 3) on the GPU, any N >= 1 -> (P,): approximate-match EMD cost(a_i, b_i) / N, the diagonal of
+    `pairwise_emd_large(a, b)` bit for bit without the other P^2 - P pairs."""
+    a, b = _equal_sized(a, b, "paired_emd")
+    if a.shape[0] != b.shape[0]:
+        raise ValueError(f"paired_emd needs as many clouds in a as in b, got {a.shape[0]} and {b.shape[0]}")
+    return _emd_large_call(a, b, True, mode, torch.empty(a.shape[0], dtype=torch.float32, device=a.device))
+
+
+def emd_route(num_points):
+    """The function `compute_all_metrics` takes its EMD matrices from at this cloud size."""
+    return pairwise_emd if num_points <= EMD_SMALL_MAX_POINTS else pairwise_emd_large
+
+
 def mmd_cov(dist):
     """dist (S, R), rows = samples, columns = references ->
     mmd: mean over references of the distance to the nearest sample; mmd_smp: mean over samples of the distance to the nearest
@@ -121,8 +178,8 @@ def metrics_from_matrices(dxy, dxx, dyy, suffix):
 
 def compute_all_metrics(sample, ref, metrics=("cd", "emd"), batch_size=None):
     """sample (S, N, 3), ref (R, N, 3) on the GPU -> flat dict of floats: mmd, mmd_smp, cov, 1nna, 1nna_sample, 1nna_ref, each
-    suffixed -cd / -emd."""
-    fns = {"cd": pairwise_chamfer, "emd": pairwise_emd}
+    suffixed -cd / -emd.  EMD matrices of clouds of up to 2048 points come from `pairwise_emd`, larger ones from `pairwise_emd_large`."""
+    fns = {"cd": pairwise_chamfer, "emd": emd_route(sample.shape[1])}
     out = {}
     for name in metrics:
         if name not in fns:
@@ -271,6 +328,18 @@ def load_clouds(path):
     return np.ascontiguousarray(arr, dtype=np.float32)
 
 
+def subsample_fps(clouds, num_points):
+    """clouds (S, N, 3) on the GPU -> (S, num_points, 3): every cloud's furthest-point sample (bdm_furthest_point_sampling, which
+    starts at point 0), points in the order they were picked.  num_points > N is an error."""
+    from .functional import furthest_point_sample
+    clouds = _clouds(clouds, "clouds")
+    if not 1 <= num_points <= clouds.shape[1]:
+        raise ValueError(f"--num-points {num_points}: the clouds have {clouds.shape[1]} points")
+    if clouds.shape[0] == 0 or num_points == clouds.shape[1]:
+        return clouds
+    return furthest_point_sample(clouds.transpose(1, 2).contiguous(), num_points).transpose(1, 2).contiguous()
+
+
 def _to_device(array):
     if not torch.cuda.is_available():
         raise L.BdmHipError("bdm_amd.metrics needs a HIP device (no CPU fallback)")
@@ -284,6 +353,8 @@ def parse_args(argv=None):
     ap.add_argument("--metrics", default="cd,emd", type=lambda s: tuple(m for m in s.split(",") if m), help="cd, emd or cd,emd")
     ap.add_argument("--normalize", action="store_true", help="centre and scale every cloud to the unit sphere first")
     ap.add_argument("--batch-size", type=int, default=None, help="references per launch")
+    ap.add_argument("--num-points", type=int, default=None, help="score furthest-point samples of this many points per cloud (the literature's protocol is 2048); "
+                    "taken before --normalize and everything else; more than the clouds have is an error")
     ap.add_argument("--jsd", action="store_true", help="also report the occupancy-grid JSD and the two sets' occupancy entropies; the grid spans radius 0.5, so pass clouds that lie "
                     "inside it (--normalize scales to radius 1: most points would then snap to the cells at the sphere's surface)")
     ap.add_argument("--jsd-resolution", type=int, default=28, help="cells per axis of the occupancy grid")
@@ -291,12 +362,18 @@ def parse_args(argv=None):
     bad = [m for m in args.metrics if m not in ("cd", "emd")]
     if bad or not args.metrics:
         ap.error(f"--metrics: choose from cd, emd (got {','.join(bad) or 'nothing'})")
+    if args.num_points is not None and args.num_points < 1:
+        ap.error("--num-points must be positive")
     return args
 
 
 def main(argv=None):
     args = parse_args(argv)
     sample, ref = load_clouds(args.sample), load_clouds(args.ref)
+    if args.num_points is not None:
+        if args.num_points > min(sample.shape[1], ref.shape[1]):
+            raise ValueError(f"--num-points {args.num_points}: the clouds have {sample.shape[1]} and {ref.shape[1]} points")
+        sample, ref = (subsample_fps(_to_device(c), args.num_points).cpu().numpy() for c in (sample, ref))
     if args.normalize:
         sample, ref = normalize_unit_sphere(sample), normalize_unit_sphere(ref)
     sample_dev, ref_dev = _to_device(sample), _to_device(ref)

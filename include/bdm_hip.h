@@ -810,9 +810,9 @@ int bdm_simple_add(long long n, const float *a, const float *b, float *out, void
 
 /* ------------------------------------------------------------------------------------
  * 7. Generation metrics: all-pairs cloud-to-cloud distance matrices (csrc/metrics.hip; bdm_amd/metrics.py reduces them to
- *    MMD, COV and 1-NNA).  Clouds are point-major: a (s, n, 3), b (r, m, 3).  No workspace; no atomics: entry (i, j) is
- *    reduced in a fixed order that depends on the point counts alone, so it carries the bits of the 1 x 1 call on clouds
- *    i and j.  s = 0 or r = 0 is a no-op.
+ *    MMD, COV and 1-NNA).  Clouds are point-major: a (s, n, 3), b (r, m, 3).  No workspace (but for bdm_pairwise_emd_large,
+ *    csrc/metrics_emd_large.hip); no atomics: entry (i, j) is reduced in a fixed order that depends on the point counts alone,
+ *    so it carries the bits of the 1 x 1 call on clouds i and j.  s = 0 or r = 0 is a no-op.
  * ---------------------------------------------------------------------------------- */
 /* out_ab[i, j] = mean over the points p of a_i of min over the points q of b_j of |p - q|^2, out_ba[i, j] the same with the
  * roles swapped; both (s, r), either may be NULL.  Distances in the difference form dx^2 + dy^2 + dz^2. */
@@ -824,8 +824,28 @@ int bdm_pairwise_chamfer(int s, int r, int n, int m, const float *a, const float
 int bdm_pairwise_chamfer_variant(int s, int r, int n, int *p, int *tj);
 /* Approximate-match earth mover's distance (Fan et al., approxmatch + matchcost: ten levels exp(-4^j d^2), j = 7 .. -1, then 0;
  * DESIGN.md section 10) between equal-sized clouds: out[i, j] = cost(a_i, b_j) / n, (s, r).  Not symmetric in (a, b).
- * n above 2048 returns 3 (unsupported). */
+ * n above 2048 returns 3 (unsupported): bdm_pairwise_emd_large below takes any size. */
 int bdm_pairwise_emd_approx(int s, int r, int n, const float *a, const float *b, float *out, void *stream);
+/* The same measure for clouds of any size up to 65536 points (csrc/metrics_emd_large.hip), all pairs or paired; beside
+ * bdm_pairwise_emd_approx, whose bits it need not reproduce (the final sum over the points is ordered differently).  One
+ * workgroup per pair in a persistent grid of at most 256 workgroups, each with a slab of the caller's workspace for the per-point
+ * state (20 bytes per point padded to a multiple of 4): the workspace does not grow with the number of pairs beyond 256.
+ * Two forms of one algorithm with the same bits: RESIDENT (both clouds in LDS; n <= 4096) and STREAMED (the other cloud passes
+ * through LDS in stages of 1024 points; any n).  Entry (i, j) carries the bits of the 1 x 1 call in either form, paired or not.
+ * The upper limit of n is a budget, not a capacity: a pair is never split over workgroups, so its time grows with n^2 on one CU. */
+/* bytes of workspace a call on `pairs` pairs (s * r, or s when paired) of n-point clouds needs; 0 for pairs < 1, n < 1 or n > 65536 */
+size_t bdm_pairwise_emd_large_workspace_bytes(int pairs, int n);
+/* Host only: what a call with (n, mode) launches -- resident (1) or streamed (0), threads per workgroup, owned points per thread
+ * and row tile, points per LDS stage (0 for the resident form).  Outputs are HOST pointers and may be NULL; no GPU call.
+ * Returns 0; 1 for n < 1 or an unknown mode; 3 for mode 1 above 4096 points and for n above 65536 (outputs 0). */
+int bdm_pairwise_emd_large_variant(int n, int mode, int *resident, int *threads, int *kpt, int *stage);
+/* paired = 0: out[i, j] = cost(a_i, b_j) / n, (s, r).  paired = 1: s == r, out[i] = cost(a_i, b_i) / n, (s).
+ * mode 0: resident while it fits, else streamed; 1: resident (3 if n > 4096); 2: streamed.  workspace: device memory of at least
+ * bdm_pairwise_emd_large_workspace_bytes(pairs, n) bytes, 4-byte aligned, contents irrelevant before and after.
+ * Returns 1 and launches nothing for bad sizes, a NULL pointer with work to do, s != r when paired, or a workspace too small;
+ * 3 for n > 65536.  s = 0 or r = 0 is a no-op. */
+int bdm_pairwise_emd_large(int s, int r, int n, int paired, int mode, const float *a, const float *b, void *workspace,
+                           size_t workspace_bytes, float *out, void *stream);
 
 /* ------------------------------------------------------------------------------------
  * 8. PC^2 colouring model (experiments/model/model_coloring.py, point_cloud_transformer_model.py:13-80 with
