@@ -33,6 +33,10 @@ class RunConfig:  # structured.py:14-56
     # orbit frames it adds per predicted cloud (1 = none; must divide 360)
     render_sample_dir: Optional[str] = None
     render_num_frames: int = 1
+    # "normals": the uncoloured kinds (gt, pred, the orbit of an uncoloured prediction) are shaded by their estimated normals
+    # (bdm_amd.normals, neighbourhoods of render_normals_k points) instead of rendering as black silhouettes; "none" = as before
+    render_shading: str = "none"
+    render_normals_k: int = 50
     save_dir: Optional[str] = None
     # not in the reference: "reference" = its draws (CPU generator for the initial cloud and the blend masks, the device's
     # global generator for DDPM / PVD noise, seeded seed + rank); "per_shape" = Philox streams keyed by (seed, global

@@ -39,6 +39,28 @@ def save_pointcloud_ply_rgb(points, colors, path):
         f.write(rec.tobytes())
 
 
+def save_pointcloud_ply_normals(points, normals, path):
+    """Binary little-endian PLY with float32 x, y, z, nx, ny, nz per vertex (what MeshLab and Open3D read as oriented points)."""
+    pts = np.asarray(points, dtype="<f4").reshape(-1, 3)
+    nrm = np.asarray(normals, dtype="<f4").reshape(-1, 3)
+    if nrm.shape[0] != pts.shape[0]:
+        raise ValueError(f"{pts.shape[0]} points but {nrm.shape[0]} normals")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    header = (f"ply\nformat binary_little_endian 1.0\nelement vertex {pts.shape[0]}\nproperty float x\nproperty float y\n"
+              "property float z\nproperty float nx\nproperty float ny\nproperty float nz\nend_header\n")
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(np.ascontiguousarray(np.concatenate([pts, nrm], axis=1)).tobytes())
+
+
+def _ply_normals(props, column):
+    """Per-vertex normals (n, 3) float32 from the nx / ny / nz properties; column(i) as in _ply_colors."""
+    names = [p[2] for p in props]
+    if not all(c in names for c in ("nx", "ny", "nz")):
+        raise ValueError("the PLY has no nx / ny / nz vertex properties")
+    return np.stack([column(names.index(c)).astype(np.float32) for c in ("nx", "ny", "nz")], axis=1)
+
+
 def _ply_colors(props, column):
     """Per-vertex colours in [0, 1] from the red / green / blue properties (uchar: / 255; float: as stored); column(i) -> the
     values of property i as a numpy array."""
@@ -53,9 +75,14 @@ def _ply_colors(props, column):
     return np.stack(cols, axis=1)
 
 
-def load_pointcloud_ply(path, with_colors=False):
+def load_pointcloud_ply(path, with_colors=False, with_normals=False):
     """(n, 3) float32 from an ASCII or binary-little-endian PLY whose vertex element starts with float x, y, z.
-    with_colors=True: (points, colors), colors (n, 3) float32 in [0, 1] from its red / green / blue properties."""
+    with_colors=True: (points, colors), colors (n, 3) float32 in [0, 1] from its red / green / blue properties.
+    with_normals=True: the normals (n, 3) float32 from its nx / ny / nz properties come last: (points, normals) or
+    (points, colors, normals)."""
+    def result(pts, column):
+        out = (pts,) + ((_ply_colors(props, column),) if with_colors else ()) + ((_ply_normals(props, column),) if with_normals else ())
+        return out if len(out) > 1 else pts
     with open(path, "rb") as f:
         raw = f.read()
     end = raw.index(b"end_header\n") + len(b"end_header\n")
@@ -66,10 +93,10 @@ def load_pointcloud_ply(path, with_colors=False):
     if fmt == "ascii":
         rows = raw[end:].decode("ascii").split("\n")[:n]
         pts = np.array([[float(v) for v in r.split()[:3]] for r in rows], dtype=np.float32).reshape(-1, 3)
-        if not with_colors:
+        if not (with_colors or with_normals):
             return pts
         table = np.array([[float(v) for v in r.split()] for r in rows], dtype=np.float64).reshape(n, -1)
-        return pts, _ply_colors(props, lambda i: table[:, i])
+        return result(pts, lambda i: table[:, i])
     if fmt != "binary_little_endian":
         raise ValueError(f"{path}: unsupported PLY format {fmt}")
     sizes = {"float": 4, "float32": 4, "double": 8, "float64": 8, "uchar": 1, "uint8": 1, "int": 4, "int32": 4}
@@ -78,14 +105,14 @@ def load_pointcloud_ply(path, with_colors=False):
         raise ValueError(f"{path}: vertex element must start with float x, y, z")
     body = np.frombuffer(raw, dtype=np.uint8, count=n * stride, offset=end).reshape(n, stride)
     pts = np.ascontiguousarray(body[:, :12]).view("<f4").reshape(n, 3).astype(np.float32)
-    if not with_colors:
+    if not (with_colors or with_normals):
         return pts
     offs = np.cumsum([0] + [sizes[p[1]] for p in props])
     kinds = {"float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8", "uchar": "u1", "uint8": "u1", "int": "<i4", "int32": "<i4"}
 
     def column(i):
         return np.ascontiguousarray(body[:, offs[i]:offs[i + 1]]).view(kinds[props[i][1]]).reshape(n)
-    return pts, _ply_colors(props, column)
+    return result(pts, column)
 
 
 def save_image_png(image_chw, path):

@@ -79,6 +79,24 @@ def render_pointcloud_batch_pytorch3d(cameras, pointclouds, image_size=224, radi
                    background_color, compositor, fragments=False)[1]
 
 
+def shade_by_normals(points, normals, cameras, ambient=0.3, albedo=(0.8, 0.8, 0.8)):
+    """Features (B, N, 3) that light an uncoloured cloud from its cameras: albedo * (ambient + (1 - ambient) |n . v|), v the unit
+    vector from the point to the camera centre (perspective) or the view axis (orthographic).  Two-sided, so the picture does
+    not depend on the sign rule of the normals.  Elementwise torch on whatever device the points live on: not a hot path."""
+    cameras = join_cameras(cameras)
+    if len(cameras) != points.shape[0]:
+        raise ValueError(f"{len(cameras)} cameras for {points.shape[0]} clouds")
+    R, T = cameras.R.to(points), cameras.T.to(points)
+    if cameras.orthographic:
+        v = R[:, :, 2][:, None, :].expand_as(points)                 # X_view = X_world R + T: the view z axis in world coordinates
+    else:
+        centre = -torch.bmm(T[:, None, :], R.transpose(1, 2))        # X_view = 0  <=>  X_world = -T R^T
+        v = centre - points
+        v = v / v.norm(dim=-1, keepdim=True).clamp_min(1e-12)
+    lambert = (normals.to(points) * v).sum(-1, keepdim=True).abs()
+    return torch.as_tensor(albedo, dtype=points.dtype, device=points.device) * (ambient + (1.0 - ambient) * lambert)
+
+
 def make_grid(tensor, nrow=8, padding=2, pad_value=0.0):
     """torchvision.utils.make_grid (restated; torchvision is absent) for a (B, C, H, W) batch with its defaults normalize=False,
     scale_each=False: single-channel images are repeated to three channels, ONE image is returned as it is (no border), otherwise

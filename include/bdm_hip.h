@@ -887,6 +887,34 @@ int bdm_color_block_tail(int b, int e, int n, const float *h, const float *p, co
 int bdm_occupancy_grid(int s, int n, int r, const float *clouds, const float *axis, const unsigned char *cell_mask,
                        int *hits, int *active, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * 10. Point-cloud normals (csrc/normals.hip): K nearest neighbours of every point within its own cloud, the covariance of the
+ *     neighbourhood and its eigen-decomposition, restating pytorch3d's estimate_pointcloud_normals (ops/points_normals.py) from
+ *     its published behaviour (pytorch3d is not installed: parity unpinned, as for the renderer).  DESIGN.md section 14.
+ * ---------------------------------------------------------------------------------- */
+/* points (b, n, 3) point-major.
+ * Neighbours: for query point i the candidates are all points j of the same cloud, i itself included.  dx = fl(x_j - x_i),
+ *   likewise dy and dz; d2 = fl(fl(fl(dx*dx) + fl(dy*dy)) + fl(dz*dz)), no FMA contraction.  The neighbourhood is the k candidates
+ *   with the smallest (d2, j), in ascending order; knn_idx (b, n, k) holds those j as the index within the cloud.  These indices
+ *   are bit-exact quantities, like the library's other neighbour indices.
+ * Covariance: e_j = p_j - p_i over the neighbourhood, C = (1/k) sum_j (e_j - ebar)(e_j - ebar)^T with ebar the mean of the e_j;
+ *   formed from these differences, never from sum p p^T - k mean^2; the summation order is the kernel's (fixed); all float32.
+ * Eigen-decomposition: curvatures (b, n, 3) = the three eigenvalues of C, ascending; normals (b, n, 3) = the unit eigenvector of
+ *   the smallest (cyclic Jacobi, a fixed sweep count, on the trace-scaled matrix).
+ * Sign: orient = 0: the component of largest magnitude is positive (ties: lowest axis).  orient = 1 (pytorch3d's
+ *   _disambiguate_vector_directions): n_pos = the number of neighbours with e_j . normal > 0; the normal is negated when
+ *   n_pos < 0.5 k.  orient = 2: negated when normal . (viewpoint_b - p_i) < 0, viewpoints (b, 3).
+ * Non-finite input: a point with a non-finite coordinate is nobody's neighbour; its own normal and curvatures are NaN and its
+ *   knn_idx row is -1.  A cloud with fewer than k finite points gets these values everywhere.
+ * Limits: 3 <= k <= 64, n > k, b >= 0 (b == 0 launches nothing and returns 0), b n k < 2^31, orient in {0, 1, 2}; viewpoints
+ *   non-NULL if and only if orient == 2.  Outside these the call returns 1 and launches nothing.  knn_idx and curvatures may be
+ *   NULL (the other outputs keep their bits).
+ * Determinism: no floating-point atomics; cloud j of a batch has the same bits as the same cloud run alone, and so does a
+ *   repeated call.  workspace: bdm_estimate_normals_workspace_bytes(b, n, k) bytes (0 in this implementation: NULL is accepted). */
+size_t bdm_estimate_normals_workspace_bytes(int b, int n, int k);
+int bdm_estimate_normals(int b, int n, int k, int orient, const float *points, const float *viewpoints, int *knn_idx,
+                         float *normals, float *curvatures, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

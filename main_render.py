@@ -6,6 +6,8 @@ Reads  ${run.render_sample_dir}/{gt,pred,colored}/<category>/<name>.ply  (also <
 only where main_coloring.py has written it), looks every <name> up in the dataset, and writes
 ${run.render_sample_dir}/renders/{gt,pred,colored}/<category>/<stem>.png.  With run.render_num_frames = F > 1 it also writes the
 orbiting orthographic view of every predicted cloud (the coloured one where it exists) as renders/orbit/<category>/<stem>-<f>.png.
+With run.render_shading=normals the uncoloured kinds (gt, pred, the orbit of an uncoloured prediction) are lit by their estimated
+normals (bdm_amd.normals, run.render_normals_k neighbours) instead of rendering as black silhouettes; `colored` is untouched.
 
     python main_blending.py run.job=sample_bdm_blending dataset=synthetic run.num_samples=1 dataset.max_points=1024
     python main_render.py dataset=synthetic run.render_sample_dir=<the directory the first command printed>
@@ -18,6 +20,7 @@ import torch
 from main_blending import get_dataloader
 
 KINDS = ("gt", "pred", "colored")
+SHADINGS = ("none", "normals")
 
 
 def parse_args(argv):
@@ -27,6 +30,8 @@ def parse_args(argv):
         raise ValueError("run.render_sample_dir=<directory holding pred/<category>/<name>.ply> is required")
     if cfg.run.render_num_frames < 1 or 360 % cfg.run.render_num_frames:
         raise ValueError("run.render_num_frames must divide 360")
+    if cfg.run.render_shading not in SHADINGS:
+        raise ValueError(f"run.render_shading={cfg.run.render_shading!r}: expected one of {SHADINGS}")
     return cfg
 
 
@@ -38,13 +43,20 @@ def clouds_of(sample_dir, kind, category, name):
     return hits
 
 
-def render_tree(cfg, batches, render_fn, orbit_fn=None, device="cpu"):
+def render_tree(cfg, batches, render_fn, orbit_fn=None, device="cpu", shade_fn=None):
     """Walk the dataset, render every cloud found under the sample directory, write renders/<kind>/<category>/<stem>.png; returns
     the paths written.  render_fn(cameras (list of single cameras), points (B, n, 3), colours (B, n, 3) or None) -> images
     (B, H, W, 3) in [0, 1]: one call per batch, kind and distinct point count.  orbit_fn(points (1, n, 3), colours or None,
-    path of <stem>.png, num_frames) -> the paths it wrote: called per predicted cloud when run.render_num_frames > 1."""
+    path of <stem>.png, num_frames) -> the paths it wrote: called per predicted cloud when run.render_num_frames > 1.
+    shade_fn(cameras, points (B, n, 3)) -> colours (B, n, 3): with run.render_shading=normals the uncoloured kinds get their
+    colours from it, once per batch group (a config without the key, or "none", leaves them None as before)."""
     from bdm_amd.io import load_pointcloud_ply, save_image_png
     root, written = Path(cfg.run.render_sample_dir), []
+    shading = getattr(cfg.run, "render_shading", "none")
+    if shading not in SHADINGS:
+        raise ValueError(f"run.render_shading={shading!r}: expected one of {SHADINGS}")
+    if shading == "normals" and shade_fn is None:
+        raise ValueError("run.render_shading=normals needs a shade_fn")
     for batch_idx, batch in enumerate(batches):
         if cfg.run.num_sample_batches is not None and batch_idx >= cfg.run.num_sample_batches:
             break
@@ -66,7 +78,10 @@ def render_tree(cfg, batches, render_fn, orbit_fn=None, device="cpu"):
         for (kind, _), items in sorted(groups.items()):
             points = torch.stack([it[2] for it in items]).to(device)
             colors = torch.stack([it[3] for it in items]).to(device) if kind == "colored" else None
-            images = render_fn([cameras[it[0]] for it in items], points, colors)
+            cams = [cameras[it[0]] for it in items]
+            if colors is None and shading == "normals":
+                colors = shade_fn(cams, points)
+            images = render_fn(cams, points, colors)
             for (i, path, _, _), image in zip(items, images):
                 out = root / "renders" / kind / batch.sequence_category[i] / f"{path.stem}.png"
                 save_image_png(image.detach().cpu().permute(2, 0, 1).numpy(), out)
@@ -86,7 +101,7 @@ def render_tree(cfg, batches, render_fn, orbit_fn=None, device="cpu"):
 def main(argv=None):
     from bdm_amd.cameras import Pointclouds
     from bdm_amd.distributed import barrier, gpu_turn, init_from_env
-    from bdm_amd.render import render_pointcloud_batch_pytorch3d, visualize_pointcloud_batch_pytorch3d
+    from bdm_amd.render import render_pointcloud_batch_pytorch3d, shade_by_normals, visualize_pointcloud_batch_pytorch3d
     cfg = parse_args(sys.argv[1:] if argv is None else argv)
     rank, local_rank, world = init_from_env()
     device = torch.device("cuda", local_rank)
@@ -96,13 +111,34 @@ def main(argv=None):
         with gpu_turn(device):
             return render_pointcloud_batch_pytorch3d(cameras, Pointclouds(points, colors)).cpu()
 
+    def shade_fn(cameras, points):
+        from bdm_amd.normals import estimate_pointcloud_normals
+        with gpu_turn(device):
+            return shade_by_normals(points, estimate_pointcloud_normals(points, cfg.run.render_normals_k), cameras)
+
     def orbit_fn(points, colors, path, num_frames):
+        if colors is None and cfg.run.render_shading == "normals":
+            return shaded_orbit(points, path, num_frames)
         with gpu_turn(device):
             visualize_pointcloud_batch_pytorch3d(Pointclouds(points, colors), output_file_image=str(path), num_frames=num_frames,
                                                  scale_factor=cfg.model.scale_factor)
         return [path.with_name(f"{path.stem}-{f}.png") for f in range(num_frames)]
 
-    written = render_tree(cfg, get_dataloader(cfg, rank, world), render_fn, orbit_fn, device)
+    def shaded_orbit(points, path, num_frames):
+        """The orbit of visualize_pointcloud_batch_pytorch3d (same cameras, same file names), every frame lit from its camera."""
+        from bdm_amd.cameras import OrthographicCameras, look_at_view_transform
+        from bdm_amd.normals import estimate_pointcloud_normals
+        out = [path.with_name(f"{path.stem}-{f}.png") for f in range(num_frames)]
+        with gpu_turn(device):
+            normals = estimate_pointcloud_normals(points, cfg.run.render_normals_k)
+            R, T = look_at_view_transform(dist=10.0, elev=30, azim=list(range(0, 360, 360 // num_frames)), degrees=True, device=device)
+            for f in range(num_frames):
+                cam = OrthographicCameras(focal_length=0.25 * cfg.model.scale_factor, device=device, R=R[f:f + 1], T=T[f:f + 1])
+                visualize_pointcloud_batch_pytorch3d(Pointclouds(points, shade_by_normals(points, normals, cam)),
+                                                     output_file_image=str(out[f]), cameras=cam)
+        return out
+
+    written = render_tree(cfg, get_dataloader(cfg, rank, world), render_fn, orbit_fn, device, shade_fn)
     barrier()
     print(f"rank {rank}: rendered {len(written)} images under {(Path(cfg.run.render_sample_dir) / 'renders').absolute()}")
     return written
