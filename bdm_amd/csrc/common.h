@@ -183,15 +183,33 @@ __device__ __forceinline__ float wave_max(float v) {
 #endif
 
 // workspace layout of the deterministic voxeliser (pvcnn_ops.hip: vox_plan_kernel)
+// Cell records: one per occupied row k of a shape (the order of occ_list), VOX_REC ints = 32 bytes:
+//   {count, start, p0 .. p5}  -- the cell's count and list start and the first six entries of its list (unused slots zero).
+// The feature gather of the sparse convolution reads ONE coalesced record per cell instead of walking occ_list -> cnt / start -> sorted
+// (three dependent round trips); lists longer than six continue in `sorted`.  Written by bdm_voxelize_plan_full only: rec_flag[shape]
+// says whether the shape's records exist (bdm_voxelize_plan, which knows no occupied rows, clears it).
+#define VOX_REC 8
+#define VOX_REC_PTS (VOX_REC - 2)
+// Layout (ints): start | rec_flag, padded to 16 bytes | rec | tmp | sorted -- `start` opens the workspace and `sorted` closes it.
 struct VoxWs {
-  int *start;   // [b][r3]  exclusive prefix of the per-voxel counts
-  int *tmp;     // [b][n]
-  int *sorted;  // [b][n]   per-voxel point lists, ascending point index inside a voxel
+  int *start;     // [b][r3]  exclusive prefix of the per-voxel counts
+  int *rec_flag;  // [b]      1: the shape's cell records are filled
+  int *rec;       // [b][rec_rows][VOX_REC], 16-byte aligned relative to the workspace
+  int *tmp;       // [b][n]
+  int *sorted;    // [b][n]   per-voxel point lists, ascending point index inside a voxel
+  int rec_rows;   // min(n, r3): no shape has more occupied cells
 };
+static inline size_t vox_ws_rec_offset(int b, int r3) { return ((size_t)b * r3 + (size_t)b + 3) & ~(size_t)3; }
+static inline size_t vox_ws_ints(int b, int n, int r3) {
+  return vox_ws_rec_offset(b, r3) + (size_t)b * (n < r3 ? n : r3) * VOX_REC + 2 * (size_t)b * n;
+}
 static inline VoxWs vox_ws(void *ws, int b, int n, int r3) {
   VoxWs w;
   w.start = (int *)ws;
-  w.tmp = w.start + (size_t)b * r3;
+  w.rec_flag = w.start + (size_t)b * r3;
+  w.rec = w.start + vox_ws_rec_offset(b, r3);
+  w.rec_rows = n < r3 ? n : r3;
+  w.tmp = w.rec + (size_t)b * w.rec_rows * VOX_REC;
   w.sorted = w.tmp + (size_t)b * n;
   return w;
 }

@@ -611,17 +611,173 @@ __global__ void fp_assemble_kernel(int n, int c_a, const float *__restrict__ fa,
   }
 }
 
+// LDS-staged form of the assembly.  The kernel above issues three scattered 4-byte loads per (point, channel) from a channel-first row:
+// the access pattern that left the feature gather of the sparse convolution bound by the texture-address unit (sparse_conv.hip).  Here a
+// workgroup owns (shape, chunk of `ch` source channels, slice of `pts_per` points): it copies the chunk's rows (ch x 4m bytes, coalesced)
+// into LDS, then walks its points V at a time -- the three indices and weights of a point are read once and held in registers across the
+// chunk's channels, the three operands come from LDS, and every output row is written in contiguous runs (16 bytes per thread with V = 4).
+// Chunks along the grid's y axis: [0, ka) interpolated features, [ka, ka + kt) interpolated t_emb, [ka + kt, ka + kt + ks) skip rows (a
+// plain copy, 16 bytes per thread where the source allows).  The expression per output element is the kernel above's: same bits.
+template <int V>
+__global__ __launch_bounds__(256) void fp_assemble_lds_kernel(int m, int n, int ch, int pts_per, int src_vec, int skip_vec, int c_a,
+                                                              const float *__restrict__ fa, long long bs_a, int ld_a, int c_s,
+                                                              const float *__restrict__ fs, long long bs_s, int ld_s, int c_t,
+                                                              const float *__restrict__ ft, long long bs_t, int ld_t,
+                                                              const int *__restrict__ indices, const float *__restrict__ weights,
+                                                              float *__restrict__ out0, long long bs_0, int ld_0,
+                                                              float *__restrict__ out1, long long bs_1, int ld_1) {
+  extern __shared__ float srow[];  // [ch][m]
+  const int tid = threadIdx.x, T = blockDim.x, bi = blockIdx.z;
+  const int ka = (c_a + ch - 1) / ch, kt = (c_t + ch - 1) / ch;
+  const int p_lo = blockIdx.x * pts_per, p_hi = min(n, p_lo + pts_per);
+  int y = blockIdx.y;
+  if (y >= ka + kt) {  // skip rows: out0[c_a + c] = fs[c]
+    const int c0 = (y - ka - kt) * ch, nc = min(ch, c_s - c0);
+    const float *src = fs + (size_t)bi * bs_s + (size_t)c0 * ld_s;
+    float *dst = out0 + (size_t)bi * bs_0 + (size_t)(c_a + c0) * ld_0;
+    for (int j = p_lo + tid * V; j < p_hi; j += T * V)
+      for (int cc = 0; cc < nc; ++cc) {
+        if (V == 4 && skip_vec) {
+          *reinterpret_cast<float4 *>(dst + (size_t)cc * ld_0 + j) = *reinterpret_cast<const float4 *>(src + (size_t)cc * ld_s + j);
+        } else {
+#pragma unroll
+          for (int u = 0; u < V; ++u) dst[(size_t)cc * ld_0 + j + u] = src[(size_t)cc * ld_s + j + u];
+        }
+      }
+    return;
+  }
+  const bool temb = y >= ka;
+  if (temb) y -= ka;
+  const int c0 = y * ch, nc = min(ch, (temb ? c_t : c_a) - c0);
+  const float *src = temb ? ft + (size_t)bi * bs_t + (size_t)c0 * ld_t : fa + (size_t)bi * bs_a + (size_t)c0 * ld_a;
+  const int ld_src = temb ? ld_t : ld_a;
+  const int ld_dst = temb ? ld_1 : ld_0;
+  float *dst = temb ? out1 + (size_t)bi * bs_1 + (size_t)c0 * ld_1 : out0 + (size_t)bi * bs_0 + (size_t)c0 * ld_0;
+  if (src_vec) {  // m, the row strides and the bases are multiples of 16 bytes
+    const int m4 = m >> 2;
+    for (int cc = 0; cc < nc; ++cc) {
+      const float4 *s4 = reinterpret_cast<const float4 *>(src + (size_t)cc * ld_src);
+      float4 *d4 = reinterpret_cast<float4 *>(srow + cc * m);
+      for (int p = tid; p < m4; p += T) d4[p] = s4[p];
+    }
+  } else {
+    for (int cc = 0; cc < nc; ++cc)
+      for (int p = tid; p < m; p += T) srow[cc * m + p] = src[(size_t)cc * ld_src + p];
+  }
+  __syncthreads();
+  const int *id = indices + (size_t)bi * 3 * n;
+  const float *w = weights + (size_t)bi * 3 * n;
+  for (int j = p_lo + tid * V; j < p_hi; j += T * V) {  // V == 4: n and pts_per are multiples of 4, so j + 3 < p_hi
+    int i0[V], i1[V], i2[V];
+    float w0[V], w1[V], w2[V];
+    if constexpr (V == 4) {
+      const int4 a = *reinterpret_cast<const int4 *>(id + j), b4 = *reinterpret_cast<const int4 *>(id + n + j),
+                 c4 = *reinterpret_cast<const int4 *>(id + 2 * (size_t)n + j);
+      const float4 x = *reinterpret_cast<const float4 *>(w + j), y4 = *reinterpret_cast<const float4 *>(w + n + j),
+                   z = *reinterpret_cast<const float4 *>(w + 2 * (size_t)n + j);
+      i0[0] = a.x; i0[1] = a.y; i0[2] = a.z; i0[3] = a.w;
+      i1[0] = b4.x; i1[1] = b4.y; i1[2] = b4.z; i1[3] = b4.w;
+      i2[0] = c4.x; i2[1] = c4.y; i2[2] = c4.z; i2[3] = c4.w;
+      w0[0] = x.x; w0[1] = x.y; w0[2] = x.z; w0[3] = x.w;
+      w1[0] = y4.x; w1[1] = y4.y; w1[2] = y4.z; w1[3] = y4.w;
+      w2[0] = z.x; w2[1] = z.y; w2[2] = z.z; w2[3] = z.w;
+    } else {
+      i0[0] = id[j]; i1[0] = id[n + j]; i2[0] = id[2 * (size_t)n + j];
+      w0[0] = w[j]; w1[0] = w[n + j]; w2[0] = w[2 * (size_t)n + j];
+    }
+#pragma unroll 4
+    for (int cc = 0; cc < nc; ++cc) {
+      const float *fr = srow + cc * m;
+      float o[V];
+#pragma unroll
+      for (int u = 0; u < V; ++u)
+        o[u] = __fadd_rn(__fadd_rn(__fmul_rn(fr[i0[u]], w0[u]), __fmul_rn(fr[i1[u]], w1[u])), __fmul_rn(fr[i2[u]], w2[u]));
+      if constexpr (V == 4) {
+        *reinterpret_cast<float4 *>(dst + (size_t)cc * ld_dst + j) = make_float4(o[0], o[1], o[2], o[3]);
+      } else {
+        dst[(size_t)cc * ld_dst + j] = o[0];
+      }
+    }
+  }
+}
+
+static bool aligned16(const void *p, long long bs, int ld) { return (reinterpret_cast<size_t>(p) & 15) == 0 && (bs & 3) == 0 && (ld & 3) == 0; }
+
+// form: 0 = by sizes (the staged kernel wherever a source row fits its LDS budget), 1 = the per-point kernel, 2 = the staged kernel or an error
+static int fp_assemble_launch(int form, int b, int m, int n, const int *indices, const float *weights, int c_a, const float *fa,
+                              long long bs_a, int ld_a, int c_s, const float *fs, long long bs_s, int ld_s, int c_t, const float *ft,
+                              long long bs_t, int ld_t, float *out0, long long bs_0, int ld_0, float *out1, long long bs_1, int ld_1,
+                              void *stream) {
+  BDM_REQUIRE(b >= 0 && m >= 1 && n >= 0 && c_a >= 0 && c_s >= 0 && c_t >= 0, "fp_assemble: bad sizes");
+  BDM_REQUIRE(form >= 0 && form <= 2, "fp_assemble: form must be 0, 1 or 2");
+  if (b == 0 || n == 0 || c_a + c_s + c_t == 0) return BDM_OK;
+  constexpr int LDS_BUDGET = 32 * 1024, LDS_MAX = 64 * 1024;  // per workgroup: four to five workgroups co-reside on a CU's 160 KB
+  const bool fits = (size_t)m * 4 <= LDS_MAX && b <= 65535;
+  BDM_REQUIRE(form != 2 || fits, "fp_assemble: the staged form needs m <= 16384 and b <= 65535");
+  // n <= 256 (the two coarsest FP stages): a launch of ~5 us either way, the staged form measured 0.3 - 1 us slower
+  if (form == 1 || !fits || (form == 0 && n <= 256)) {
+    const int c = c_a + c_s + c_t;
+    dim3 grid(cdiv(n, 256), c < 64 ? c : 64, b);
+    hipLaunchKernelGGL(fp_assemble_kernel, grid, dim3(256), 0, (hipStream_t)stream, n, c_a, fa, bs_a, ld_a, c_s, fs, bs_s, ld_s, c_t,
+                       ft, bs_t, ld_t, indices, weights, out0, bs_0, ld_0, out1, bs_1, ld_1);
+    return launch_status("fp_assemble");
+  }
+  // source channels per workgroup: 8 where the rows allow (32 KB at m = 1024), fewer for longer rows
+  int ch = LDS_BUDGET / (4 * m);
+  ch = ch < 1 ? 1 : (ch > 8 ? 8 : ch);
+  const int chunks = cdiv(c_a, ch) + cdiv(c_t, ch) + cdiv(c_s, ch);
+  // four points per thread when every index / weight / output row can be accessed 16 bytes at a time
+  const bool v4 = (n & 3) == 0 && (reinterpret_cast<size_t>(indices) & 15) == 0 && (reinterpret_cast<size_t>(weights) & 15) == 0 &&
+                  (c_a + c_s == 0 || aligned16(out0, bs_0, ld_0)) && (c_t == 0 || aligned16(out1, bs_1, ld_1));
+  const int V = v4 ? 4 : 1;
+  const int src_vec = (m & 3) == 0 && (c_a == 0 || aligned16(fa, bs_a, ld_a)) && (c_t == 0 || aligned16(ft, bs_t, ld_t));
+  const int skip_vec = c_s == 0 || aligned16(fs, bs_s, ld_s);
+  const int T = min(256, max(64, (cdiv(n, V) + 63) & ~63));
+  // point slices: enough workgroups for two per CU, each slice at least one pass of the workgroup (every slice restages its chunk's rows)
+  int cus = 256;
+  {
+    int dev = 0, v = 0;
+    static int cached[16] = {0};
+    (void)hipGetDevice(&dev);
+    if (dev >= 0 && dev < 16) {
+      if (cached[dev] == 0 && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cached[dev] = v;
+      if (cached[dev] > 0) cus = cached[dev];
+    }
+  }
+  const int pass = T * V;
+  long long slices = cdivll(2ll * cus, (long long)b * chunks);
+  slices = slices < 1 ? 1 : slices;
+  if (slices > cdiv(n, pass)) slices = cdiv(n, pass);
+  const int pts_per = cdiv(cdiv(n, (int)slices), pass) * pass;
+  dim3 grid(cdiv(n, pts_per), chunks, b);
+  BDM_REQUIRE(chunks <= 65535, "fp_assemble: too many channels");
+  const size_t smem = sizeof(float) * (size_t)ch * m;
+  if (v4) {
+    BDM_ALLOW_LDS(fp_assemble_lds_kernel<4>, smem);
+    hipLaunchKernelGGL(fp_assemble_lds_kernel<4>, grid, dim3(T), smem, (hipStream_t)stream, m, n, ch, pts_per, src_vec, skip_vec, c_a, fa,
+                       bs_a, ld_a, c_s, fs, bs_s, ld_s, c_t, ft, bs_t, ld_t, indices, weights, out0, bs_0, ld_0, out1, bs_1, ld_1);
+  } else {
+    BDM_ALLOW_LDS(fp_assemble_lds_kernel<1>, smem);
+    hipLaunchKernelGGL(fp_assemble_lds_kernel<1>, grid, dim3(T), smem, (hipStream_t)stream, m, n, ch, pts_per, src_vec, skip_vec, c_a, fa,
+                       bs_a, ld_a, c_s, fs, bs_s, ld_s, c_t, ft, bs_t, ld_t, indices, weights, out0, bs_0, ld_0, out1, bs_1, ld_1);
+  }
+  return launch_status("fp_assemble");
+}
+
 extern "C" int bdm_fp_assemble(int b, int m, int n, const int *indices, const float *weights, int c_a, const float *fa,
                                long long bs_a, int ld_a, int c_s, const float *fs, long long bs_s, int ld_s, int c_t,
                                const float *ft, long long bs_t, int ld_t, float *out0, long long bs_0, int ld_0, float *out1,
                                long long bs_1, int ld_1, void *stream) {
-  BDM_REQUIRE(b >= 0 && m >= 1 && n >= 0 && c_a >= 0 && c_s >= 0 && c_t >= 0, "fp_assemble: bad sizes");
-  if (b == 0 || n == 0 || c_a + c_s + c_t == 0) return BDM_OK;
-  const int c = c_a + c_s + c_t;
-  dim3 grid(cdiv(n, 256), c < 64 ? c : 64, b);
-  hipLaunchKernelGGL(fp_assemble_kernel, grid, dim3(256), 0, (hipStream_t)stream, n, c_a, fa, bs_a, ld_a, c_s, fs, bs_s, ld_s, c_t,
-                     ft, bs_t, ld_t, indices, weights, out0, bs_0, ld_0, out1, bs_1, ld_1);
-  return launch_status("fp_assemble");
+  return fp_assemble_launch(0, b, m, n, indices, weights, c_a, fa, bs_a, ld_a, c_s, fs, bs_s, ld_s, c_t, ft, bs_t, ld_t, out0, bs_0, ld_0,
+                            out1, bs_1, ld_1, stream);
+}
+
+extern "C" int bdm_fp_assemble_form(int form, int b, int m, int n, const int *indices, const float *weights, int c_a, const float *fa,
+                                    long long bs_a, int ld_a, int c_s, const float *fs, long long bs_s, int ld_s, int c_t,
+                                    const float *ft, long long bs_t, int ld_t, float *out0, long long bs_0, int ld_0, float *out1,
+                                    long long bs_1, int ld_1, void *stream) {
+  return fp_assemble_launch(form, b, m, n, indices, weights, c_a, fa, bs_a, ld_a, c_s, fs, bs_s, ld_s, c_t, ft, bs_t, ld_t, out0, bs_0,
+                            ld_0, out1, bs_1, ld_1, stream);
 }
 
 extern "C" int bdm_three_nn_interpolate_forward(int b, int c, int m, int n, const float *points,
@@ -641,13 +797,14 @@ extern "C" int bdm_three_nn_interpolate_forward(int b, int c, int m, int n, cons
 //   ascending point index (unordered atomic fill, then rank-within-list placement).
 // Reduce kernel: out[c][v] = sum over list(v), in list order, of feat[c][p] * (1/cnt[v]).
 extern "C" size_t bdm_voxelize_workspace_bytes(int b, int n, int r) {
-  return sizeof(int) * ((size_t)b * r * r * r + 2 * (size_t)b * n);
+  return sizeof(int) * vox_ws_ints(b, n, r * r * r);  // start, cell records, tmp, sorted (common.h: VoxWs)
 }
 
 __global__ void vox_plan_kernel(int n, int r, const int *__restrict__ coords, int *__restrict__ ind,
                                 int *__restrict__ cnt, int *__restrict__ start, int *__restrict__ tmp,
                                 int *__restrict__ sorted, int n_max, int *__restrict__ occ_index,
-                                int *__restrict__ occ_list, int *__restrict__ n_occ, unsigned char *__restrict__ rowocc) {
+                                int *__restrict__ occ_list, int *__restrict__ n_occ, unsigned char *__restrict__ rowocc,
+                                int *__restrict__ rec_flag, int *__restrict__ rec, int rec_rows) {
   extern __shared__ int lcnt[];  // [r3] counters, then cursors
   __shared__ int wave_tot[16];
   const int r2 = r * r, r3 = r2 * r;
@@ -694,7 +851,10 @@ __global__ void vox_plan_kernel(int n, int r, const int *__restrict__ coords, in
     for (int q = 0; q < cv; ++q) rank += tp[s + q] < i;
     so[s + rank] = i;
   }
-  if (occ_index == nullptr) return;
+  if (occ_index == nullptr) {
+    if (tid == 0) rec_flag[bi] = 0;  // no occupied rows, no cell records
+    return;
+  }
   // ---- optional tail (bdm_voxelize_plan_full): occupied-cell compaction and row occupancy of the same shape, in the
   // launch that already owns it (what bdm_voxel_compact + bdm_voxel_row_occupancy do in two more launches)
   __syncthreads();
@@ -714,11 +874,22 @@ __global__ void vox_plan_kernel(int n, int r, const int *__restrict__ coords, in
   int off = 0, total = 0;
   for (int w = 0; w < (T >> 6); ++w) { if (w < wave) off += wave_tot[w]; total += wave_tot[w]; }
   int orun = off + oincl - occ_local;
+  int4 *rc = reinterpret_cast<int4 *>(rec + (size_t)bi * rec_rows * VOX_REC);
   for (int v = lo; v < hi; ++v) {
-    if (gc[v] > 0) { oi[v] = orun; ol[orun] = v; ++orun; }
-    else oi[v] = -1;
+    const int cv = gc[v];
+    if (cv > 0) {
+      oi[v] = orun; ol[orun] = v;
+      // the cell's record (common.h): count, start and the head of its list (written above by this workgroup, behind a barrier)
+      const int s = gs[v];
+      int pq[VOX_REC_PTS];
+#pragma unroll
+      for (int q = 0; q < VOX_REC_PTS; ++q) pq[q] = q < cv ? so[s + q] : 0;
+      rc[2 * orun] = make_int4(cv, s, pq[0], pq[1]);
+      rc[2 * orun + 1] = make_int4(pq[2], pq[3], pq[4], pq[5]);
+      ++orun;
+    } else oi[v] = -1;
   }
-  if (tid == 0) n_occ[bi] = total;
+  if (tid == 0) { n_occ[bi] = total; rec_flag[bi] = 1; }
   for (int row = tid; row < r2; row += T) {
     int any = 0;
     for (int z = 0; z < r; ++z) any |= gc[row * r + z];
@@ -736,7 +907,8 @@ __global__ __launch_bounds__(1024) void vox_plan_slab_kernel(int n, int r, int s
                                                              int *__restrict__ ind, int *__restrict__ cnt,
                                                              int *__restrict__ start, int *__restrict__ sorted, int n_max,
                                                              int *__restrict__ occ_index, int *__restrict__ occ_list,
-                                                             int *__restrict__ n_occ, unsigned char *__restrict__ rowocc) {
+                                                             int *__restrict__ n_occ, unsigned char *__restrict__ rowocc,
+                                                             int *__restrict__ rec_flag, int *__restrict__ rec, int rec_rows) {
   extern __shared__ int slab_smem[];
   constexpr int T = 1024, PER = CS / T;  // cells per thread (contiguous run)
   static_assert(CS % T == 0 && PER >= 1, "slab size must be a multiple of the workgroup size");
@@ -744,7 +916,8 @@ __global__ __launch_bounds__(1024) void vox_plan_slab_kernel(int n, int r, int s
   int *lcnt = slab_smem;                                   // [CS] counters, then cursors
   unsigned *bits = reinterpret_cast<unsigned *>(lcnt + CS);  // [r3 / 32] occupancy of the whole grid
   int *lbeg = reinterpret_cast<int *>(bits + r3 / 32);     // [CS] slab-local start of each cell's list
-  int *lst = lbeg + CS;                                    // [n] the slab's points grouped by cell (unordered inside a cell)
+  int *lrow = lbeg + CS;                                   // [CS] occupied-row number of each cell (cell records)
+  int *lst = lrow + CS;                                    // [n] the slab's points grouped by cell (unordered inside a cell)
   __shared__ int red[16], red2[16];
   const int bi = blockIdx.x / slabs, sl = blockIdx.x % slabs, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lo_cell = sl * CS;
@@ -782,6 +955,8 @@ __global__ __launch_bounds__(1024) void vox_plan_slab_kernel(int n, int r, int s
   int point_base = 0, occ_base = 0, occ_all = 0;
   for (int w = 0; w < T / 64; ++w) { point_base += red[w]; occ_base += red2[w]; occ_all += red3[w]; }
   if (sl == 0 && tid == 0 && n_occ != nullptr) n_occ[bi] = occ_all;
+  if (sl == 0 && tid == 0) rec_flag[bi] = occ_index != nullptr;  // cell records (common.h) exist with the occupied rows only
+  int *const rc = rec + (size_t)bi * rec_rows * VOX_REC;
   __syncthreads();  // red / red2 are reused below
 
   // exclusive scans over the slab's cells (points and occupied cells): each thread owns PER contiguous cells
@@ -808,8 +983,14 @@ __global__ __launch_bounds__(1024) void vox_plan_slab_kernel(int n, int r, int s
     lcnt[tid * PER + j] = run;  // cursor for the fill below
     lbeg[tid * PER + j] = run;
     if (occ_index != nullptr) {
-      if (cv[j] > 0) { occ_index[(size_t)bi * r3 + v] = orun; occ_list[(size_t)bi * n_max + orun] = v; ++orun; }
-      else occ_index[(size_t)bi * r3 + v] = -1;
+      if (cv[j] > 0) {
+        occ_index[(size_t)bi * r3 + v] = orun; occ_list[(size_t)bi * n_max + orun] = v;
+        // the cell's record: count, start, empty list head (its entries are placed with the list below)
+        reinterpret_cast<int4 *>(rc)[2 * orun] = make_int4(cv[j], point_base + run, 0, 0);
+        reinterpret_cast<int4 *>(rc)[2 * orun + 1] = make_int4(0, 0, 0, 0);
+        lrow[tid * PER + j] = orun;
+        ++orun;
+      } else occ_index[(size_t)bi * r3 + v] = -1;
     }
     run += cv[j];
   }
@@ -839,6 +1020,7 @@ __global__ __launch_bounds__(1024) void vox_plan_slab_kernel(int n, int r, int s
       int rank = 0;
       for (int q = 0; q < cvv; ++q) rank += lst[s0 + q] < i;
       so[point_base + s0 + rank] = i;
+      if (occ_index != nullptr && rank < VOX_REC_PTS) rc[(size_t)lrow[v - lo_cell] * VOX_REC + 2 + rank] = i;
     }
   }
 }
@@ -874,7 +1056,8 @@ extern "C" int bdm_voxelize_plan(int b, int n, int r, const int *coords, int *in
   const size_t smem = (size_t)r3 * sizeof(int);
   BDM_ALLOW_LDS(vox_plan_kernel, smem);
   hipLaunchKernelGGL(vox_plan_kernel, dim3(b), dim3(1024), smem, (hipStream_t)stream, n, r, coords, ind, cnt, w.start,
-                     w.tmp, w.sorted, 0, (int *)nullptr, (int *)nullptr, (int *)nullptr, (unsigned char *)nullptr);
+                     w.tmp, w.sorted, 0, (int *)nullptr, (int *)nullptr, (int *)nullptr, (unsigned char *)nullptr, w.rec_flag, w.rec,
+                     w.rec_rows);
   return launch_status("vox_plan");
 }
 
@@ -885,17 +1068,17 @@ extern "C" int bdm_voxelize_plan_full(int b, int n, int r, int n_max, const int 
   if (b == 0) return BDM_OK;
   const int r3 = r * r * r;
   VoxWs w = vox_ws(workspace, b, n, r3);
-  if (r == 32 && n <= 24576 && vox_plan_slabs()) {  // eight workgroups per shape (LDS: 2 x 16 KB counters / starts + 4 KB bitset + 4 n bytes)
-    const size_t sm = sizeof(int) * (2 * 4096 + (size_t)r3 / 32 + (size_t)n);
+  if (r == 32 && n <= 24576 && vox_plan_slabs()) {  // eight workgroups per shape (LDS: 3 x 16 KB counters / starts / rows + 4 KB bitset + 4 n bytes)
+    const size_t sm = sizeof(int) * (3 * 4096 + (size_t)r3 / 32 + (size_t)n);
     BDM_ALLOW_LDS(vox_plan_slab_kernel<4096>, sm);
     hipLaunchKernelGGL(vox_plan_slab_kernel<4096>, dim3(b * 8), dim3(1024), sm, (hipStream_t)stream, n, r, 8, coords, ind, cnt,
-                       w.start, w.sorted, n_max, occ_index, occ_list, n_occ, rowocc);
+                       w.start, w.sorted, n_max, occ_index, occ_list, n_occ, rowocc, w.rec_flag, w.rec, w.rec_rows);
     return launch_status("vox_plan_full");
   }
   const size_t smem = (size_t)r3 * sizeof(int);
   BDM_ALLOW_LDS(vox_plan_kernel, smem);
   hipLaunchKernelGGL(vox_plan_kernel, dim3(b), dim3(1024), smem, (hipStream_t)stream, n, r, coords, ind, cnt, w.start,
-                     w.tmp, w.sorted, n_max, occ_index, occ_list, n_occ, rowocc);
+                     w.tmp, w.sorted, n_max, occ_index, occ_list, n_occ, rowocc, w.rec_flag, w.rec, w.rec_rows);
   return launch_status("vox_plan_full");
 }
 

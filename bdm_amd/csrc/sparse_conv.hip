@@ -204,6 +204,7 @@ __global__ void sparse_vox_features_s3_kernel(int c, int n, int r3, int n_max, i
 //   OUT = 0: bf16-triple records (sparse_gemm_s3);  OUT = 1: fp32 records + max |value| (sparse_gemm_h2 path)
 // With few channel groups (32-channel layers: 4 groups x 16 shapes = 64 units) `ksplit` workgroups share a unit, each with
 // its own copy of the rows and a slice of `cells_per` cells.
+// The cells' counts, list starts and list heads come from the plan's cell records (common.h: VoxWs), one coalesced 32-byte load per cell.
 template <int OUT>
 __global__ __launch_bounds__(1024) void sparse_vox_features_lds_kernel(int c, int n, int r3, int n_max, int G, int ksplit,
                                                                        int cells_per,
@@ -211,7 +212,9 @@ __global__ __launch_bounds__(1024) void sparse_vox_features_lds_kernel(int c, in
                                                                        const int *__restrict__ cnt, const int *__restrict__ start,
                                                                        const int *__restrict__ sorted,
                                                                        const int *__restrict__ occ_list,
-                                                                       const int *__restrict__ n_occ, void *__restrict__ outp,
+                                                                       const int *__restrict__ n_occ,
+                                                                       const int *__restrict__ rec_flag, const int *__restrict__ rec,
+                                                                       int rec_rows, void *__restrict__ outp,
                                                                        unsigned *__restrict__ amax) {
 #pragma clang fp contract(off)  // same arithmetic as vox_reduce_kernel: the values equal the dense grid's bit for bit
   extern __shared__ float frows[];  // [8][n]
@@ -219,13 +222,14 @@ __global__ __launch_bounds__(1024) void sparse_vox_features_lds_kernel(int c, in
   const int unit = blockIdx.x / ksplit, k0 = (blockIdx.x % ksplit) * cells_per, bi = unit / G, g = unit % G;
   const int tid = threadIdx.x, T = blockDim.x;
   const int nocc = min(n_occ[bi], n_max);
+  const bool has_rec = rec_flag[bi] != 0;  // the plan carries cell records (common.h: VoxWs) -- plans of bdm_voxelize_plan_full do
   // rows the consumers read: the GEMM's last 128-row tile that holds an occupied cell (S3) / every row (fp32 records: split pass)
   const int lim = min(OUT == 0 ? min((nocc + 127) & ~127, n_max) : n_max, k0 + cells_per);
   if (k0 >= lim) return;  // nothing to write in this slice
   const int nch = min(8, c - g * 8);
-  // The group's rows go to registers FIRST (independent loads, 16 bytes each): a wave issues in order, so behind the index chain below
-  // (cell -> count / start -> first list entries: three dependent round trips, each ending in a wait) they would not even be requested
-  // before the chain is through -- four serial trips instead of three overlapped with one.
+  // The rows go to registers FIRST (independent loads, 16 bytes each): a wave issues in order, so behind the index loads below (one
+  // record per cell; without records cell -> count / start -> first list entries: three dependent round trips, each ending in a wait)
+  // they would not even be requested before those are through.
   const float *fb = feat + (size_t)bi * bs_f + (size_t)g * 8 * ld_f;
   const bool vec = (n & 3) == 0 && (ld_f & 3) == 0 && ((reinterpret_cast<size_t>(fb) & 15) == 0) && (n >> 2) <= T;   // 16-byte row pieces, one per thread and row
   const int n4 = n >> 2;
@@ -235,26 +239,38 @@ __global__ __launch_bounds__(1024) void sparse_vox_features_lds_kernel(int c, in
     for (int j = 0; j < 8; ++j)
       rowv[j] = reinterpret_cast<const float4 *>(fb + (size_t)min(j, nch - 1) * ld_f)[min(tid, n4 - 1)];
   }
-  // the cells' point lists (two dependent index loads) are fetched while the rows stream in
-  int cs[CPT], cc[CPT];
+  // the cells' counts, list starts and list heads are fetched while the rows stream in: ONE coalesced 32-byte record per cell ...
+  constexpr int PRE = VOX_REC_PTS;
+  int cs[CPT], cc[CPT], pre[CPT][PRE];
+  if (has_rec) {
+    const int4 *rc = reinterpret_cast<const int4 *>(rec + (size_t)bi * rec_rows * VOX_REC);
 #pragma unroll
-  for (int i = 0; i < CPT; ++i) {
-    const int k = k0 + tid + i * T;
-    cs[i] = 0; cc[i] = 0;
-    if (k < nocc && k < lim) {
-      const int v = occ_list[(size_t)bi * n_max + k];
-      cc[i] = cnt[(size_t)bi * r3 + v];
-      cs[i] = start[(size_t)bi * r3 + v];
+    for (int i = 0; i < CPT; ++i) {
+      const int k = k0 + tid + i * T;
+      int4 a = make_int4(0, 0, 0, 0), b4 = make_int4(0, 0, 0, 0);
+      if (k < nocc && k < lim) { a = rc[2 * k]; b4 = rc[2 * k + 1]; }
+      cc[i] = a.x; cs[i] = a.y;
+      pre[i][0] = a.z; pre[i][1] = a.w; pre[i][2] = b4.x; pre[i][3] = b4.y; pre[i][4] = b4.z; pre[i][5] = b4.w;
     }
-  }
-  // ... and so are the first four entries of each cell's point list (cells hold 1 - 3 points on these levels): after the barrier the
-  // common cell needs LDS only (its list read there was one more dependent round trip per cell, two per thread at 32^3)
-  int pre[CPT][4];
+  } else {
+    // ... or, on a plan without records, the chain occupied row -> cell -> count / start -> first list entries (cells hold 1 - 3 points
+    // on these levels: after the barrier the common cell needs LDS only)
 #pragma unroll
-  for (int i = 0; i < CPT; ++i) {
-    const int *so = sorted + (size_t)bi * n + cs[i];
+    for (int i = 0; i < CPT; ++i) {
+      const int k = k0 + tid + i * T;
+      cs[i] = 0; cc[i] = 0;
+      if (k < nocc && k < lim) {
+        const int v = occ_list[(size_t)bi * n_max + k];
+        cc[i] = cnt[(size_t)bi * r3 + v];
+        cs[i] = start[(size_t)bi * r3 + v];
+      }
+    }
 #pragma unroll
-    for (int u = 0; u < 4; ++u) pre[i][u] = cc[i] > 0 ? so[min(u, cc[i] - 1)] : 0;
+    for (int i = 0; i < CPT; ++i) {
+      const int *so = sorted + (size_t)bi * n + cs[i];
+#pragma unroll
+      for (int u = 0; u < PRE; ++u) pre[i][u] = cc[i] > 0 ? so[min(u, cc[i] - 1)] : 0;
+    }
   }
   if (vec) {
     if (tid < n4) {
@@ -291,7 +307,8 @@ __global__ __launch_bounds__(1024) void sparse_vox_features_lds_kernel(int c, in
     for (int q0 = 0; q0 < cv; q0 += 4) {
       int p[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) p[u] = q0 == 0 ? pre[i][u] : so[min(q0 + u, cv - 1)];
+      for (int u = 0; u < 4; ++u)  // list entries 0 .. 5 are in registers, the rest of a long list comes from `sorted`
+        p[u] = q0 == 0 ? pre[i][u] : (q0 == 4 && u < PRE - 4 ? pre[i][min(4 + u, PRE - 1)] : so[min(q0 + u, cv - 1)]);
 #pragma unroll
       for (int u = 0; u < 4; ++u)
         if (q0 + u < cv) {
@@ -310,48 +327,53 @@ __global__ __launch_bounds__(1024) void sparse_vox_features_lds_kernel(int c, in
     }
   }
   if (OUT == 1) {
+    // per shape; non-negative floats order as unsigned ints.  ONE atomic per workgroup, and none when the slot already holds as much
+    // (it only grows, so a stale read errs on the safe side): the atomics of a shape all hit one address and are served one after the
+    // other -- with one per wave they, not the gather, set this kernel's duration (measured: 34 us at 128 waves per shape against 13 us
+    // for the same gather without a maximum)
+    __shared__ float wmax[16];
     m = wave_max(m);
-    if ((tid & 63) == 0 && m > 0.f) atomicMax(amax + bi, __float_as_uint(m));  // per shape; non-negative floats order as unsigned ints
+    if ((tid & 63) == 0) wmax[tid >> 6] = m;
+    __syncthreads();
+    if (tid == 0) {
+      for (int w = 1; w < (T >> 6); ++w) m = fmaxf(m, wmax[w]);
+      if (m > 0.f && __float_as_uint(m) > __atomic_load_n(amax + bi, __ATOMIC_RELAXED)) atomicMax(amax + bi, __float_as_uint(m));
+    }
   }
 }
 
-// shared launcher (also used by bdm_sparse_voxel_features_f32 in sparse_conv_fused.hip); false: shape not covered
-bool bdm_sparse_features_lds_launch(int out_kind, int b, int c, int n, int r3, int n_max, const float *features, long long bs_f,
-                                    int ld_f, const int *cnt, const int *start, const int *sorted, const int *occ_list,
-                                    const int *n_occ, void *out, unsigned *amax, hipStream_t stream, int *rc) {
-  if (bdm_staging_choice() == 0 || n > 4096 || n_max > 4096) return false;  // BDM_STAGING=0 keeps the global-memory gather (common.h)
+template <int OUT>
+static bool sparse_features_lds_go(int b, int c, int n, int r3, int n_max, const float *features, long long bs_f, int ld_f, const int *cnt,
+                                   const VoxWs &w, const int *occ_list, const int *n_occ, void *out, unsigned *amax, hipStream_t stream) {
   const int G = (c + 7) / 8, units = b * G;
   // workgroups per unit: every extra one refills the rows, which costs more than the parallelism gains (measured: 32-channel
-  // layer at 32^3, 8 slices: 132 -> 207 us)
+  // layer at 32^3, 8 slices: 132 -> 207 us); cutting a unit's CHANNELS over 2 or 4 workgroups (each staging its own rows only) is
+  // slower too
   const int ksplit = 1;
   const int cells_per = ((n_max + ksplit - 1) / ksplit + 63) & ~63;
   const int T = cells_per > 1024 ? 1024 : 256;  // 4 cells per thread cover the slice
   const size_t smem = sizeof(float) * 8 * (size_t)n;
-  *rc = BDM_OK;
-  if (out_kind == 0) {
-    static int granted0[16] = {0};  // per device: the attribute call costs microseconds of host time, once is enough
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (smem > 48 * 1024 && (dev < 0 || dev >= 16 || granted0[dev] < (int)smem)) {
-      hipError_t e = hipFuncSetAttribute((const void *)sparse_vox_features_lds_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      if (e != hipSuccess) return false;
-      if (dev >= 0 && dev < 16) granted0[dev] = (int)smem;
-    }
-    hipLaunchKernelGGL(sparse_vox_features_lds_kernel<0>, dim3(units * ksplit), dim3(T), smem, stream, c, n, r3, n_max, G, ksplit,
-                       cells_per, features, bs_f, ld_f, cnt, start, sorted, occ_list, n_occ, out, amax);
-  } else {
-    static int granted1[16] = {0};  // per device: the attribute call costs microseconds of host time, once is enough
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (smem > 48 * 1024 && (dev < 0 || dev >= 16 || granted1[dev] < (int)smem)) {
-      hipError_t e = hipFuncSetAttribute((const void *)sparse_vox_features_lds_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      if (e != hipSuccess) return false;
-      if (dev >= 0 && dev < 16) granted1[dev] = (int)smem;
-    }
-    hipLaunchKernelGGL(sparse_vox_features_lds_kernel<1>, dim3(units * ksplit), dim3(T), smem, stream, c, n, r3, n_max, G, ksplit,
-                       cells_per, features, bs_f, ld_f, cnt, start, sorted, occ_list, n_occ, out, amax);
+  static int granted[16] = {0};  // per (kernel, device): the attribute call costs microseconds of host time, once is enough
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (smem > 48 * 1024 && (dev < 0 || dev >= 16 || granted[dev] < (int)smem)) {
+    hipError_t e = hipFuncSetAttribute((const void *)sparse_vox_features_lds_kernel<OUT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (e != hipSuccess) return false;
+    if (dev >= 0 && dev < 16) granted[dev] = (int)smem;
   }
+  hipLaunchKernelGGL(sparse_vox_features_lds_kernel<OUT>, dim3(units * ksplit), dim3(T), smem, stream, c, n, r3, n_max, G, ksplit, cells_per,
+                     features, bs_f, ld_f, cnt, w.start, w.sorted, occ_list, n_occ, w.rec_flag, w.rec, w.rec_rows, out, amax);
   return true;
+}
+
+// shared launcher (also used by bdm_sparse_voxel_features_f32 in sparse_conv_h2.hip); w: the plan's workspace; false: shape not covered
+bool bdm_sparse_features_lds_launch(int out_kind, int b, int c, int n, int r3, int n_max, const float *features, long long bs_f,
+                                    int ld_f, const int *cnt, const bdm::VoxWs &w, const int *occ_list, const int *n_occ, void *out,
+                                    unsigned *amax, hipStream_t stream, int *rc) {
+  if (bdm_staging_choice() == 0 || n > 4096 || n_max > 4096) return false;  // BDM_STAGING=0 keeps the global-memory gather (common.h)
+  *rc = BDM_OK;
+  return out_kind == 0 ? sparse_features_lds_go<0>(b, c, n, r3, n_max, features, bs_f, ld_f, cnt, w, occ_list, n_occ, out, amax, stream)
+                       : sparse_features_lds_go<1>(b, c, n, r3, n_max, features, bs_f, ld_f, cnt, w, occ_list, n_occ, out, amax, stream);
 }
 
 extern "C" int bdm_sparse_voxel_features_s3(int b, int c, int n, int r, int n_max, const float *features, long long bs_f,
@@ -362,7 +384,7 @@ extern "C" int bdm_sparse_voxel_features_s3(int b, int c, int n, int r, int n_ma
   const int r3 = r * r * r;
   VoxWs w = vox_ws(const_cast<void *>(plan_workspace), b, n, r3);
   int rc_lds = BDM_OK;
-  if (bdm_sparse_features_lds_launch(0, b, c, n, r3, n_max, features, bs_f, ld_f, cnt, w.start, w.sorted, occ_list, n_occ, xs, nullptr,
+  if (bdm_sparse_features_lds_launch(0, b, c, n, r3, n_max, features, bs_f, ld_f, cnt, w, occ_list, n_occ, xs, nullptr,
                                      (hipStream_t)stream, &rc_lds))
     return launch_status("sparse_voxel_features_s3");
   const int G = (c + 7) / 8, units = b * G, kblocks = cdiv(n_max, 128);

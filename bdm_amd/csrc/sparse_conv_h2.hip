@@ -15,8 +15,8 @@ using namespace bdm;
 
 // LDS-cached feature gather shared with sparse_conv.hip (defined there)
 bool bdm_sparse_features_lds_launch(int out_kind, int b, int c, int n, int r3, int n_max, const float *features, long long bs_f,
-                                    int ld_f, const int *cnt, const int *start, const int *sorted, const int *occ_list,
-                                    const int *n_occ, void *out, unsigned *amax, hipStream_t stream, int *rc);
+                                    int ld_f, const int *cnt, const bdm::VoxWs &w, const int *occ_list, const int *n_occ, void *out,
+                                    unsigned *amax, hipStream_t stream, int *rc);
 
 // ---------------------------------------------------------------------------------------------------
 // occupied cells' mean features as fp32 records: xr (B, G, n_max) records of 8 channels (32 bytes), rows >= n_occ zero;
@@ -83,8 +83,8 @@ extern "C" int bdm_sparse_voxel_features_f32(int b, int c, int n, int r, int n_m
   const int r3 = r * r * r;
   VoxWs w = vox_ws(const_cast<void *>(plan_workspace), b, n, r3);
   int rc_lds = BDM_OK;
-  if (bdm_sparse_features_lds_launch(1, b, c, n, r3, n_max, features, bs_f, ld_f, cnt, w.start, w.sorted, occ_list, n_occ, xr,
-                                     (unsigned *)amax, (hipStream_t)stream, &rc_lds))
+  if (bdm_sparse_features_lds_launch(1, b, c, n, r3, n_max, features, bs_f, ld_f, cnt, w, occ_list, n_occ, xr, (unsigned *)amax,
+                                     (hipStream_t)stream, &rc_lds))
     return launch_status("sparse_voxel_features_f32");
   const int G = (c + 7) / 8, units = b * G, kblocks = cdiv(n_max, 128);
   hipLaunchKernelGGL(sparse_vox_features_f32_kernel, dim3(cdiv(units, 8) * 8 * kblocks), dim3(128), 0, (hipStream_t)stream, c,

@@ -73,6 +73,13 @@ int bdm_grouping_forward(int b, int c, int n, int m, int u, const float *feature
 int bdm_fp_assemble(int b, int m, int n, const int *indices, const float *weights, int c_a, const float *fa, long long bs_a,
                     int ld_a, int c_s, const float *fs, long long bs_s, int ld_s, int c_t, const float *ft, long long bs_t,
                     int ld_t, float *out0, long long bs_0, int ld_0, float *out1, long long bs_1, int ld_1, void *stream);
+/* The same with the kernel form chosen by the caller (equality tests): 0 = by sizes as bdm_fp_assemble (source rows staged in LDS per
+ * (shape, channel chunk) wherever a row of m floats fits 64 KB), 1 = the per-point kernel (three scattered loads per element), 2 = the
+ * staged kernel or BDM_ERR_ARG.  All forms evaluate the same expression per element: identical bits. */
+int bdm_fp_assemble_form(int form, int b, int m, int n, const int *indices, const float *weights, int c_a, const float *fa,
+                         long long bs_a, int ld_a, int c_s, const float *fs, long long bs_s, int ld_s, int c_t, const float *ft,
+                         long long bs_t, int ld_t, float *out0, long long bs_0, int ld_0, float *out1, long long bs_1, int ld_1,
+                         void *stream);
 int bdm_three_nn_interpolate_forward(int b, int c, int m, int n, const float *points,
                                      const float *centers, const float *features, float *out,
                                      int *indices, float *weights, void *stream);
@@ -341,7 +348,10 @@ int bdm_group_norm_stats(int b, int c, int l, int groups, const float *x, long l
                          int *slices_out, void *stream);
 /* avg_voxelize_forward writing S3 (features strided: bs_f, ld_f); same deterministic summation order. */
 int bdm_voxelize_plan(int b, int n, int r, const int *coords, int *ind, int *cnt, void *workspace, void *stream);
-/* the plan plus bdm_voxel_compact and bdm_voxel_row_occupancy of the same shape in ONE launch (same values) */
+/* the plan plus bdm_voxel_compact and bdm_voxel_row_occupancy of the same shape in ONE launch (same values).  It also leaves one
+ * 32-byte cell record {count, start, first six list entries} per occupied row in the workspace (layout: csrc/common.h, VoxWs), which
+ * bdm_sparse_voxel_features_s3 / _f32 read instead of walking occ_list -> cnt / start -> list; a workspace filled by
+ * bdm_voxelize_plan carries a cleared flag instead, and they walk the lists. */
 int bdm_voxelize_plan_full(int b, int n, int r, int n_max, const int *coords, int *ind, int *cnt, void *workspace,
                            int *occ_index, int *occ_list, int *n_occ, unsigned char *rowocc, void *stream);
 int bdm_avg_voxelize_s3(int b, int c, int n, int r, const float *features, long long bs_f, int ld_f,
