@@ -16,7 +16,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from . import _lib as L
-from . import ops
+from . import ops, replay
 from .cameras import PerspectiveCameras, Pointclouds, join_cameras
 from .feature_model import FeatureModel
 from .pvcnn import PVCNN2_PC2, PVCNN_fuse
@@ -328,11 +328,6 @@ class ConditionalPointCloudDiffusionModel(PointCloudProjectionModel):
         self.point_cloud_model = PointCloudModel(model_type=point_cloud_model, embed_dim=point_cloud_model_embed_dim,
                                                  in_channels=self.in_channels, out_channels=self.out_channels)
 
-    def _weights_signature(self):
-        """Changes whenever a denoiser parameter is rewritten or replaced: a recorded step (graph or tape) holds the addresses
-        of the weight packs derived from them, so it must not outlive the weights it was recorded with."""
-        return hash(tuple((p.data_ptr(), p._version) for p in self.point_cloud_model.parameters()))
-
     _step_kwargs = {}  # e.g. {"eta": 0.0} for DDIM (the reference forwards eta only to schedulers that accept it)
 
     def _denoise_loop(self, x_t, camera, image_rgb, mask, scheduler, timesteps, generator=None):
@@ -342,7 +337,7 @@ class ConditionalPointCloudDiffusionModel(PointCloudProjectionModel):
             return self._denoise_loop_graph(x_t, camera, image_rgb, mask, scheduler, timesteps, generator)
         # the tape holds the denoiser forward only; schedulers that keep earlier model outputs (PNDM) would see them overwritten
         if (long_enough and type(scheduler) in (DDPMScheduler, DDIMScheduler)
-                and (TAPE_STEPS == "1" or (TAPE_STEPS == "auto" and x_t.shape[0] * x_t.shape[1] <= TAPE_MAX_POINTS))):
+                and replay.wanted(TAPE_STEPS, x_t.shape[0] * x_t.shape[1], TAPE_MAX_POINTS)):
             return self._denoise_loop_tape(x_t, camera, image_rgb, mask, scheduler, timesteps, generator)
         B = x_t.shape[0]
         for t in timesteps:
@@ -360,8 +355,8 @@ class ConditionalPointCloudDiffusionModel(PointCloudProjectionModel):
     # to the eager loop (same kernels, same arguments, same RNG stream: the noise is drawn eagerly, in order).
     def _step_graph(self, x_t, camera, image_rgb, mask, scheduler):
         feat, _ = self.conditioning_image(image_rgb, mask)
-        key = (tuple(x_t.shape), str(x_t.device), id(camera), id(scheduler), scheduler.num_inference_steps, self._weights_signature(),
-               ops.saturation_epoch())
+        key = replay.step_key(self.point_cloud_model, x_t.shape, x_t.device, id(camera), id(scheduler), scheduler.num_inference_steps,
+                              stream=False)  # (the graph holds the scheduler step too; it replays on whichever stream is current)
         g = getattr(self, "_graph_cache", None)
         if g is not None and g["key"] == key and g["feat"] is feat and g["image"] is image_rgb:
             return g
@@ -396,7 +391,7 @@ class ConditionalPointCloudDiffusionModel(PointCloudProjectionModel):
         g["x"].copy_(x_t)
         probe = int(getattr(self, "eager_probe_every", 0))  # bench.py: every k-th step runs eagerly so that single
         for i, t in enumerate(timesteps):                     # kernels can be timed with HIP events inside the loop
-            if probe and i % probe == probe - 1:
+            if probe and i % probe == probe - 1:  # (unlike replay.run_step: counted per call, and profiling.PROBE_WEIGHT stays 1)
                 tt = torch.full((x_t.shape[0],), t, dtype=torch.int64, device=x_t.device)
                 x_in = self.get_input_with_conditioning(g["x"], camera=camera, image_rgb=image_rgb, mask=mask, t=tt, lazy=True)
                 g["x"].copy_(scheduler.step(self.point_cloud_model(x_in, tt), t, g["x"], generator=generator).prev_sample)
@@ -408,55 +403,23 @@ class ConditionalPointCloudDiffusionModel(PointCloudProjectionModel):
             g["graph"].replay()
         return g["x"].clone()
 
-    # ---- launch-tape form of the reverse loop (tape.py) --------------------------------------------------------
-    # The conditioning + denoiser forward on static buffers is RECORDED while it runs eagerly (second step of the loop: the
-    # first one leaves every lazy cache -- weight packs, workspaces, kernel attributes -- behind it) and later steps
-    # replay the flat list of C-ABI calls: ~11 us of host time per launch instead of 15-20.  The scheduler step stays
-    # eager, so DDPM and DDIM, generator / noise_source draws and the per-shape Philox streams all work unchanged.
-    # Default for every configuration up to B * N = TAPE_MAX_POINTS: recorded inside a private memory pool (tape.py) the replay
-    # costs the GPU what the eager step costs, and the host one library call per step.
+    # ---- launch-tape form of the reverse loop: the conditioning + denoiser forward is recorded once and replayed per step
+    # (mechanism, cache record and its key: replay.py); the scheduler step stays eager, so DDPM and DDIM, generator draws work unchanged
     def _denoise_loop_tape(self, x_t, camera, image_rgb, mask, scheduler, timesteps, generator=None):
-        from . import tape as T
         feat, _ = self.conditioning_image(image_rgb, mask)
-        dev, B = x_t.device, x_t.shape[0]
-        key = (tuple(x_t.shape), str(dev), id(camera), torch._C._cuda_getCurrentRawStream(torch._C._cuda_getDevice()),
-               self._weights_signature(), ops.saturation_epoch())
-        g = getattr(self, "_tape_cache", None)
-        if g is None or g["key"] != key or g["feat"] is not feat:  # (feat is a static buffer: conditioning_image)
-            g = {"key": key, "feat": feat, "image": image_rgb, "camera": camera, "tape": None, "warm": False, "off": None, "eps": None,
-                 "x": torch.empty_like(x_t, memory_format=torch.contiguous_format),
-                 "t": torch.zeros(B, dtype=torch.int64, device=dev)}
-            self._tape_cache = g
+        key = replay.step_key(self.point_cloud_model, x_t.shape, x_t.device, id(camera))
+        g = replay.step_record(self, key, x_t, valid=lambda r: r["feat"] is feat,  # (feat is a static buffer: conditioning_image)
+                               feat=feat, image=image_rgb, camera=camera)
 
         def denoise():  # conditioning + denoiser on the static buffers: everything between two scheduler steps
             x_in = self.get_input_with_conditioning(g["x"], camera=camera, image_rgb=image_rgb, mask=mask, t=g["t"], lazy=True)
             return self.point_cloud_model(x_in, g["t"])
 
         g["x"].copy_(x_t)
-        probe = int(getattr(self, "eager_probe_every", 0))  # bench.py: every k-th step runs eagerly, through the kernel-class
-        from . import profiling                               # profiler (HIP events around single launches inside the timed loop)
+        probe = int(getattr(self, "eager_probe_every", 0))  # bench.py: every k-th step runs eagerly, through the kernel-class profiler
         for t in timesteps:
             g["t"].fill_(t)
-            g["steps"] = i = g.get("steps", -1) + 1  # counted across calls: the samplers run the loop in segments of 32 ... 744 steps
-            if g["tape"] is not None and probe and i % probe == probe - 1:
-                profiling.PROBE_WEIGHT[0] = probe
-                try:
-                    eps = denoise()
-                finally:
-                    profiling.PROBE_WEIGHT[0] = 1
-            elif g["tape"] is not None:
-                g["tape"].replay()
-                eps = g["eps"]
-            elif g["warm"] and g["off"] is None:
-                with ops.static_step(), T.record() as tp:
-                    eps = denoise()
-                if tp.broken:
-                    g["off"] = tp.broken  # stay eager (on the static buffers) and say why: model._tape_cache["off"]
-                else:
-                    g["tape"], g["eps"] = tp, eps
-            else:
-                eps = denoise()
-                g["warm"] = True
+            eps = replay.run_step(g, denoise, probe)
             # the scheduler step stays eager (one launch): its scalars, its noise draw and the per-shape Philox streams change per step
             if type(scheduler) is DDPMScheduler and not self._step_kwargs:
                 scheduler.step(eps, t, g["x"], generator=generator, out=g["x"])   # in place: the step is elementwise (no copy launch)

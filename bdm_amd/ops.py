@@ -5,7 +5,10 @@ are contiguous (e.g. a channel slice of a concat buffer) is passed by (batch str
 row stride) without a copy.  Torch supplies memory and the current stream only.
 """
 import ctypes
+import math
 import os
+import warnings
+import weakref
 
 import torch
 
@@ -53,11 +56,15 @@ def _addend_strides(add):
 _ws_cache = {}
 
 
+def _stream_key(device):
+    """(device, its current raw stream): what per-stream caches are keyed by"""
+    dev = torch.device(device)
+    return str(device), torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch._C._cuda_getDevice())
+
+
 def workspace(nbytes, device, tag="ws"):
     """Cached scratch buffer per (tag, device, current stream): kernels of different streams never share one."""
-    dev = torch.device(device)
-    raw = torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch._C._cuda_getDevice()) if dev.type == "cuda" else 0
-    key = (tag, str(device), raw)
+    key = (tag,) + (_stream_key(device) if torch.device(device).type == "cuda" else (str(device), 0))
     buf = _ws_cache.get(key)
     if buf is None or buf.numel() < nbytes:
         buf = torch.empty(max(int(nbytes), 1 << 16), dtype=torch.uint8, device=device)
@@ -425,8 +432,7 @@ _counter_cache = {}
 
 def _zero_counters(n, device):
     """int32 counters that kernels find zero and leave zero (one buffer per device and stream)."""
-    dev = torch.device(device)
-    key = (str(device), torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch._C._cuda_getDevice()))
+    key = _stream_key(device)
     buf = _counter_cache.get(key)
     if buf is None or buf.numel() < n:
         buf = torch.zeros(max(n, 256), dtype=torch.int32, device=device)
@@ -458,7 +464,7 @@ def amax_slots(device, n):
         return torch.zeros(n, dtype=torch.float32, device=device)
     while True:
         first = _amax_slot(device)
-        ring = _amax_rings[(str(device), torch._C._cuda_getCurrentRawStream(first.device.index))]
+        ring = _amax_rings[_stream_key(device)]
         if ring[1] - 1 + n <= ring[0].shape[0]:
             start = ring[1] - 1
             ring[1] = start + n
@@ -523,7 +529,6 @@ def conv3d(x, packed_w, bias, r, rowocc=None):
 
 # ---- bf16x6 ("S3") convolution path: fp32 accuracy on the bf16 matrix cores (csrc/conv3d_s3.hip) -------------------
 def conv3d_s3_pack(weight):
-    import ctypes
     cout, cin = weight.shape[:2]
     w = weight.contiguous()
     packed = torch.empty(L.lib().bdm_conv3d_s3_weight_elems(cout, cin), dtype=torch.bfloat16, device=w.device)
@@ -584,7 +589,6 @@ def conv3d_h2_pack(weight):
 
 
 def _pow2_below(v):
-    import math
     return 2.0 ** math.floor(math.log2(v))
 
 
@@ -613,7 +617,6 @@ def saturation_epoch():
 
 def saturation_slot(owner, device):
     """One sticky device word per fp16x3 layer (`owner` = its PVConv): set by to_h2 when a value left fp16's range."""
-    import weakref
     key = str(device)
     reg = _sat_registry.get(key)
     if reg is None:
@@ -640,7 +643,6 @@ def poll_h2_saturation():
     """Host check of the saturation words (ONE small device->host copy; the samplers call it once per trajectory, never per
     step).  Every flagged layer is switched to the bf16x6 kernels (exact split, no range limit) for all later calls and a
     warning names it: the trajectory that just finished used clamped activations in that layer."""
-    import warnings
     global _sat_epoch
     hit = []
     for key, (flags, owners) in _sat_registry.items():
@@ -934,8 +936,7 @@ class static_step:
 def _amax_slot(device):
     """One zeroed float per sparse convolution call (its activation-scale maximum): slots of a per-(device, stream) ring that
     is refilled with zeros in ONE launch every 256 calls, so the convolution itself needs no memset."""
-    dev = torch.device(device)
-    key = (str(device), torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch._C._cuda_getDevice()))
+    key = _stream_key(device)
     ring = _amax_rings.get(key)
     if ring is None or ring[1] >= ring[0].shape[0] or ring[2] != _static_epoch:
         # a NEW buffer (not an in-place refill): slots handed out earlier may still be read by enqueued kernels

@@ -196,7 +196,7 @@ SPEC = {
 }
 
 
-PROBE_WEIGHT = [1]  # launches one profiled launch stands for (the tape loop profiles every k-th step only: model._denoise_loop_tape)
+PROBE_WEIGHT = [1]  # launches one profiled launch stands for (the tape loops profile every k-th step only: replay.run_step)
 
 
 def _plain(v):

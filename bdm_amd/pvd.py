@@ -8,11 +8,13 @@ any DataParallel scatter/gather -- one process drives one GPU.
 """
 import numpy as np
 import os
+import warnings
 
 import torch
 import torch.nn as nn
 
 from . import _lib as L
+from . import replay
 from .pvcnn import PVCNN2_PVD
 
 
@@ -167,60 +169,30 @@ class Model(nn.Module):
         assert out.shape == torch.Size([B, D, N])
         return out
 
-    # ---- launch-tape form of the sampling loop (tape.py; the PC^2 loop's form: model._denoise_loop_tape) ----------------------
-    # The denoiser forward on static buffers is recorded while it runs eagerly (second step: the first leaves every lazy cache behind it)
-    # and later steps -- of this call, of later prior segments, of later trajectories -- replay the flat list of C-ABI calls; the
-    # p_sample arithmetic stays eager (one launch, in place): its scalars and its noise draw change per step.  The BDM recipes run the
-    # prior in segments of `roll_step` (16) steps, 80 per shape: eager, those steps are host-bound at B = 16 (~190 launches each).
+    # ---- launch-tape form of the sampling loop: the denoiser forward is recorded once and replayed per step (replay.py).  The BDM recipes
+    # run the prior in segments of `roll_step` (16) steps, 80 per shape: eager, those steps are host-bound at B = 16 (~190 launches each).
     tape_steps = os.environ.get("BDM_TAPE", "auto")
     tape_max_points = 1 << 20
     tape_min_steps = 4
     tape_pvd = os.environ.get("BDM_PVD_TAPE", "1") == "1"   # (A/B switch: 0 keeps the prior's loop eager while the PC^2 loop replays)
 
-    def _weights_signature(self):
-        return hash(tuple((p.data_ptr(), p._version) for p in self.model.parameters()))
-
     def _tape_ok(self, data, constrain_fn, clip_denoised, keep_running, n_steps):
         return (data.is_cuda and not clip_denoised and not keep_running and n_steps >= self.tape_min_steps
                 and self.tape_pvd and constrain_fn is _no_constraint and data.dim() == 3 and data.dtype == torch.float32
-                and (self.tape_steps == "1" or (self.tape_steps == "auto" and data.shape[0] * data.shape[2] <= self.tape_max_points)))
+                and replay.wanted(self.tape_steps, data.shape[0] * data.shape[2], self.tape_max_points))
 
     def _gen_samples_tape(self, data, noise_fn, start_time, final_time):
-        from . import ops, profiling, tape as T
-        dev, B = data.device, data.shape[0]
-        key = (tuple(data.shape), str(dev), torch._C._cuda_getCurrentRawStream(torch._C._cuda_getDevice()), self._weights_signature(),
-               ops.saturation_epoch())
-        g = getattr(self, "_tape_cache", None)
-        if g is None or g["key"] != key:
-            g = {"key": key, "tape": None, "warm": False, "off": None, "eps": None,
-                 "x": torch.empty_like(data, memory_format=torch.contiguous_format),
-                 "t": torch.zeros(B, dtype=torch.int64, device=dev)}
-            self._tape_cache = g
+        g = replay.step_record(self, replay.step_key(self.model, data.shape, data.device), data)
+
+        def denoise():
+            return self._denoise(g["x"], g["t"])
+
         g["x"].copy_(data)
         probe = int(getattr(self, "eager_probe_every", 0))  # bench.py: every k-th step runs eagerly through the kernel-class profiler
         for t in reversed(range(final_time, start_time)):
             g["t"].fill_(t)
-            g["steps"] = i = g.get("steps", -1) + 1
-            if g["tape"] is not None and probe and i % probe == probe - 1:
-                profiling.PROBE_WEIGHT[0] = probe
-                try:
-                    eps = self._denoise(g["x"], g["t"])
-                finally:
-                    profiling.PROBE_WEIGHT[0] = 1
-            elif g["tape"] is not None:
-                g["tape"].replay()
-                eps = g["eps"]
-            elif g["warm"] and g["off"] is None:
-                with ops.static_step(), T.record() as tp:
-                    eps = self._denoise(g["x"], g["t"])
-                if tp.broken:
-                    g["off"] = tp.broken   # stay eager (on the static buffers) and say why: Model._tape_cache["off"]
-                else:
-                    g["tape"], g["eps"] = tp, eps
-            else:
-                eps = self._denoise(g["x"], g["t"])
-                g["warm"] = True
-            self.diffusion.p_step(g["x"], eps, t, noise_fn=noise_fn, out=g["x"])   # in place: elementwise
+            eps = replay.run_step(g, denoise, probe)
+            self.diffusion.p_step(g["x"], eps, t, noise_fn=noise_fn, out=g["x"])   # eager, in place: elementwise
         return g["x"].clone()
 
     def gen_samples(self, data, shape, device, noise_fn=torch.randn, constrain_fn=None, clip_denoised=False,
@@ -269,7 +241,6 @@ def prepare_pvd_model(opt, device):
         else:
             raise KeyError(f"{ckpt}: neither 'model_state' nor 'prior_model' in the checkpoint (keys: {list(resumed)[:8]})")
     else:
-        import warnings
         from .utils.procedural import fill_module_
         seed = int(str(ckpt).split(":")[1]) if ckpt and ":" in str(ckpt) else 0
         if not ckpt:

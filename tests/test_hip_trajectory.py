@@ -158,6 +158,46 @@ def test_launch_tape_replay_equals_eager_loop(hip, monkeypatch):
     assert torch.equal(changed_tape, changed_eager) and not torch.equal(changed_tape, eager)
 
 
+def test_launch_tape_counts_steps_and_is_reused_across_segments(hip, monkeypatch):
+    """Two interaction_sample segments of one trajectory on the launch tape (the samplers run the PC^2 loop in segments): the record's
+    step counter runs on across them (replay.run_step), the second segment replays the first's recording, and the result has the
+    bits of the same two segments run eagerly."""
+    import bdm_amd.model as M
+    from bdm_amd.config import ProjectConfig
+    from bdm_amd.data import SyntheticShapes
+    from bdm_amd.utils.procedural import fill_module_
+    B, N, steps = 2, 1024, 12
+    cfg = ProjectConfig()
+    cfg.dataset.max_points = N
+    model = fill_module_(M.get_model(cfg).eval(), seed=3).cuda()
+    batch = next(iter(SyntheticShapes(range(B), B, num_points=N))).to("cuda")
+    x0 = torch.randn(B, N, 3, generator=torch.Generator().manual_seed(5)).cuda()
+    noise = [torch.randn(B, N, 3, generator=torch.Generator().manual_seed(100 + i)).cuda() for i in range(2 * steps)]
+
+    def run(mode):
+        monkeypatch.setattr(M, "TAPE_STEPS", mode)
+        it = iter(noise)
+        model.scheduler.noise_source = lambda shape, device: next(it)
+        tapes = []
+        try:
+            x = x0.clone()
+            for start in (500, 500 - steps):
+                x = model.interaction_sample(x, batch.camera, batch.image_rgb, None, start_time=start, end_time=start - steps)
+                tapes.append((getattr(model, "_tape_cache", None) or {}).get("tape"))
+            return x.cpu(), tapes
+        finally:
+            model.scheduler.noise_source = None
+
+    eager, tapes = run("0")
+    assert tapes == [None, None]
+    taped, tapes = run("1")
+    g = model._tape_cache
+    assert g["off"] is None, g["off"]
+    assert g["steps"] == 2 * steps - 1
+    assert tapes[0] is not None and tapes[1] is tapes[0] and g["tape"] is tapes[0]
+    assert torch.equal(eager, taped)
+
+
 def test_prior_loop_replayed_from_a_tape_equals_the_eager_loop(hip, monkeypatch):
     """pvd.Model.gen_samples in launch-tape form (the prior's 16-step segments of the BDM recipes, pvd/__init__.py:226-270 through
     generate_pvd_xyz :450-473): the bits of the eager loop, with the reference's global-generator noise and with the per-shape Philox
