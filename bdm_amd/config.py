@@ -34,7 +34,8 @@ class RunConfig:  # structured.py:14-56
     render_sample_dir: Optional[str] = None
     render_num_frames: int = 1
     # "normals": the uncoloured kinds (gt, pred, the orbit of an uncoloured prediction) are shaded by their estimated normals
-    # (bdm_amd.normals, neighbourhoods of render_normals_k points) instead of rendering as black silhouettes; "none" = as before
+    # (bdm_amd.normals, neighbourhoods of render_normals_k points) instead of rendering as black silhouettes; "oriented": the same
+    # with normals oriented by visibility voting and one-sided shading; "none" = as before
     render_shading: str = "none"
     render_normals_k: int = 50
     save_dir: Optional[str] = None

@@ -79,10 +79,12 @@ def render_pointcloud_batch_pytorch3d(cameras, pointclouds, image_size=224, radi
                    background_color, compositor, fragments=False)[1]
 
 
-def shade_by_normals(points, normals, cameras, ambient=0.3, albedo=(0.8, 0.8, 0.8)):
+def shade_by_normals(points, normals, cameras, ambient=0.3, albedo=(0.8, 0.8, 0.8), two_sided=True):
     """Features (B, N, 3) that light an uncoloured cloud from its cameras: albedo * (ambient + (1 - ambient) |n . v|), v the unit
     vector from the point to the camera centre (perspective) or the view axis (orthographic).  Two-sided, so the picture does
-    not depend on the sign rule of the normals.  Elementwise torch on whatever device the points live on: not a hot path."""
+    not depend on the sign rule of the normals; two_sided=False is one-sided Lambert, max(n . v, 0) in place of |n . v|, for
+    normals whose signs can be trusted (normals.orient_normals_by_visibility): a surface seen from behind gets the ambient term
+    alone.  Elementwise torch on whatever device the points live on: not a hot path."""
     cameras = join_cameras(cameras)
     if len(cameras) != points.shape[0]:
         raise ValueError(f"{len(cameras)} cameras for {points.shape[0]} clouds")
@@ -93,7 +95,8 @@ def shade_by_normals(points, normals, cameras, ambient=0.3, albedo=(0.8, 0.8, 0.
         centre = -torch.bmm(T[:, None, :], R.transpose(1, 2))        # X_view = 0  <=>  X_world = -T R^T
         v = centre - points
         v = v / v.norm(dim=-1, keepdim=True).clamp_min(1e-12)
-    lambert = (normals.to(points) * v).sum(-1, keepdim=True).abs()
+    lambert = (normals.to(points) * v).sum(-1, keepdim=True)
+    lambert = lambert.abs() if two_sided else lambert.clamp_min(0.0)
     return torch.as_tensor(albedo, dtype=points.dtype, device=points.device) * (ambient + (1.0 - ambient) * lambert)
 
 

@@ -925,6 +925,47 @@ size_t bdm_estimate_normals_workspace_bytes(int b, int n, int k);
 int bdm_estimate_normals(int b, int n, int k, int orient, const float *points, const float *viewpoints, int *knn_idx,
                          float *normals, float *curvatures, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * 11. Consistent orientation of point-cloud normals by visibility voting (csrc/orient.hip).  The cloud is looked at from v
+ *     directions; a point that survives a splatted z-buffer test in a view votes for the side of its normal that faces that
+ *     viewer; points no view decided take the sign their decided neighbours give them.  DESIGN.md section 15.
+ * ---------------------------------------------------------------------------------- */
+/* points, normals_in, normals_out (b, n, 3) point-major; knn_idx (b, n, k) as bdm_estimate_normals writes it; views (v, 3, 3).
+ * All arithmetic is float32, every operation rounded on its own (no FMA contraction), division and sqrt correctly rounded;
+ * everything after the projection is integer.  dot(p, p') = fl(fl(fl(x x') + fl(y y')) + fl(z z')).
+ * Per cloud: only the points whose three coordinates are finite take part ("finite points").  c = the centre of their bounding
+ *   box, fl(0.5 * fl(min + max)) per axis (min and max are exact: no summation order enters).  q_i = fl(p_i - c) per axis.
+ *   rho = the largest d2(q_i) = fl(fl(fl(qx*qx) + fl(qy*qy)) + fl(qz*qz)) (section 10's form).  h = fl(1.02f * sqrt(rho)).
+ *   A cloud with no finite point, or with rho == 0, has no visible point in any view: votes and seen are zero.
+ * Per view: three rows u, w, d; d points from the cloud to the viewer (orthographic).  No trigonometry, no normalisation: the
+ *   rows are taken as passed.  a = dot(q, u), b = dot(q, w), t = dot(q, d).
+ *   Pixel X = clamp(floor(fl(fl(fl(a / h) + 1) * (r / 2))), 0, r - 1) with r / 2 = fl(0.5 * r) (exact), Y the same from b.
+ *   Depth key Z = clamp(floor(fl(fl(1 - fl(t / h)) * 32768)), 0, 65535): smaller is nearer the viewer.  A NaN clamps to 0.
+ * Z-buffer: zb[x, y] = the minimum Z_i over the finite points with |x - X_i| <= splat and |y - Y_i| <= splat, inside the image.
+ *   Point i is visible in view v if and only if it is finite and Z_i <= zb[X_i, Y_i] + eps.
+ * Votes: sigma(i, v) = +1 if dot(n_i, d_v) > 0, -1 if it is < 0, 0 if it is zero or NaN.  votes_i = sum_v visible(i, v) sigma(i, v),
+ *   seen_i = sum_v visible(i, v), both int32 (b, n): integer sums, the same bits in any order.  s_i = sgn(votes_i).
+ * Fallback: at most `rounds` Jacobi rounds; every round reads the state s as it stood when the round began.  For every i with
+ *   s_i == 0: the window of i is the first kg entries j of knn_idx[i] (in row order, all k entries are looked at) that have 0 <= j < n
+ *   and j != i; t_i = sum over the window of s_j * sgn(dot(n_i, n_j)) (an undecided j, s_j == 0, adds nothing; sgn of NaN is 0);
+ *   s_i <- sgn(t_i).  Points with s_i != 0 keep it.  The rounds stop early when one changes nothing.
+ * Output: normals_out_i = the bits of n_i, with the sign bit of all three components flipped when s_i < 0 (so NaN stays NaN).
+ *   A point still undecided (s_i == 0: it keeps its input sign) is counted in undecided (b); non-finite points are among them.
+ *   Wherever s_i != 0 the output does not depend on the signs of the input normals.
+ * votes, seen, undecided may be NULL.  normals_out must not alias normals_in.
+ * Limits: b >= 0 (b == 0 launches nothing and returns 0), 1 <= n <= 32768 (the state s of a cloud lives twice in one workgroup's
+ *   LDS), 1 <= k, b n k < 2^31, 1 <= v <= 256, b v < 2^31, 1 <= r <= 128 (the r x r z-buffer lives in one workgroup's LDS: 64 KiB at 128),
+ *   0 <= splat <= 4, 0 <= eps <= 65535, 1 <= kg <= k, 0 <= rounds <= 32, no NULL among the inputs, normals_out and the
+ *   workspace.  Outside these the call returns 1 and launches nothing.
+ * Determinism: integer atomics in LDS only (minimum, sum), no floating-point atomics, no workgroup waits on another; cloud j of
+ *   a batch has the same bits as the same cloud run alone, and so does a repeated call.
+ * workspace: bdm_orient_normals_workspace_bytes(b, n, v) bytes (one byte per cloud, view and point: the vote of that pair),
+ *   contents irrelevant before and after; 0 for sizes outside the limits. */
+size_t bdm_orient_normals_workspace_bytes(int b, int n, int v);
+int bdm_orient_normals(int b, int n, int k, int v, int r, int splat, int eps, int kg, int rounds, const float *points,
+                       const float *normals_in, const int *knn_idx, const float *views, float *normals_out, int *votes,
+                       int *seen, int *undecided, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

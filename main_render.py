@@ -8,6 +8,7 @@ ${run.render_sample_dir}/renders/{gt,pred,colored}/<category>/<stem>.png.  With 
 orbiting orthographic view of every predicted cloud (the coloured one where it exists) as renders/orbit/<category>/<stem>-<f>.png.
 With run.render_shading=normals the uncoloured kinds (gt, pred, the orbit of an uncoloured prediction) are lit by their estimated
 normals (bdm_amd.normals, run.render_normals_k neighbours) instead of rendering as black silhouettes; `colored` is untouched.
+run.render_shading=oriented does the same with normals oriented by visibility voting and one-sided shading.
 
     python main_blending.py run.job=sample_bdm_blending dataset=synthetic run.num_samples=1 dataset.max_points=1024
     python main_render.py dataset=synthetic run.render_sample_dir=<the directory the first command printed>
@@ -20,7 +21,7 @@ import torch
 from main_blending import get_dataloader
 
 KINDS = ("gt", "pred", "colored")
-SHADINGS = ("none", "normals")
+SHADINGS = ("none", "normals", "oriented")
 
 
 def parse_args(argv):
@@ -48,15 +49,15 @@ def render_tree(cfg, batches, render_fn, orbit_fn=None, device="cpu", shade_fn=N
     the paths written.  render_fn(cameras (list of single cameras), points (B, n, 3), colours (B, n, 3) or None) -> images
     (B, H, W, 3) in [0, 1]: one call per batch, kind and distinct point count.  orbit_fn(points (1, n, 3), colours or None,
     path of <stem>.png, num_frames) -> the paths it wrote: called per predicted cloud when run.render_num_frames > 1.
-    shade_fn(cameras, points (B, n, 3)) -> colours (B, n, 3): with run.render_shading=normals the uncoloured kinds get their
-    colours from it, once per batch group (a config without the key, or "none", leaves them None as before)."""
+    shade_fn(cameras, points (B, n, 3)) -> colours (B, n, 3): with run.render_shading=normals or oriented the uncoloured kinds get
+    their colours from it, once per batch group (a config without the key, or "none", leaves them None as before)."""
     from bdm_amd.io import load_pointcloud_ply, save_image_png
     root, written = Path(cfg.run.render_sample_dir), []
     shading = getattr(cfg.run, "render_shading", "none")
     if shading not in SHADINGS:
         raise ValueError(f"run.render_shading={shading!r}: expected one of {SHADINGS}")
-    if shading == "normals" and shade_fn is None:
-        raise ValueError("run.render_shading=normals needs a shade_fn")
+    if shading != "none" and shade_fn is None:
+        raise ValueError(f"run.render_shading={shading} needs a shade_fn")
     for batch_idx, batch in enumerate(batches):
         if cfg.run.num_sample_batches is not None and batch_idx >= cfg.run.num_sample_batches:
             break
@@ -79,7 +80,7 @@ def render_tree(cfg, batches, render_fn, orbit_fn=None, device="cpu", shade_fn=N
             points = torch.stack([it[2] for it in items]).to(device)
             colors = torch.stack([it[3] for it in items]).to(device) if kind == "colored" else None
             cams = [cameras[it[0]] for it in items]
-            if colors is None and shading == "normals":
+            if colors is None and shading != "none":
                 colors = shade_fn(cams, points)
             images = render_fn(cams, points, colors)
             for (i, path, _, _), image in zip(items, images):
@@ -111,13 +112,18 @@ def main(argv=None):
         with gpu_turn(device):
             return render_pointcloud_batch_pytorch3d(cameras, Pointclouds(points, colors)).cpu()
 
-    def shade_fn(cameras, points):
+    oriented = cfg.run.render_shading == "oriented"   # visibility-oriented normals, lit one-sided
+
+    def normals_of(points):
         from bdm_amd.normals import estimate_pointcloud_normals
+        return estimate_pointcloud_normals(points, cfg.run.render_normals_k, "visibility" if oriented else True)
+
+    def shade_fn(cameras, points):
         with gpu_turn(device):
-            return shade_by_normals(points, estimate_pointcloud_normals(points, cfg.run.render_normals_k), cameras)
+            return shade_by_normals(points, normals_of(points), cameras, two_sided=not oriented)
 
     def orbit_fn(points, colors, path, num_frames):
-        if colors is None and cfg.run.render_shading == "normals":
+        if colors is None and cfg.run.render_shading != "none":
             return shaded_orbit(points, path, num_frames)
         with gpu_turn(device):
             visualize_pointcloud_batch_pytorch3d(Pointclouds(points, colors), output_file_image=str(path), num_frames=num_frames,
@@ -127,14 +133,13 @@ def main(argv=None):
     def shaded_orbit(points, path, num_frames):
         """The orbit of visualize_pointcloud_batch_pytorch3d (same cameras, same file names), every frame lit from its camera."""
         from bdm_amd.cameras import OrthographicCameras, look_at_view_transform
-        from bdm_amd.normals import estimate_pointcloud_normals
         out = [path.with_name(f"{path.stem}-{f}.png") for f in range(num_frames)]
         with gpu_turn(device):
-            normals = estimate_pointcloud_normals(points, cfg.run.render_normals_k)
+            normals = normals_of(points)
             R, T = look_at_view_transform(dist=10.0, elev=30, azim=list(range(0, 360, 360 // num_frames)), degrees=True, device=device)
             for f in range(num_frames):
                 cam = OrthographicCameras(focal_length=0.25 * cfg.model.scale_factor, device=device, R=R[f:f + 1], T=T[f:f + 1])
-                visualize_pointcloud_batch_pytorch3d(Pointclouds(points, shade_by_normals(points, normals, cam)),
+                visualize_pointcloud_batch_pytorch3d(Pointclouds(points, shade_by_normals(points, normals, cam, two_sided=not oriented)),
                                                      output_file_image=str(out[f]), cameras=cam)
         return out
 
