@@ -75,6 +75,57 @@ def _ply_colors(props, column):
     return np.stack(cols, axis=1)
 
 
+def _ply_vertex_props(head):
+    """The property lines of the vertex element (a mesh file has a face element with a list property behind it)."""
+    props, element = [], None
+    for l in head:
+        if l.startswith("element"):
+            element = l.split()[1]
+        elif l.startswith("property") and element == "vertex":
+            props.append(l.split())
+    return props
+
+
+def save_mesh_ply(verts, faces, path):
+    """Binary little-endian PLY of a triangle mesh: float32 x, y, z per vertex, then per face a uchar count (3) and three int32
+    vertex indices (`property list uchar int vertex_indices`: what MeshLab, Open3D and pytorch3d read)."""
+    v = np.ascontiguousarray(np.asarray(verts, dtype="<f4").reshape(-1, 3))
+    f = np.asarray(faces).reshape(-1, 3)
+    if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+        raise ValueError(f"face indices outside 0..{v.shape[0] - 1}")
+    rec = np.empty(f.shape[0], dtype=[("count", "u1"), ("idx", "<i4", 3)])
+    rec["count"], rec["idx"] = 3, f
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    header = (f"ply\nformat binary_little_endian 1.0\nelement vertex {v.shape[0]}\nproperty float x\nproperty float y\n"
+              f"property float z\nelement face {f.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n")
+    with open(path, "wb") as out:
+        out.write(header.encode("ascii"))
+        out.write(v.tobytes())
+        out.write(rec.tobytes())
+
+
+def load_mesh_ply(path):
+    """(verts (V, 3) float32, faces (F, 3) int64) from a binary little-endian PLY in save_mesh_ply's form: a vertex element that
+    holds float x, y, z only, then triangles as `property list uchar int vertex_indices`."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    end = raw.index(b"end_header\n") + len(b"end_header\n")
+    head = raw[:end].decode("ascii").split("\n")
+    if [l for l in head if l.startswith("format")][0].split()[1] != "binary_little_endian":
+        raise ValueError(f"{path}: only binary little-endian mesh files are read")
+    if [p[1:] for p in _ply_vertex_props(head)] not in ([["float", c] for c in "xyz"], [["float32", c] for c in "xyz"]):
+        raise ValueError(f"{path}: the vertex element must hold float x, y, z only")
+    faces_line = [l for l in head if l.startswith("element face")]
+    if not faces_line or not any(l.split()[:4] in (["property", "list", "uchar", "int"], ["property", "list", "uint8", "int32"]) for l in head):
+        raise ValueError(f"{path}: no face element with a `list uchar int` property")
+    nv, nf = int([l for l in head if l.startswith("element vertex")][0].split()[-1]), int(faces_line[0].split()[-1])
+    verts = np.frombuffer(raw, dtype="<f4", count=3 * nv, offset=end).reshape(nv, 3).astype(np.float32)
+    rec = np.frombuffer(raw, dtype=[("count", "u1"), ("idx", "<i4", 3)], count=nf, offset=end + 12 * nv)
+    if nf and not (rec["count"] == 3).all():
+        raise ValueError(f"{path}: only triangles are read")
+    return verts, rec["idx"].astype(np.int64)
+
+
 def load_pointcloud_ply(path, with_colors=False, with_normals=False):
     """(n, 3) float32 from an ASCII or binary-little-endian PLY whose vertex element starts with float x, y, z.
     with_colors=True: (points, colors), colors (n, 3) float32 in [0, 1] from its red / green / blue properties.
@@ -89,7 +140,7 @@ def load_pointcloud_ply(path, with_colors=False, with_normals=False):
     head = raw[:end].decode("ascii").split("\n")
     n = int([l for l in head if l.startswith("element vertex")][0].split()[-1])
     fmt = [l for l in head if l.startswith("format")][0].split()[1]
-    props = [l.split() for l in head if l.startswith("property")]
+    props = _ply_vertex_props(head)
     if fmt == "ascii":
         rows = raw[end:].decode("ascii").split("\n")[:n]
         pts = np.array([[float(v) for v in r.split()[:3]] for r in rows], dtype=np.float32).reshape(-1, 3)

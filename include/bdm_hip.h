@@ -966,6 +966,63 @@ int bdm_orient_normals(int b, int n, int k, int v, int r, int splat, int eps, in
                        const float *normals_in, const int *knn_idx, const float *views, float *normals_out, int *votes,
                        int *seen, int *undecided, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * 12. Triangle meshes from oriented clouds (csrc/surface.hip): the cloud is accumulated into a signed-distance grid (implicit
+ *     moving least squares with a compact polynomial weight, in fixed point) and the grid is meshed by surface nets: one vertex
+ *     per sign-change cell, one quad per sign-change edge.  DESIGN.md section 16.
+ * ---------------------------------------------------------------------------------- */
+/* points, normals (b, n, 3) point-major, the normals taken to point outwards; r grid nodes per axis, node (i, j, k) of a cloud at
+ * (i r + j) r + k; s the support in voxels; min_weight.  All float32 arithmetic is rounded operation by operation (no FMA
+ * contraction), in the order written, division correctly rounded; fl() is left out below.  Everything after step 3 is integer
+ * except the vertex positions.
+ * 1. Valid points: a point is valid when its three coordinates and the three components of its normal are all finite; the others
+ *    contribute nothing.  counts[3] = the number of valid points.  A cloud with no valid point, or whose valid points have
+ *    min == max on every axis, is empty: SW = SU = 0 everywhere, V = F = skipped = 0.
+ * 2. Grid coordinates: lo, hi = the per-axis minima and maxima of the valid points (exact).  c = 0.5 * (lo + hi) per axis,
+ *    half = the largest 0.5 * (hi - lo) over the axes, inv = float(r - 1 - 2 (s + 1)) / (2 * half),
+ *    q = (p - c) * inv + float(r - 1) / 2 per axis (float(r - 1) / 2 is exact).
+ *    A valid point with a component of q outside [0, r - 1] (NaN included: an overflow on the way) contributes nothing.
+ * 3. Contributions: base = floor(q) per axis.  For every node g = base + o, o in {-s + 1, ..., s}^3, inside the grid (a node with
+ *    a coordinate outside 0 .. r - 1 is left out): d = float(g) - q per axis; d2 = (dx*dx + dy*dy) + dz*dz;
+ *    t = float(s*s) - d2; no contribution if t <= 0; w = t / float(s*s); w3 = (w*w)*w; a = (nx*dx + ny*dy) + nz*dz; u = w3 * a;
+ *    W = rint(w3 * 4096); U = rint(u * 4096) clamped to [-4096 s, 4096 s], rint rounding half to even; U = 0 if u * 4096 is NaN.
+ * 4. Grid: SW(g) = sum W and SU(g) = sum U over the contributions, exact int32 sums (n <= 65536 and s <= 4 keep |SU| <= 2^30):
+ *    integer sums have the same bits in any order.  thr = max(1, rint(min_weight * 4096)) (the product in float32).
+ *    A node is defined iff SW >= thr, negative (inside) iff SU < 0; f(g) = float(SU) / float(SW), the conversions rounding to nearest even.
+ * 5. Vertices: cell (i, j, k), 0 <= i, j, k < r - 1, with corners (i + dx, j + dy, k + dz), is active iff its 8 corners are all
+ *    defined and 1 to 7 of them are negative.  Its 12 edges are taken in the order: corner a = (dx, dy, dz) in lexicographic
+ *    order, then axis 0, 1, 2 with a[axis] == 0; the edge runs from a to b = a + e_axis.  An edge whose ends differ in sign gives
+ *    tt = f(a) / (f(a) - f(b)) (the denominator is never 0: one end is < 0, the other >= 0) and the point float(a) with tt as its
+ *    component along the axis.  The points are summed per component in that order, starting from the first, and divided by
+ *    float(their count); grid = float(cell index) + that mean per axis; world = (grid - float(r - 1) / 2) / inv + c per axis.
+ *    Vertex ids: the rank of the cell among the cloud's active cells in ascending (i (r - 1) + j)(r - 1) + k.
+ * 6. Faces: for axis = 0, 1, 2 (outer), then for every node g with g[axis] <= r - 2 in ascending (i r + j) r + k, the edge from g
+ *    to g + e_axis.  With u = (axis + 1) mod 3, v = (axis + 2) mod 3: the edge is a candidate when g[u] and g[v] lie in 1 .. r - 2,
+ *    both ends are defined and the ends differ in sign.  The four cells around it, all with g's coordinate along the axis:
+ *    c00 at (g[u] - 1, g[v] - 1), c10 at (g[u], g[v] - 1), c11 at (g[u], g[v]), c01 at (g[u] - 1, g[v]) in (u, v).
+ *    A candidate with all four cells active emits the quad (c00, c10, c11, c01) when g is the negative end and
+ *    (c01, c11, c10, c00) when g is the non-negative end (triangle normals point to the non-negative side: outward normals give a
+ *    positive signed volume); the quad (q0, q1, q2, q3) gives the triangles (q0, q1, q2) then (q0, q2, q3) of vertex ids.
+ *    A candidate with a non-active cell around it emits nothing and adds 1 to skipped.
+ *    Faces are ordered by axis, then edge, then triangle.
+ * bdm_surface_grid runs steps 1 - 4 and marks and counts the cells and edges of steps 5 and 6.  counts (b, 4) int32 =
+ *   {V, F, skipped, valid points} per cloud.  The workspace then holds, from its start, SW (b, r, r, r) int32, SU (b, r, r, r) int32
+ *   and the cell-to-vertex map (b, r, r, r) int32 (vertex id of the cell whose lowest corner is the node, -1 elsewhere), followed
+ *   by what bdm_surface_extract needs; it has to stay untouched between the two calls.
+ * bdm_surface_extract, with the same b, n, r, s and workspace: writes cloud c's vertices to verts + 3 vert_offsets[c] (V rows of 3
+ *   floats) and its faces to faces + 3 face_offsets[c] (F rows of 3 int32 vertex ids local to the cloud); the offsets are b
+ *   non-negative 64-bit integers on the device, counted in rows; nothing else is written.
+ * Limits: b >= 0 (b == 0 launches nothing and returns 0), 1 <= n <= 65536, 16 <= r <= 256, 2 <= s <= 4, 0 <= min_weight <= 1 (a NaN is refused), b r^3 < 2^31, no NULL
+ *   pointer, no output or the workspace equal to an input.  Outside these a call returns 1 and launches nothing.
+ * Determinism: integer atomic sums in global memory only, no floating-point atomics, no workgroup waits on another, every loop
+ *   is bounded by a launch argument; cloud j of a batch has the same bits as the same cloud run alone, and so does a repeated call.
+ * workspace: bdm_surface_workspace_bytes(b, n, r, s) bytes (0 for sizes outside the limits), contents irrelevant before. */
+size_t bdm_surface_workspace_bytes(int b, int n, int r, int s);
+int bdm_surface_grid(int b, int n, int r, int s, float min_weight, const float *points, const float *normals, int *counts,
+                     void *workspace, void *stream);
+int bdm_surface_extract(int b, int n, int r, int s, const long long *vert_offsets, const long long *face_offsets, float *verts,
+                        int *faces, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
