@@ -114,6 +114,74 @@ class Pointclouds:
         return list(self._points)
 
 
+class Meshes:
+    """pytorch3d's Meshes, the list form only (restated; unpinned: pytorch3d is absent): verts a list of (V_i, 3) float tensors,
+    faces a list of (F_i, 3) integer tensors of vertex indices within their own mesh -- what surface.reconstruct_surface returns.
+    A mesh without vertices or without faces is legal.  Only what the mesh renderer (bdm_amd/render.py) reads is kept."""
+
+    def __init__(self, verts, faces):
+        if not isinstance(verts, (list, tuple)) or not isinstance(faces, (list, tuple)):
+            raise ValueError("Meshes takes a list of (V, 3) vertex tensors and a list of (F, 3) face tensors")
+        if len(verts) != len(faces):
+            raise ValueError(f"{len(verts)} vertex tensors for {len(faces)} face tensors")
+        for v, f in zip(verts, faces):
+            if v.dim() != 2 or v.shape[1] != 3 or not v.is_floating_point():
+                raise ValueError(f"vertices must be (V, 3) floating point, got {tuple(v.shape)} {v.dtype}")
+            if f.dim() != 2 or f.shape[1] != 3 or f.is_floating_point() or f.dtype == torch.bool:
+                raise ValueError(f"faces must be (F, 3) integers, got {tuple(f.shape)} {f.dtype}")
+        self._verts, self._faces = list(verts), list(faces)
+
+    def __len__(self):
+        return len(self._verts)
+
+    @property
+    def device(self):
+        return self._verts[0].device if self._verts else torch.device("cpu")
+
+    def verts_list(self):
+        return self._verts
+
+    def faces_list(self):
+        return self._faces
+
+    def verts_packed(self):
+        """(sum V, 3): the vertices of all meshes, mesh after mesh."""
+        return torch.cat(self._verts) if self._verts else torch.zeros(0, 3)
+
+    def faces_packed(self):
+        """(sum F, 3) int64 indices into verts_packed() (pytorch3d's convention: each mesh's indices shifted by its first row)."""
+        if not self._faces:
+            return torch.zeros(0, 3, dtype=torch.int64)
+        first = self.mesh_to_verts_packed_first_idx()
+        return torch.cat([f.long() + int(o) for f, o in zip(self._faces, first)])
+
+    def mesh_to_verts_packed_first_idx(self):
+        """(len,) int64 on the host: the row of verts_packed() at which each mesh starts."""
+        sizes = torch.tensor([v.shape[0] for v in self._verts], dtype=torch.int64)
+        return torch.cumsum(sizes, 0) - sizes
+
+    def mesh_to_faces_packed_first_idx(self):
+        sizes = torch.tensor([f.shape[0] for f in self._faces], dtype=torch.int64)
+        return torch.cumsum(sizes, 0) - sizes
+
+    def faces_normals_packed(self, normalized=True):
+        """(sum F, 3): (v1 - v0) x (v2 - v0) per face, of unit length unless normalized=False (then twice the area long)."""
+        verts, faces = self.verts_packed(), self.faces_packed().to(self.device)
+        tri = verts[faces]
+        n = torch.linalg.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0], dim=1)
+        return n / n.norm(dim=1, keepdim=True).clamp_min(1e-12) if normalized else n
+
+    def verts_normals_packed(self):
+        """(sum V, 3): the area-weighted face normals summed over the faces around each vertex (index_add_; the order of the sum is
+        not fixed) and normalised; a vertex no face uses gets zeros.  Torch code on the meshes' device: not a hot path."""
+        verts, faces = self.verts_packed(), self.faces_packed().to(self.device)
+        n = self.faces_normals_packed(normalized=False)
+        acc = torch.zeros_like(verts)
+        for k in range(3):
+            acc.index_add_(0, faces[:, k], n)
+        return acc / acc.norm(dim=1, keepdim=True).clamp_min(1e-12)
+
+
 def r2n2_camera(azimuth, elevation, distance, focal=2.1875):
     """R2N2-style camera looking at the origin (dataset/utils.py:40-114 + shapenet_r2n2.py:46-53,86-93 with the
     identity normalisation mean=0, std=1): used for synthetic benchmark inputs."""

@@ -38,6 +38,10 @@ class RunConfig:  # structured.py:14-56
     # with normals oriented by visibility voting and one-sided shading; "none" = as before
     render_shading: str = "none"
     render_normals_k: int = 50
+    # the tree of triangle meshes (python -m bdm_amd.surface --out_dir) under render_sample_dir that main_render.py also draws when
+    # it exists, and how: "smooth" (Gouraud from vertex normals), "flat" (one colour per face) or "none" (black silhouettes)
+    render_mesh_subdir: str = "pred_mesh"
+    render_mesh_shading: str = "smooth"
     save_dir: Optional[str] = None
     # not in the reference: "reference" = its draws (CPU generator for the initial cloud and the blend masks, the device's
     # global generator for DDPM / PVD noise, seeded seed + rank); "per_shape" = Philox streams keyed by (seed, global

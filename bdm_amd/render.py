@@ -6,7 +6,10 @@ The reference renders with pytorch3d's PointsRasterizer + NormWeightedCompositor
 torchvision's make_grid.  Neither package is installed here, so both are restated from their published behaviour ("parity
 unpinned", as oracle/ref_sampler.py says of the conditioning rasteriser).  Two documented departures from pytorch3d
 (DESIGN.md section 12): `Fragments.idx` is the index of the point WITHIN its cloud (pytorch3d: within the packed batch), and for
-H != W each image axis spans NDC [-1, 1] (pytorch3d scales the longer axis by the aspect ratio)."""
+H != W each image axis spans NDC [-1, 1] (pytorch3d scales the longer axis by the aspect ratio).
+
+The mesh half of that package (MeshRasterizer plus a shader) follows further down: rasterize_meshes, render_mesh_batch and
+visualize_mesh_batch over bdm_render_meshes (csrc/mesh_render.hip)."""
 import math
 import os
 from collections import namedtuple
@@ -98,6 +101,163 @@ def shade_by_normals(points, normals, cameras, ambient=0.3, albedo=(0.8, 0.8, 0.
     lambert = (normals.to(points) * v).sum(-1, keepdim=True)
     lambert = lambert.abs() if two_sided else lambert.clamp_min(0.0)
     return torch.as_tensor(albedo, dtype=points.dtype, device=points.device) * (ambient + (1.0 - ambient) * lambert)
+
+
+# ---- triangle meshes ---------------------------------------------------------------------------------------------------------------
+# pytorch3d's MeshRasterizer (faces_per_pixel = 1, blur_radius = 0) and a Gouraud / flat shader over bdm_render_meshes
+# (csrc/mesh_render.hip; the rule is stated in include/bdm_hip.h section 13 and DESIGN.md section 17).  Departures from pytorch3d,
+# beside the two above: `pix_to_face` counts WITHIN the mesh (pytorch3d: within the packed batch), K is fixed at 1, there is no
+# `dists` (no blur radius, so pytorch3d's would only hold the signed distance to the winning face's edges), and a pixel centre on
+# a shared edge belongs to exactly one face by a half-plane rule (pytorch3d decides by floating-point signs).
+MeshFragments = namedtuple("MeshFragments", ["pix_to_face", "zbuf", "bary_coords"])
+MESH_SHADINGS = ("smooth", "flat", "none")
+MESH_MAX_SIDE, MESH_MAX_C = 4096, 4   # limits of bdm_render_meshes
+
+
+def _check_mesh_args(cameras, meshes, image_size):
+    """The argument checks that need no device -> (joined cameras, H, W)."""
+    if not hasattr(meshes, "verts_list") or not hasattr(meshes, "faces_list"):
+        raise ValueError(f"expected a Meshes, got {type(meshes).__name__}")
+    cameras = join_cameras(cameras)
+    if len(cameras) != len(meshes):
+        raise ValueError(f"{len(cameras)} cameras for {len(meshes)} meshes")
+    H, W = _image_hw(image_size)
+    if not (1 <= H <= MESH_MAX_SIDE and 1 <= W <= MESH_MAX_SIDE):
+        raise ValueError(f"image size {H} x {W} is outside 1..{MESH_MAX_SIDE}")
+    if len(meshes) * H * W >= 2 ** 31:
+        raise ValueError(f"{len(meshes)} images of {H} x {W} pixels reach 2^31: split the batch")
+    return cameras, H, W
+
+
+def _render_meshes(cameras, meshes, image_size, cull_backfaces=False, vert_features=None, face_features=None, background=None,
+                   fragments=True):
+    """One bdm_render_meshes call: (MeshFragments or None, image (B, H, W, C) or None; an image is made iff `background` is given)."""
+    cameras, H, W = _check_mesh_args(cameras, meshes, image_size)
+    if vert_features is not None and face_features is not None:
+        raise ValueError("vertex features and face features are exclusive")
+    B = len(meshes)
+    verts_list, faces_list = meshes.verts_list(), meshes.faces_list()
+    nv, nf = [int(v.shape[0]) for v in verts_list], [int(f.shape[0]) for f in faces_list]
+    sum_v, sum_f = sum(nv), sum(nf)
+    bg, C = None, 3
+    if background is not None:
+        bg = torch.as_tensor(background, dtype=torch.float32).reshape(-1)
+        C = int(bg.shape[0])
+        if not 1 <= C <= MESH_MAX_C:
+            raise ValueError(f"{C} background channels are outside 1..{MESH_MAX_C}")
+    for name, feats, rows in (("vertex", vert_features, sum_v), ("face", face_features, sum_f)):
+        if feats is not None and (background is None or tuple(feats.shape) != (rows, C)):
+            raise ValueError(f"{name} features {tuple(feats.shape)} do not match ({rows}, {C}) and a {C}-channel background")
+    if B == 0:
+        dev = cameras.device
+        frag = MeshFragments(torch.zeros(0, H, W, 1, dtype=torch.int64, device=dev), torch.zeros(0, H, W, 1, device=dev),
+                             torch.zeros(0, H, W, 1, 3, device=dev)) if fragments else None
+        return frag, (None if bg is None else torch.zeros(0, H, W, C, device=dev))
+    dev = verts_list[0].device
+    # the ABI takes no NULL input: an empty batch side still gets one (unread) row
+    verts = L.f32(torch.cat(verts_list)) if sum_v else torch.zeros(1, 3, device=dev)
+    faces = L.i32(torch.cat(faces_list)) if sum_f else torch.zeros(1, 3, dtype=torch.int32, device=dev)
+    vert_first = torch.tensor([0] + nv, dtype=torch.int64).cumsum(0)   # host arrays: the call reads them before it returns
+    face_first = torch.tensor([0] + nf, dtype=torch.int64).cumsum(0)
+    cams = cameras.packed().to(dev)
+    pix = zbuf = bary = image = None
+    if fragments:
+        pix = torch.empty(B, H, W, dtype=torch.int32, device=dev)
+        zbuf = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+        bary = torch.empty(B, H, W, 3, dtype=torch.float32, device=dev)
+    if bg is not None:
+        bg = bg.to(dev)
+        image = torch.empty(B, H, W, C, dtype=torch.float32, device=dev)
+        vert_features = None if vert_features is None else L.f32(vert_features)
+        face_features = None if face_features is None else L.f32(face_features)
+    lib = L.lib()
+    ws = ops.workspace(lib.bdm_render_meshes_workspace_bytes(B, sum_v, sum_f, H, W), dev, "render_meshes")
+    L.check(lib.bdm_render_meshes(B, H, W, C, int(cameras.orthographic), int(bool(cull_backfaces)), L.ptr(verts), L.ptr(faces),
+                                  vert_first.data_ptr(), face_first.data_ptr(), L.ptr(cams), L.ptr(vert_features), L.ptr(face_features),
+                                  L.ptr(bg), L.ptr(pix), L.ptr(zbuf), L.ptr(bary), L.ptr(image), L.ptr(ws), L.stream()), "render_meshes")
+    frag = MeshFragments(pix.long()[..., None], zbuf[..., None], bary[:, :, :, None, :]) if fragments else None
+    return frag, image
+
+
+def rasterize_meshes(cameras, meshes, image_size=224, cull_backfaces=False):
+    """pytorch3d's MeshRasterizer at faces_per_pixel = 1, blur_radius = 0 -> MeshFragments of pix_to_face (B, H, W, 1) int64 (the
+    face index WITHIN the mesh, -1 = empty), zbuf (B, H, W, 1) (view depth, -1) and bary_coords (B, H, W, 1, 3) (perspective-correct
+    under a perspective camera, in the face's own vertex order, -1).  cull_backfaces drops the faces whose geometric normal
+    (v1 - v0) x (v2 - v0) points away from the camera.  There is no near-plane clipping: a face with a vertex at or behind the
+    camera plane is dropped whole."""
+    return _render_meshes(cameras, meshes, image_size, cull_backfaces)[0]
+
+
+@torch.no_grad()
+def render_mesh_batch(cameras, meshes, image_size=224, shading="smooth", vert_colors=None, background_color=BACKGROUND, ambient=0.3,
+                      cull_backfaces=False):
+    """Images (B, H, W, 3) of the meshes seen from `cameras` (Perspective- or OrthographicCameras, or a list of single cameras).
+    shading="smooth": shade_by_normals(..., two_sided=False) on the vertices and their normals (Meshes.verts_normals_packed),
+    Gouraud colours the kernel interpolates; "flat": the same on face centroids and face normals, one colour per face; "none":
+    `vert_colors` (sum V, 3) interpolated, or zeros.  Bad arguments raise ValueError before any launch."""
+    if shading not in MESH_SHADINGS:
+        raise ValueError(f"shading={shading!r}: expected one of {MESH_SHADINGS}")
+    if vert_colors is not None and shading != "none":
+        raise ValueError("vert_colors need shading='none'")
+    if not 0.0 <= float(ambient) <= 1.0:
+        raise ValueError(f"ambient={ambient} is outside 0..1")
+    cameras, _, _ = _check_mesh_args(cameras, meshes, image_size)
+    vert_features = face_features = None
+    if shading == "none":
+        vert_features = vert_colors
+    elif len(meshes) and sum(int(f.shape[0]) for f in meshes.faces_list()):
+        verts = meshes.verts_packed()
+        if shading == "smooth":
+            where, normals, sizes = verts, meshes.verts_normals_packed(), [int(v.shape[0]) for v in meshes.verts_list()]
+        else:
+            where, normals = verts[meshes.faces_packed().to(verts.device)].mean(dim=1), meshes.faces_normals_packed()
+            sizes = [int(f.shape[0]) for f in meshes.faces_list()]
+        if cameras.orthographic:
+            # one-sided, shade_by_normals lights an orthographic view along R[:, :, 2], the view axis INTO the screen (pinned by
+            # tests/test_orient_host.py): a surface that faces the viewer has n . axis < 0, so the normals go in negated
+            normals = -normals
+        # shade_by_normals works on (B, n, 3) with one camera per row: one row per mesh, each with its own camera
+        colours = [shade_by_normals(p[None], n[None], _camera_row(cameras, i), ambient=ambient, two_sided=False)[0]
+                   for i, (p, n) in enumerate(zip(torch.split(where, sizes), torch.split(normals, sizes)))]
+        colours = torch.cat(colours).float().contiguous()
+        vert_features, face_features = (colours, None) if shading == "smooth" else (None, colours)
+    return _render_meshes(cameras, meshes, image_size, cull_backfaces, vert_features, face_features, background_color, fragments=False)[1]
+
+
+def _camera_row(cameras, i):
+    return type(cameras)(cameras.focal_length[i:i + 1], cameras.principal_point[i:i + 1], cameras.R[i:i + 1], cameras.T[i:i + 1],
+                         device=cameras.device)
+
+
+@torch.no_grad()
+def visualize_mesh_batch(meshes, output_file_image=None, num_frames=1, elev=30, scale_factor=1.0, shading="smooth", image_size=224,
+                         cull_backfaces=False):
+    """The orbit of visualize_pointcloud_batch_pytorch3d for meshes: `num_frames` orthographic cameras (focal 0.25 * scale_factor)
+    at distance 10 and elevation `elev`, every frame lit from its own camera, tiled with make_grid(nrow=int(sqrt(B)), pad_value=1);
+    one frame goes to `output_file_image`, with num_frames > 1 frame f goes to <stem>-<f>.png beside it.  Returns the grids
+    (F, C, H', W') on the host."""
+    from .cameras import Meshes
+    from .io import save_image_png
+    F = int(num_frames)
+    if F < 1 or 360 % F:
+        raise ValueError("num_frames must divide 360")
+    B = len(meshes)
+    if B == 0:
+        raise ValueError("no mesh to draw")
+    device = meshes.device
+    R, T = look_at_view_transform(dist=10.0, elev=elev, azim=list(range(0, 360, 360 // F)), degrees=True, device=device)
+    cameras = OrthographicCameras(focal_length=0.25 * scale_factor, device=device, R=R.repeat_interleave(B, dim=0), T=T.repeat_interleave(B, dim=0))
+    images = render_mesh_batch(cameras, Meshes(meshes.verts_list() * F, meshes.faces_list() * F), image_size, shading, cull_backfaces=cull_backfaces)
+    frames = images.reshape(F, B, *images.shape[1:]).permute(0, 1, 4, 2, 3)
+    grids = torch.stack([make_grid(f, nrow=int(math.sqrt(B)), pad_value=1) for f in frames], dim=0).detach().cpu()
+    if output_file_image is not None:
+        if F == 1:
+            save_image_png(grids[0].numpy(), output_file_image)
+        else:
+            stem, ext = os.path.splitext(str(output_file_image))
+            for f in range(F):
+                save_image_png(grids[f].numpy(), f"{stem}-{f}{ext or '.png'}")
+    return grids
 
 
 def make_grid(tensor, nrow=8, padding=2, pad_value=0.0):

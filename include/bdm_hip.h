@@ -1023,6 +1023,60 @@ int bdm_surface_grid(int b, int n, int r, int s, float min_weight, const float *
 int bdm_surface_extract(int b, int n, int r, int s, const long long *vert_offsets, const long long *face_offsets, float *verts,
                         int *faces, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * 13. Rendering of triangle meshes (csrc/mesh_render.hip): one face per pixel, all-integer coverage with a half-plane fill rule,
+ *     float32 depth and barycentrics rounded operation by operation; restates pytorch3d's MeshRasterizer (faces_per_pixel = 1,
+ *     blur_radius = 0) plus a Gouraud / flat shader from its published behaviour (pytorch3d is not installed: parity unpinned).
+ *     DESIGN.md section 17.
+ * ---------------------------------------------------------------------------------- */
+/* Inputs: verts (sum V, 3) float32 world coordinates and faces (sum F, 3) int32 vertex indices WITHIN their own mesh, both packed
+ *   mesh after mesh; vert_first, face_first (b + 1) int64 row offsets of the meshes into the two arrays (entry b = sum V, sum F),
+ *   arrays in HOST memory: they are read during the call (they size the launches) and copied to the device as launch arguments,
+ *   so they may be freed when the call returns.  A mesh with V == 0 or F == 0 is legal and renders as background.
+ *   cameras (b, 16) as bdm_render_points takes them; ortho = 1: OrthographicCameras.
+ * All float32 arithmetic is rounded operation by operation (no FMA contraction), in the order written, division correctly
+ *   rounded; fl() is left out below.
+ * Vertices: xv = ((x c0 + y c3) + z c6) + c9, yv and zv alike with c1, c4, c7, c10 and c2, c5, c8, c11 (bdm_render_points' view
+ *   transform); ndc_x = (c12 xv) / zv + c14, ndc_y = (c13 yv) / zv + c15; ortho = 1 drops the two divisions.
+ *   sx = (1 - ndc_x) * (0.5 w), sy = (1 - ndc_y) * (0.5 h) (0.5 w is exact): pixel (yi, xi) has its centre at (xi + 0.5, yi + 0.5),
+ *   +X left and +Y up as in the point renderer; for h != w each axis spans [-1, 1].
+ *   Snapped to 1/256 pixel: SX = rint(sx * 256), SY = rint(sy * 256), rint rounding half to even, as integers.
+ *   A vertex is usable iff zv is finite and zv > 0 and both products sx * 256, sy * 256 are finite with magnitude <= 2^22.
+ *   A face with an unusable vertex, or a vertex index outside [0, V), is dropped whole.  There is NO near-plane clipping: a
+ *   triangle that crosses the camera plane disappears.
+ * Coverage (all int64): edge(a, b, p) = (bx - ax)(py - ay) - (by - ay)(px - ax).  A = edge(v0, v1, v2); A == 0: dropped.
+ *   A < 0 is a FRONT face, its geometric normal (v1 - v0) x (v2 - v0) points to the camera (view axes x left, y up, z into the
+ *   screen are right-handed, and the screen reverses both x and y, which keeps the sign of the z component of the normal).
+ *   cull = 1 drops the faces with A > 0.  If A < 0, v1 and v2 are swapped (and A negated), so that A > 0 from here on;
+ *   everything below, the depth included, uses the swapped order and the barycentrics are swapped back at the end.
+ *   P = (256 xi + 128, 256 yi + 128); E0 = edge(v1, v2, P), E1 = edge(v2, v0, P), E2 = edge(v0, v1, P).  The pixel is covered
+ *   iff for every i: E_i > 0, or E_i == 0 and edge i owns its boundary; the edge from a to b with (dx, dy) = b - a owns its
+ *   boundary iff dy > 0 || (dy == 0 && dx > 0).  Two faces on opposite sides of a shared edge see opposite directions, so a
+ *   centre on the edge belongs to exactly one of them, and a centre on the shared vertex of a closed fan to exactly one face.
+ * Depth and barycentrics: w_i = float(E_i) / float(A), the int64 -> float32 conversions rounding to nearest even.
+ *   Orthographic: bary = w; z = ((w0 z0) + (w1 z1)) + (w2 z2).
+ *   Perspective (perspective-correct): t_i = w_i / z_i; s = (t0 + t1) + t2; z = 1 / s; bary_i = t_i / s.
+ *   A fragment whose z is not finite or not > 0 is dropped.  The pixel keeps the fragment with the smallest key
+ *   (bits of z) << 32 | face index within the mesh: equal depths go to the lower index.  One face per pixel, no blur radius.
+ * Outputs, any of which may be NULL: pix_to_face (b, h, w) int32, the face index WITHIN the mesh, -1 = empty; zbuf (b, h, w), -1 =
+ *   empty; bary (b, h, w, 3) in the face's own vertex order, -1 = empty; image (b, h, w, c): from vert_features (sum V, c)
+ *   ((b0 f0) + (b1 f1)) + (b2 f2) per channel, from face_features (sum F, c) the winning face's row (flat shading), with neither
+ *   zeros; an empty pixel takes background (c).  Passing both feature arrays is an error.
+ * Limits: b >= 0 (b == 0 launches nothing and returns 0), 1 <= c <= 4, 1 <= h, w <= 4096, ortho and cull in {0, 1}, sum V and
+ *   sum F < 2^31, b h w < 2^31, offsets non-decreasing from 0, no NULL among verts, faces, vert_first, face_first, cameras and the
+ *   workspace (nor background when image is given), no output and no part of the workspace overlapping an input or each other.
+ *   Outside these the call returns 1 and launches nothing.
+ * Determinism: one integer atomic minimum per surviving fragment in global memory, no floating-point atomics, no workgroup waits
+ *   on another, every loop is bounded by a launch argument; mesh j of a batch has the bits of that mesh rendered alone, and so
+ *   has a repeated call.
+ * workspace: bdm_render_meshes_workspace_bytes(b, sum_v, sum_f, h, w) bytes (0 for sizes outside the limits), contents irrelevant
+ *   before: the (b, h, w) 64-bit key image, 16 bytes per vertex (SX, SY, zv, usable) and the two offset arrays. */
+size_t bdm_render_meshes_workspace_bytes(int b, long long sum_v, long long sum_f, int h, int w);
+int bdm_render_meshes(int b, int h, int w, int c, int ortho, int cull, const float *verts, const int *faces,
+                      const long long *vert_first, const long long *face_first, const float *cameras,
+                      const float *vert_features, const float *face_features, const float *background, int *pix_to_face,
+                      float *zbuf, float *bary, float *image, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,9 +9,14 @@ orbiting orthographic view of every predicted cloud (the coloured one where it e
 With run.render_shading=normals the uncoloured kinds (gt, pred, the orbit of an uncoloured prediction) are lit by their estimated
 normals (bdm_amd.normals, run.render_normals_k neighbours) instead of rendering as black silhouettes; `colored` is untouched.
 run.render_shading=oriented does the same with normals oriented by visibility voting and one-sided shading.
+Where ${run.render_sample_dir}/${run.render_mesh_subdir} exists (the tree `python -m bdm_amd.surface` writes), every triangle mesh
+<category>/<name>.ply or <name>-<k>.ply in it is drawn from its entry's camera as renders/mesh/<category>/<stem>.png
+(run.render_mesh_shading = smooth | flat | none), and with run.render_num_frames > 1 its orbit as
+renders/mesh_orbit/<category>/<stem>-<f>.png; a file without a face element is a cloud and is left alone.
 
     python main_blending.py run.job=sample_bdm_blending dataset=synthetic run.num_samples=1 dataset.max_points=1024
     python main_render.py dataset=synthetic run.render_sample_dir=<the directory the first command printed>
+    python -m bdm_amd.surface --in_dir <that directory>/pred --out_dir <that directory>/pred_mesh     (then the line above again)
 """
 import sys
 from pathlib import Path
@@ -22,6 +27,7 @@ from main_blending import get_dataloader
 
 KINDS = ("gt", "pred", "colored")
 SHADINGS = ("none", "normals", "oriented")
+MESH_SHADINGS = ("smooth", "flat", "none")
 
 
 def parse_args(argv):
@@ -33,6 +39,8 @@ def parse_args(argv):
         raise ValueError("run.render_num_frames must divide 360")
     if cfg.run.render_shading not in SHADINGS:
         raise ValueError(f"run.render_shading={cfg.run.render_shading!r}: expected one of {SHADINGS}")
+    if cfg.run.render_mesh_shading not in MESH_SHADINGS:
+        raise ValueError(f"run.render_mesh_shading={cfg.run.render_mesh_shading!r}: expected one of {MESH_SHADINGS}")
     return cfg
 
 
@@ -44,13 +52,29 @@ def clouds_of(sample_dir, kind, category, name):
     return hits
 
 
-def render_tree(cfg, batches, render_fn, orbit_fn=None, device="cpu", shade_fn=None):
+def meshes_of(sample_dir, subdir, category, name):
+    """The triangle meshes of one dataset entry under <sample_dir>/<subdir>: [(path, verts (V, 3) float32, faces (F, 3) int64)] of
+    <name>.ply and <name>-<k>.ply, sorted; a file without a face element is a cloud and is not among them."""
+    from bdm_amd.io import load_mesh_ply
+    out = []
+    for path in clouds_of(sample_dir, subdir, category, name):
+        with open(path, "rb") as f:
+            head = f.read(4096).split(b"end_header")[0]
+        if b"element face" in head:
+            out.append((path, *load_mesh_ply(path)))
+    return out
+
+
+def render_tree(cfg, batches, render_fn, orbit_fn=None, device="cpu", shade_fn=None, mesh_fn=None, mesh_orbit_fn=None):
     """Walk the dataset, render every cloud found under the sample directory, write renders/<kind>/<category>/<stem>.png; returns
     the paths written.  render_fn(cameras (list of single cameras), points (B, n, 3), colours (B, n, 3) or None) -> images
     (B, H, W, 3) in [0, 1]: one call per batch, kind and distinct point count.  orbit_fn(points (1, n, 3), colours or None,
     path of <stem>.png, num_frames) -> the paths it wrote: called per predicted cloud when run.render_num_frames > 1.
     shade_fn(cameras, points (B, n, 3)) -> colours (B, n, 3): with run.render_shading=normals or oriented the uncoloured kinds get
-    their colours from it, once per batch group (a config without the key, or "none", leaves them None as before)."""
+    their colours from it, once per batch group (a config without the key, or "none", leaves them None as before).
+    Where <sample_dir>/<run.render_mesh_subdir> exists: mesh_fn(cameras, verts_list, faces_list) -> images (B, H, W, 3), one call
+    per batch, written as renders/mesh/<category>/<stem>.png; mesh_orbit_fn(verts (V, 3), faces (F, 3), path of <stem>.png,
+    num_frames) -> the paths it wrote, per mesh when run.render_num_frames > 1.  Without that directory nothing changes."""
     from bdm_amd.io import load_pointcloud_ply, save_image_png
     root, written = Path(cfg.run.render_sample_dir), []
     shading = getattr(cfg.run, "render_shading", "none")
@@ -58,6 +82,10 @@ def render_tree(cfg, batches, render_fn, orbit_fn=None, device="cpu", shade_fn=N
         raise ValueError(f"run.render_shading={shading!r}: expected one of {SHADINGS}")
     if shading != "none" and shade_fn is None:
         raise ValueError(f"run.render_shading={shading} needs a shade_fn")
+    mesh_subdir = getattr(cfg.run, "render_mesh_subdir", "pred_mesh")
+    with_meshes = bool(mesh_subdir) and (root / mesh_subdir).is_dir()
+    if with_meshes and mesh_fn is None:
+        raise ValueError(f"{root / mesh_subdir} holds meshes: they need a mesh_fn")
     for batch_idx, batch in enumerate(batches):
         if cfg.run.num_sample_batches is not None and batch_idx >= cfg.run.num_sample_batches:
             break
@@ -96,13 +124,29 @@ def render_tree(cfg, batches, render_fn, orbit_fn=None, device="cpu", shade_fn=N
                     out = root / "renders" / "orbit" / cat / f"{path.stem}.png"
                     written += [Path(p) for p in orbit_fn(pts[None].to(device), None if col is None else col[None].to(device), out,
                                                           cfg.run.render_num_frames)]
+        if with_meshes:
+            found = [(i, *item) for i, (name, cat) in enumerate(zip(batch.sequence_name, batch.sequence_category))
+                     for item in meshes_of(root, mesh_subdir, cat, name)]
+            if found:
+                verts = [torch.from_numpy(v).to(device) for _, _, v, _ in found]
+                faces = [torch.from_numpy(f).to(device) for _, _, _, f in found]
+                images = mesh_fn([cameras[i] for i, _, _, _ in found], verts, faces)
+                for (i, path, _, _), image in zip(found, images):
+                    out = root / "renders" / "mesh" / batch.sequence_category[i] / f"{path.stem}.png"
+                    save_image_png(image.detach().cpu().permute(2, 0, 1).numpy(), out)
+                    written.append(out)
+                if cfg.run.render_num_frames > 1 and mesh_orbit_fn is not None:
+                    for (i, path, _, _), v, f in zip(found, verts, faces):
+                        out = root / "renders" / "mesh_orbit" / batch.sequence_category[i] / f"{path.stem}.png"
+                        written += [Path(p) for p in mesh_orbit_fn(v, f, out, cfg.run.render_num_frames)]
     return written
 
 
 def main(argv=None):
-    from bdm_amd.cameras import Pointclouds
+    from bdm_amd.cameras import Meshes, Pointclouds
     from bdm_amd.distributed import barrier, gpu_turn, init_from_env
-    from bdm_amd.render import render_pointcloud_batch_pytorch3d, shade_by_normals, visualize_pointcloud_batch_pytorch3d
+    from bdm_amd.render import (render_mesh_batch, render_pointcloud_batch_pytorch3d, shade_by_normals, visualize_mesh_batch,
+                                visualize_pointcloud_batch_pytorch3d)
     cfg = parse_args(sys.argv[1:] if argv is None else argv)
     rank, local_rank, world = init_from_env()
     device = torch.device("cuda", local_rank)
@@ -143,7 +187,17 @@ def main(argv=None):
                                                      output_file_image=str(out[f]), cameras=cam)
         return out
 
-    written = render_tree(cfg, get_dataloader(cfg, rank, world), render_fn, orbit_fn, device, shade_fn)
+    def mesh_fn(cameras, verts, faces):
+        with gpu_turn(device):
+            return render_mesh_batch(cameras, Meshes(verts, faces), shading=cfg.run.render_mesh_shading).cpu()
+
+    def mesh_orbit_fn(verts, faces, path, num_frames):
+        with gpu_turn(device):
+            visualize_mesh_batch(Meshes([verts], [faces]), output_file_image=str(path), num_frames=num_frames,
+                                 scale_factor=cfg.model.scale_factor, shading=cfg.run.render_mesh_shading)
+        return [path.with_name(f"{path.stem}-{f}.png") for f in range(num_frames)]
+
+    written = render_tree(cfg, get_dataloader(cfg, rank, world), render_fn, orbit_fn, device, shade_fn, mesh_fn, mesh_orbit_fn)
     barrier()
     print(f"rank {rank}: rendered {len(written)} images under {(Path(cfg.run.render_sample_dir) / 'renders').absolute()}")
     return written
