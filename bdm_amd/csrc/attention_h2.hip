@@ -9,6 +9,7 @@
 // v and probability scales at the final normalisation).  Probabilities (in [0, 1]) are scaled by 2^14 before their split.
 #include "../../include/bdm_hip.h"
 #include "common.h"
+#include "h2_split.h"
 #include <type_traits>
 
 using namespace bdm;
@@ -17,13 +18,6 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 
 namespace {
-
-__device__ __forceinline__ float h2_scale_from_max(float amax) {  // power of two s with amax * s in [2^14, 2^15)
-  if (!(amax > 0.f) || !(amax < INFINITY)) return 1.f;
-  int ex;
-  (void)frexpf(amax, &ex);
-  return ldexpf(1.f, 15 - ex);
-}
 
 __device__ __forceinline__ void split2h(float v, unsigned short &h, unsigned short &l) {
   const _Float16 hi = (_Float16)v;
@@ -45,7 +39,7 @@ __global__ void attn_split_qk_h2_kernel(int C, int L, const float *__restrict__ 
                                         int ld, const float *__restrict__ amax, uint4 *__restrict__ qs, uint4 *__restrict__ ks) {
   const int l = blockIdx.x * blockDim.x + threadIdx.x, c8 = blockIdx.y, C8 = gridDim.y, bi = blockIdx.z >> 1, which = blockIdx.z & 1;
   if (l >= L) return;
-  const float s = h2_scale_from_max(amax[bi * 3 + which]);  // per shape
+  const float s = act_scale_from_max(amax[bi * 3 + which]);  // per shape
   const float *src = (which ? k : q) + (size_t)bi * bs;
   uint4 *dst = (which ? ks : qs) + ((size_t)bi * C8 + c8) * 2 * (size_t)L;
   unsigned short h[8], lo[8];
@@ -63,7 +57,7 @@ __global__ void attn_split_v_h2_kernel(int C, int CP, int L, int Lp, const float
                                        const float *__restrict__ amax, unsigned short *__restrict__ vt) {
   const int l0 = (blockIdx.x * blockDim.x + threadIdx.x) * 8, c = blockIdx.y, bi = blockIdx.z;
   if (l0 >= Lp) return;
-  const float s = h2_scale_from_max(amax[bi * 3 + 2]);
+  const float s = act_scale_from_max(amax[bi * 3 + 2]);
   unsigned short h[8], lo[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) split2h((c < C && l0 + j < L) ? v[(size_t)bi * bs + (size_t)c * ld + l0 + j] * s : 0.f, h[j], lo[j]);
@@ -106,7 +100,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
   const int i0 = ((item - bi * qtiles) * 4 + wave) * 32;  // this wave's first query
   const uint4 *qb = qs + (size_t)bi * C8 * 2 * L, *kb = ks + (size_t)bi * C8 * 2 * L;
   const unsigned short *vb = vt + (size_t)bi * 2 * CP * Lp;
-  const float sq = h2_scale_from_max(amax[bi * 3]), sk = h2_scale_from_max(amax[bi * 3 + 1]), sv = h2_scale_from_max(amax[bi * 3 + 2]);
+  const float sq = act_scale_from_max(amax[bi * 3]), sk = act_scale_from_max(amax[bi * 3 + 1]), sv = act_scale_from_max(amax[bi * 3 + 2]);
   // exp(x) = 2^(x log2 e): the q.k scale (a power of two, exact) is divided out inside the constant
   const float ec = 1.44269504088896340736f / (sq * sk);
 
@@ -340,7 +334,7 @@ __global__ void attn_combine_kernel(int C, int CP, int L, int nb, int ksplit, co
     f[s] = ml[1] > 0.f ? __builtin_amdgcn_exp2f(m - ml[0]) : 0.f;
     den += ml[1] * f[s];
   }
-  const float sv = h2_scale_from_max(amax[bi * 3 + 2]);
+  const float sv = act_scale_from_max(amax[bi * 3 + 2]);
   const float inv = 1.0f / (den * 16384.f * sv);
   for (int c = blockIdx.y; c < C; c += gridDim.y) {
     float acc = 0.f;

@@ -42,16 +42,11 @@ __global__ void attn_split_v_kernel(int C, int CP, int L, int Lp, const float *_
                                     unsigned short *__restrict__ vt) {
   const int l0 = (blockIdx.x * blockDim.x + threadIdx.x) * 8, c = blockIdx.y, bi = blockIdx.z;
   if (l0 >= Lp) return;
-  unsigned short h[8], m[8], lo[8];
+  float x[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float x = (c < C && l0 + j < L) ? v[(size_t)bi * bs + (size_t)c * ld + l0 + j] : 0.f;
-    split3(x, h[j], m[j], lo[j]);
-  }
+  for (int j = 0; j < 8; ++j) x[j] = (c < C && l0 + j < L) ? v[(size_t)bi * bs + (size_t)c * ld + l0 + j] : 0.f;
   uint4 ph, pm, pl;
-  ph.x = h[0] | (h[1] << 16); ph.y = h[2] | (h[3] << 16); ph.z = h[4] | (h[5] << 16); ph.w = h[6] | (h[7] << 16);
-  pm.x = m[0] | (m[1] << 16); pm.y = m[2] | (m[3] << 16); pm.z = m[4] | (m[5] << 16); pm.w = m[6] | (m[7] << 16);
-  pl.x = lo[0] | (lo[1] << 16); pl.y = lo[2] | (lo[3] << 16); pl.z = lo[4] | (lo[5] << 16); pl.w = lo[6] | (lo[7] << 16);
+  split3_record(x, ph, pm, pl);
   unsigned short *base = vt + (size_t)bi * 3 * CP * Lp;
   *reinterpret_cast<uint4 *>(base + ((size_t)0 * CP + c) * Lp + l0) = ph;
   *reinterpret_cast<uint4 *>(base + ((size_t)1 * CP + c) * Lp + l0) = pm;

@@ -9,6 +9,7 @@
 // cell is timing dependent there too), except avg_voxelize_backward, which is a pure gather.
 #include "../../include/bdm_hip.h"
 #include "common.h"
+#include "trilinear.h"
 
 #pragma clang fp contract(off)
 
@@ -84,24 +85,15 @@ __global__ void devox_train_kernel(int c, int n, int r, const float *__restrict_
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float *cb = coords + (size_t)bi * 3 * n;
-  const float x = cb[i], y = cb[i + n], z = cb[i + 2 * n];
-  const float xl = floorf(x), yl = floorf(y), zl = floorf(z);
-  const float x1 = x - xl, y1 = y - yl, z1 = z - zl, x0 = 1.0f - x1, y0 = 1.0f - y1, z0 = 1.0f - z1;
-  const float w[8] = {x0 * y0 * z0, x0 * y0 * z1, x0 * y1 * z0, x0 * y1 * z1, x1 * y0 * z0, x1 * y0 * z1, x1 * y1 * z0, x1 * y1 * z1};
-  const int sx = x1 > 0 ? r2 : 0, sy = y1 > 0 ? r : 0, sz = z1 > 0 ? 1 : 0;
-  const int i000 = (int)xl * r2 + (int)yl * r + (int)zl;
-  const int id[8] = {i000, i000 + sz, i000 + sy, i000 + sy + sz, i000 + sx, i000 + sx + sz, i000 + sx + sy, i000 + sx + sy + sz};
+  const TrilinearCorners tc = trilinear_corners(cb[i], cb[i + n], cb[i + 2 * n], r);
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    inds[((size_t)bi * 8 + k) * n + i] = id[k];
-    wgts[((size_t)bi * 8 + k) * n + i] = w[k];
+    inds[((size_t)bi * 8 + k) * n + i] = tc.i[k];
+    wgts[((size_t)bi * 8 + k) * n + i] = tc.w[k];
   }
   for (int ci = 0; ci < c; ++ci) {
     const float *g = grid + ((size_t)bi * c + ci) * r3;
-    float acc = w[0] * g[id[0]];
-#pragma unroll
-    for (int k = 1; k < 8; ++k) acc = acc + w[k] * g[id[k]];
-    out[((size_t)bi * c + ci) * n + i] = acc;
+    out[((size_t)bi * c + ci) * n + i] = trilinear_sum_of(tc.w, [&](int k) { return g[tc.i[k]]; });
   }
 }
 

@@ -22,6 +22,8 @@
 
 #include "../../include/bdm_hip.h"
 #include "common.h"
+#include "gn_rule.h"
+#include "h2_split.h"
 
 using namespace bdm;
 
@@ -30,21 +32,9 @@ typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 
 #define H2_PAIRS 14
 
-__device__ __forceinline__ void split2(float v, unsigned short &h, unsigned short &l) {
-  v = fminf(fmaxf(v, -65504.f), 65504.f);  // saturate instead of overflowing to inf
-  const _Float16 hi = (_Float16)v;          // round to nearest even
-  const _Float16 lo = (_Float16)(v - (float)hi);  // the remainder is exact in fp32
-  h = __builtin_bit_cast(unsigned short, hi);
-  l = __builtin_bit_cast(unsigned short, lo);
-}
-
 __device__ __forceinline__ void store_h2(unsigned short *base, size_t rec, size_t split_stride, const float v[8]) {
-  unsigned short h[8], l[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) split2(v[j], h[j], l[j]);
   uint4 ph, pl;
-  ph.x = h[0] | (h[1] << 16); ph.y = h[2] | (h[3] << 16); ph.z = h[4] | (h[5] << 16); ph.w = h[6] | (h[7] << 16);
-  pl.x = l[0] | (l[1] << 16); pl.y = l[2] | (l[3] << 16); pl.z = l[4] | (l[5] << 16); pl.w = l[6] | (l[7] << 16);
+  split2_record(v, ph, pl);
   uint4 *o = reinterpret_cast<uint4 *>(base);
   o[rec] = ph;
   o[split_stride + rec] = pl;
@@ -92,6 +82,9 @@ __global__ void pack_h2_kernel(int cout, int cin, const float *__restrict__ w, c
     for (int q = 0; q < 2; ++q) wq[((((size_t)(c8 * H2_PAIRS + p) * 2 + q) * 2 + h) * cout + co) * 8 + j] = s[q];
   }
 }
+void bdm::h2_weight_scale(int cout, int cin, const float *w, float *scale, float *inv_scale, hipStream_t s) {
+  hipLaunchKernelGGL(h2_weight_scale_kernel, dim3(cout), dim3(256), 0, s, cout, cin, w, scale, inv_scale);
+}
 extern "C" size_t bdm_conv3d_h2_weight_elems(int cout, int cin) {
   return (size_t)((cin + 7) / 8) * H2_PAIRS * 2 * 2 * cout * 8;
 }
@@ -99,7 +92,7 @@ extern "C" int bdm_conv3d_h2_pack_weights(int cout, int cin, const float *w, voi
                                           float *inv_scale, void *stream) {
   BDM_REQUIRE(cout >= 1 && cin >= 1 && scale_ws != nullptr && inv_scale != nullptr, "conv3d_h2_pack_weights: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(h2_weight_scale_kernel, dim3(cout), dim3(256), 0, s, cout, cin, w, scale_ws, inv_scale);
+  h2_weight_scale(cout, cin, w, scale_ws, inv_scale, s);
   hipLaunchKernelGGL(pack_h2_kernel, dim3(512), dim3(256), 0, s, cout, cin, w, scale_ws, (unsigned short *)packed);
   return launch_status("conv3d_h2_pack_weights");
 }
@@ -447,11 +440,7 @@ __global__ void to_h2_kernel(int C, int V, int G, int S, const float *__restrict
       double a = 0.0, q = 0.0;
       const size_t bg = (size_t)bi * G + threadIdx.x;
       for (int s = 0; s < S; ++s) { a += partial[(bg * S + s) * 2]; q += partial[(bg * S + s) * 2 + 1]; }
-      const double cnt = (double)cg * V, mean = a / cnt;
-      double var = q / cnt - mean * mean;
-      if (var < 0) var = 0;
-      s_mean[threadIdx.x] = (float)mean;
-      s_rstd[threadIdx.x] = (float)(1.0 / sqrt(var + (double)eps));
+      gn_mean_rstd(a, q, (double)cg * V, eps, s_mean[threadIdx.x], s_rstd[threadIdx.x]);
     }
     __syncthreads();
   }
@@ -504,11 +493,7 @@ __global__ __launch_bounds__(256) void to_h2_stats_kernel(int C, int V, int G, i
   if (tid <= g_hi - g_lo) {
     const double a = ((s_red[tid][0][0] + s_red[tid][1][0]) + s_red[tid][2][0]) + s_red[tid][3][0];
     const double q = ((s_red[tid][0][1] + s_red[tid][1][1]) + s_red[tid][2][1]) + s_red[tid][3][1];
-    const double cnt = (double)cg * V, mean = a / cnt;
-    double var = q / cnt - mean * mean;
-    if (var < 0) var = 0;
-    s_mean[tid] = (float)mean;
-    s_rstd[tid] = (float)(1.0 / sqrt(var + (double)eps));
+    gn_mean_rstd(a, q, (double)cg * V, eps, s_mean[tid], s_rstd[tid]);
   }
   __syncthreads();
   // the block's 8 channels as affine forms (a, b): x -> a x + b, one FMA per element in the loop below (no per-element group
@@ -516,14 +501,13 @@ __global__ __launch_bounds__(256) void to_h2_stats_kernel(int C, int V, int G, i
   __shared__ float s_ab[8][2];
   if (tid < 8) {
     const int ch = c8 * 8 + tid;
-    float a = 0.f, bsh = 0.f;
+    float2 ab = make_float2(0.f, 0.f);
     if (ch < C) {
       const int g = ch / cg - g_lo;
-      a = gamma[ch] * s_rstd[g];
-      bsh = beta[ch] - s_mean[g] * a;
+      ab = gn_affine(gamma[ch], s_rstd[g], beta[ch], s_mean[g]);
     }
-    s_ab[tid][0] = a;
-    s_ab[tid][1] = bsh;
+    s_ab[tid][0] = ab.x;
+    s_ab[tid][1] = ab.y;
   }
   __syncthreads();
   float ca[8], cb[8];
@@ -554,11 +538,7 @@ extern "C" int bdm_group_norm_to_h2_stats(int b, int c, int v, int groups, const
                                           const void *partial, int slices, unsigned int *saturated, void *stream) {
   BDM_REQUIRE(b >= 0 && c >= 1 && v >= 1 && groups >= 1 && c % groups == 0 && (c / groups) >= 4 && partial != nullptr && slices >= 1,
               "group_norm_to_h2_stats: bad arguments");
-  {
-    int ex = 0;
-    BDM_REQUIRE(act_scale > 0.f && act_scale < INFINITY && frexpf(act_scale, &ex) == 0.5f,
-                "group_norm_to_h2_stats: act_scale must be a power of two (got %g)", (double)act_scale);
-  }
+  BDM_REQUIRE(h2_scale_is_pow2(act_scale), "group_norm_to_h2_stats: act_scale must be a power of two (got %g)", (double)act_scale);
   if (b == 0) return BDM_OK;
   constexpr int VB = 1024;
   dim3 grid(cdiv(v, VB), (c + 7) / 8, b);
@@ -593,25 +573,21 @@ __global__ __launch_bounds__(256) void to_h2_stats_compact_kernel(int C, int V, 
   if (tid <= g_hi - g_lo) {
     const double a = ((s_red[tid][0][0] + s_red[tid][1][0]) + s_red[tid][2][0]) + s_red[tid][3][0];
     const double q = ((s_red[tid][0][1] + s_red[tid][1][1]) + s_red[tid][2][1]) + s_red[tid][3][1];
-    const double cnt = (double)cg * V, mean = a / cnt;
-    double var = q / cnt - mean * mean;
-    if (var < 0) var = 0;
-    s_mean[tid] = (float)mean;
-    s_rstd[tid] = (float)(1.0 / sqrt(var + (double)eps));
+    gn_mean_rstd(a, q, (double)cg * V, eps, s_mean[tid], s_rstd[tid]);
   }
   __syncthreads();
   __shared__ float s_ab[8][3];   // affine form (a, b) of the GroupNorm per channel, and the channel's bias
   if (tid < 8) {
     const int ch = c8 * 8 + tid;
-    float a = 0.f, bsh = 0.f, bv = 0.f;
+    float2 ab = make_float2(0.f, 0.f);
+    float bv = 0.f;
     if (ch < C) {
       const int g = ch / cg - g_lo;
-      a = gamma[ch] * s_rstd[g];
-      bsh = beta[ch] - s_mean[g] * a;
+      ab = gn_affine(gamma[ch], s_rstd[g], beta[ch], s_mean[g]);
       bv = bias ? bias[ch] : 0.f;
     }
-    s_ab[tid][0] = a;
-    s_ab[tid][1] = bsh;
+    s_ab[tid][0] = ab.x;
+    s_ab[tid][1] = ab.y;
     s_ab[tid][2] = bv;
   }
   __syncthreads();
@@ -668,11 +644,7 @@ extern "C" int bdm_group_norm_to_h2_stats_compact(int b, int c, int v, int group
   BDM_REQUIRE(b >= 0 && c >= 1 && v >= 1 && groups >= 1 && c % groups == 0 && (c / groups) >= 4 && partial != nullptr && slices >= 1 &&
                   xc != nullptr && dil_index != nullptr && n_dil_max >= 1,
               "group_norm_to_h2_stats_compact: bad arguments");
-  {
-    int ex = 0;
-    BDM_REQUIRE(act_scale > 0.f && act_scale < INFINITY && frexpf(act_scale, &ex) == 0.5f,
-                "group_norm_to_h2_stats_compact: act_scale must be a power of two (got %g)", (double)act_scale);
-  }
+  BDM_REQUIRE(h2_scale_is_pow2(act_scale), "group_norm_to_h2_stats_compact: act_scale must be a power of two (got %g)", (double)act_scale);
   if (b == 0) return BDM_OK;
   constexpr int VB = 1024;
   dim3 grid(cdiv(v, VB), (c + 7) / 8, b);
@@ -688,11 +660,7 @@ extern "C" int bdm_group_norm_to_h2(int b, int c, int v, int groups, const float
                                     const float *beta, float eps, int act, float act_scale, void *out_h2, void *workspace,
                                     unsigned int *saturated, void *stream) {
   BDM_REQUIRE(b >= 0 && c >= 1 && v >= 1, "group_norm_to_h2: bad sizes");
-  {
-    int ex = 0;
-    BDM_REQUIRE(act_scale > 0.f && act_scale < INFINITY && frexpf(act_scale, &ex) == 0.5f,
-                "group_norm_to_h2: act_scale must be a power of two (got %g)", (double)act_scale);
-  }
+  BDM_REQUIRE(h2_scale_is_pow2(act_scale), "group_norm_to_h2: act_scale must be a power of two (got %g)", (double)act_scale);
   BDM_REQUIRE(groups == 0 || (c % groups == 0 && groups <= 64 && workspace != nullptr), "group_norm_to_h2: bad groups %d", groups);
   if (b == 0) return BDM_OK;
   int S = 0;

@@ -20,6 +20,7 @@
 // Output: fp32, channel-first (B, Cout, r^3) -- what GroupNorm statistics, attention, SE and devoxelisation read.
 #include "../../include/bdm_hip.h"
 #include "common.h"
+#include "gn_rule.h"
 
 using namespace bdm;
 #include "s3_split.h"
@@ -236,11 +237,7 @@ __global__ void to_s3_kernel(int C, int V, int G, int S, const float *__restrict
       double a = 0.0, q = 0.0;
       const size_t bg = (size_t)bi * G + threadIdx.x;
       for (int s = 0; s < S; ++s) { a += partial[(bg * S + s) * 2]; q += partial[(bg * S + s) * 2 + 1]; }
-      const double cnt = (double)cg * V, mean = a / cnt;
-      double var = q / cnt - mean * mean;
-      if (var < 0) var = 0;
-      s_mean[threadIdx.x] = (float)mean;
-      s_rstd[threadIdx.x] = (float)(1.0 / sqrt(var + (double)eps));
+      gn_mean_rstd(a, q, (double)cg * V, eps, s_mean[threadIdx.x], s_rstd[threadIdx.x]);
     }
     __syncthreads();
   }

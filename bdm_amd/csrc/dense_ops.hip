@@ -15,7 +15,9 @@
 
 #include "../../include/bdm_hip.h"
 #include "common.h"
+#include "gn_rule.h"
 #include "se_fc.h"
+#include "trilinear.h"
 
 using namespace bdm;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -67,17 +69,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void p
     }
     a = half32_sum(a); q = half32_sum(q);   // (the 32 lanes of this group: DPP, bit-identical to the xor butterfly)
     if (l == 0 && g < gn.in_G) {
-      const double cnt = (double)cgi * N, mean = a / cnt;
-      double var = q / cnt - mean * mean;
-      if (var < 0) var = 0;
-      s_mr[2 * g] = (float)mean;
-      s_mr[2 * g + 1] = (float)(1.0 / sqrt(var + (double)gn.in_eps));
+      gn_mean_rstd(a, q, (double)cgi * N, gn.in_eps, s_mr[2 * g], s_mr[2 * g + 1]);
     }
     __syncthreads();
     for (int k = tid; k < K; k += 256) {
       const int gk = k / cgi;
-      const float ak = gn.in_gamma[k] * s_mr[2 * gk + 1];
-      coef_s[k] = make_float2(ak, gn.in_beta[k] - s_mr[2 * gk] * ak);
+      coef_s[k] = gn_affine(gn.in_gamma[k], s_mr[2 * gk + 1], gn.in_beta[k], s_mr[2 * gk]);
     }
     // (visible to every wave after the first barrier of the K loop)
   }
@@ -342,7 +339,7 @@ __global__ __launch_bounds__(256) void pw_skinny_kernel(int M, int K, int N, con
   __shared__ float2 coef_s[FOLD ? 1024 : 1];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
   const int m0 = blockIdx.x * 32, bi = blockIdx.y, n0 = blockIdx.z * (32 * NB);  // wider shapes: one workgroup per 32 NB columns
-  if constexpr (FOLD) {  // same arithmetic as pw_gemm_kernel's prologue: the coefficients have the same bits
+  if constexpr (FOLD) {  // pw_gemm_kernel's prologue (finalisation and affine form: gn_rule.h): the coefficients have the same bits
     __shared__ float s_mr[16];
     const int g = tid >> 5, l = tid & 31, cgi = K / gn.in_G;
     double a = 0.0, q = 0.0;
@@ -352,17 +349,12 @@ __global__ __launch_bounds__(256) void pw_skinny_kernel(int M, int K, int N, con
     }
     a = half32_sum(a); q = half32_sum(q);   // (the 32 lanes of this group: DPP, bit-identical to the xor butterfly)
     if (l == 0 && g < gn.in_G) {
-      const double cnt = (double)cgi * N, mean = a / cnt;
-      double var = q / cnt - mean * mean;
-      if (var < 0) var = 0;
-      s_mr[2 * g] = (float)mean;
-      s_mr[2 * g + 1] = (float)(1.0 / sqrt(var + (double)gn.in_eps));
+      gn_mean_rstd(a, q, (double)cgi * N, gn.in_eps, s_mr[2 * g], s_mr[2 * g + 1]);
     }
     __syncthreads();
     for (int k = tid; k < K; k += 256) {
       const int gk = k / cgi;
-      const float ak = gn.in_gamma[k] * s_mr[2 * gk + 1];
-      coef_s[k] = make_float2(ak, gn.in_beta[k] - s_mr[2 * gk] * ak);
+      coef_s[k] = gn_affine(gn.in_gamma[k], s_mr[2 * gk + 1], gn.in_beta[k], s_mr[2 * gk]);
     }
     __syncthreads();
   }
@@ -736,11 +728,8 @@ __global__ void gn_apply_kernel(int cg, int L, const float *__restrict__ x, long
   const int bg = blockIdx.y, bi = bg / G, g = bg % G;
   double a = 0.0, q = 0.0;
   for (int s = 0; s < S; ++s) { a += partial[((size_t)bg * S + s) * 2]; q += partial[((size_t)bg * S + s) * 2 + 1]; }
-  const double cnt = (double)cg * L;
-  const double mean_d = a / cnt;
-  double var = q / cnt - mean_d * mean_d;
-  if (var < 0) var = 0;
-  const float mean = (float)mean_d, rstd = (float)(1.0 / sqrt(var + (double)eps));
+  float mean, rstd;
+  gn_mean_rstd(a, q, (double)cg * L, eps, mean, rstd);
   const float *xb = x + (size_t)bi * bs + (size_t)g * cg * ld;
   const float *rb = res ? res + (size_t)bi * bs_r + (size_t)g * cg * ld_r : nullptr;
   float *yb = y + (size_t)bi * bs_y + (size_t)g * cg * ld_y;
@@ -807,7 +796,7 @@ __global__ __launch_bounds__(1024) void gn_onepass_kernel(int cg, int L, const f
       q += (a * a + b * b) + (c * c + d * d);
     }
   }
-  const float rstd = (float)(1.0 / sqrt(block_sum((double)q, sh) / cnt + (double)eps));
+  const float rstd = gn_rstd(block_sum((double)q, sh) / cnt, eps);
   const int L4 = L / 4;
   const float inv_L4 = 1.0f / (float)L4;  // e / L4 as a float product: exact for e < 2^20 (an integer division is ~40 instructions)
 #pragma unroll
@@ -815,7 +804,8 @@ __global__ __launch_bounds__(1024) void gn_onepass_kernel(int cg, int L, const f
     const int e = threadIdx.x + i * 1024;
     if (e < n4) {
       const int ch = g * cg + (int)(((float)e + 0.5f) * inv_L4);
-      const float ga = gamma[ch] * rstd, be = beta[ch] - mean * ga;
+      const float2 ab = gn_affine(gamma[ch], rstd, beta[ch], mean);
+      const float ga = ab.x, be = ab.y;
       float4 o;
       o.x = v[i].x * ga + be; o.y = v[i].y * ga + be; o.z = v[i].z * ga + be; o.w = v[i].w * ga + be;
       if (act == 1) { o.x = swishf(o.x); o.y = swishf(o.y); o.z = swishf(o.z); o.w = swishf(o.w); }
@@ -854,11 +844,8 @@ __global__ void gn_apply_vec_kernel(int cg, int L, const float *__restrict__ x, 
   const int bg = blockIdx.y, bi = bg / G, g = bg % G;
   double a = 0.0, q = 0.0;
   for (int s = 0; s < S; ++s) { a += partial[((size_t)bg * S + s) * 2]; q += partial[((size_t)bg * S + s) * 2 + 1]; }
-  const double cnt = (double)cg * L;
-  const double mean_d = a / cnt;
-  double var = q / cnt - mean_d * mean_d;
-  if (var < 0) var = 0;
-  const float mean = (float)mean_d, rstd = (float)(1.0 / sqrt(var + (double)eps));
+  float mean, rstd;
+  gn_mean_rstd(a, q, (double)cg * L, eps, mean, rstd);
   const int n4 = cg * L / 4, L4 = L / 4;
   const float4 *xb = reinterpret_cast<const float4 *>(x + (size_t)bi * bs + (size_t)g * cg * L);
   const float4 *rb = res ? reinterpret_cast<const float4 *>(res + (size_t)bi * bs_r + (size_t)g * cg * L) : nullptr;
@@ -1007,10 +994,10 @@ __global__ void max_u_gn_kernel(int c, int m, int u, int lpr, int G, int S, cons
     double a = 0.0, q = 0.0;
     for (int sl = lane; sl < S; sl += 64) { a += pp[2 * sl]; q += pp[2 * sl + 1]; }
     a = wave_sum_bfly(a); q = wave_sum_bfly(q);   // (DPP + readlanes, bit-identical to the 64-lane xor butterfly)
-    const double cnt = (double)cg * m * u, mean = a / cnt;
-    double var = q / cnt - mean * mean;
-    if (var < 0) var = 0;
-    const float ca = gamma[ci] * (float)(1.0 / sqrt(var + (double)eps)), cb = beta[ci] - (float)mean * ca;
+    float mean, rstd;
+    gn_mean_rstd(a, q, (double)cg * m * u, eps, mean, rstd);
+    const float2 cab = gn_affine(gamma[ci], rstd, beta[ci], mean);
+    const float ca = cab.x, cb = cab.y;
     const float *xb = x + ((size_t)bi * c + ci) * m * u;
     if (lpr > 1) {
       for (int it = 0; it < lpr; ++it) {
@@ -1572,23 +1559,19 @@ __global__ void row_mean_gn_kernel(int c, int l, int G, int S, const float *__re
     double a = 0.0, q = 0.0;
     const double *p = pf.partial + ((size_t)bi * pf.G + gp) * pf.S * 2;
     for (int s = 0; s < pf.S; ++s) { a += p[2 * s]; q += p[2 * s + 1]; }
-    const double cnt = (double)cgp * pf.l, mu = a / cnt;
-    double var = q / cnt - mu * mu;
-    if (var < 0) var = 0;
-    const float ga = pf.gamma[ch] * (float)(1.0 / sqrt(var + (double)pf.eps));
-    pf_coef[row] = make_float2(ga, pf.beta[ch] - (float)mu * ga);
+    float mu, rstd;
+    gn_mean_rstd(a, q, (double)cgp * pf.l, pf.eps, mu, rstd);
+    pf_coef[row] = gn_affine(pf.gamma[ch], rstd, pf.beta[ch], mu);
   }
   if (threadIdx.x == 0) {
     double a = 0.0, q = 0.0;
     const double *p = partial + ((size_t)bi * G + g) * S * 2;
     for (int s = 0; s < S; ++s) { a += p[2 * s]; q += p[2 * s + 1]; }
-    const double cnt = (double)cg * l, mu = a / cnt;
-    double var = q / cnt - mu * mu;
-    if (var < 0) var = 0;
-    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float ga = gamma[ch] * rstd, be = beta[ch] - (float)mu * ga;
-    s_ab[0] = ga; s_ab[1] = be;
-    coef[row] = make_float2(ga, be);
+    float mu, rstd;
+    gn_mean_rstd(a, q, (double)cg * l, eps, mu, rstd);
+    const float2 ab = gn_affine(gamma[ch], rstd, beta[ch], mu);
+    s_ab[0] = ab.x; s_ab[1] = ab.y;
+    coef[row] = ab;
   }
   __syncthreads();
   const float ga = s_ab[0], be = s_ab[1];
@@ -1682,30 +1665,14 @@ __global__ void devox_gn_fused_kernel(int b, int cslots, int pblocks, int c, int
   if (i >= n) return;
   const int r2 = r * r, r3 = r2 * r;
   const float *pc = coords + (size_t)bi * 3 * n;
-  const float x = pc[i], y = pc[n + i], z = pc[2 * n + i];
-  const float xl = floorf(x), yl = floorf(y), zl = floorf(z);
-  const float x1 = x - xl, y1 = y - yl, z1 = z - zl;
-  const float x0 = 1.0f - x1, y0 = 1.0f - y1, z0 = 1.0f - z1;
-  const float w000 = x0 * y0 * z0, w001 = x0 * y0 * z1, w010 = x0 * y1 * z0, w011 = x0 * y1 * z1,
-              w100 = x1 * y0 * z0, w101 = x1 * y0 * z1, w110 = x1 * y1 * z0, w111 = x1 * y1 * z1;
-  const int sx = x1 > 0 ? r2 : 0, sy = y1 > 0 ? r : 0, sz = z1 > 0 ? 1 : 0;
-  const int i000 = (int)xl * r2 + (int)yl * r + (int)zl;
-  const int i001 = i000 + sz, i010 = i000 + sy, i011 = i010 + sz;
-  const int i100 = i000 + sx, i101 = i100 + sz, i110 = i100 + sy, i111 = i110 + sz;
+  const TrilinearCorners tc = trilinear_corners(pc[i], pc[n + i], pc[2 * n + i], r);
   for (int ci = c_first; ci < c; ci += cslots) {
     const float *g = grid + ((size_t)bi * c + ci) * r3;
     const float2 ab = coef[(size_t)bi * c + ci];
     float s = gate ? gate[(size_t)bi * c + ci] : 1.0f;
     if (se_mean != nullptr) s = se_gate_from_hidden(ci, hidden, w2, s_hid);
     // corners with weight 0 (frac == 0 on an axis) alias an in-grid cell: their value is finite and multiplies 0
-    float acc = w000 * (swishf(g[i000] * ab.x + ab.y) * s);
-    acc += w001 * (swishf(g[i001] * ab.x + ab.y) * s);
-    acc += w010 * (swishf(g[i010] * ab.x + ab.y) * s);
-    acc += w011 * (swishf(g[i011] * ab.x + ab.y) * s);
-    acc += w100 * (swishf(g[i100] * ab.x + ab.y) * s);
-    acc += w101 * (swishf(g[i101] * ab.x + ab.y) * s);
-    acc += w110 * (swishf(g[i110] * ab.x + ab.y) * s);
-    acc += w111 * (swishf(g[i111] * ab.x + ab.y) * s);
+    float acc = trilinear_sum_of(tc.w, [&](int k) { return gn_swish_gate(g[tc.i[k]], ab, s); });
     if (add) {
       float av = add[(size_t)bi * bs_a + (size_t)ci * ld_a + i];
       if (add_coef) {  // raw point-branch convolution output: its GroupNorm + Swish applied here
@@ -1721,8 +1688,8 @@ __global__ void devox_gn_fused_kernel(int b, int cslots, int pblocks, int c, int
 // LDS-cached form: one workgroup per (shape, `cpw` channels) first evaluates val[v] = swish(a grid[v] + b) * gate for the whole
 // channel grid into LDS (coalesced 16-byte reads, the transcendental once per CELL instead of once per (point, corner)), then
 // every point gathers its 8 corners from LDS.  The global-memory form above issues 8 scattered 4-byte loads per (point, channel)
-// and is bound by the texture-address unit (PMC: 57 % of its wave cycles are issue stalls).  Same expressions in the same
-// order: bit-identical output.
+// and is bound by the texture-address unit (PMC: 57 % of its wave cycles are issue stalls).  Cell value, corners and
+// sum are trilinear.h's in both forms: bit-identical output.
 __global__ __launch_bounds__(1024) void devox_gn_lds_kernel(int c, int n, int r, int cpw, const float *__restrict__ coords,
                                                             const float *__restrict__ grid, const float2 *__restrict__ coef,
                                                             const float *__restrict__ gate, const float *__restrict__ add,
@@ -1742,8 +1709,7 @@ __global__ __launch_bounds__(1024) void devox_gn_lds_kernel(int c, int n, int r,
       float4 *v4 = reinterpret_cast<float4 *>(vals + (size_t)cl * r3);
       for (int e = tid; e < r3 / 4; e += T) {
         const float4 g = g4[e];
-        v4[e] = make_float4(swishf(g.x * ab.x + ab.y) * s, swishf(g.y * ab.x + ab.y) * s, swishf(g.z * ab.x + ab.y) * s,
-                            swishf(g.w * ab.x + ab.y) * s);
+        v4[e] = gn_swish_gate(g, ab, s);
       }
     }
   }
@@ -1752,30 +1718,14 @@ __global__ __launch_bounds__(1024) void devox_gn_lds_kernel(int c, int n, int r,
 #pragma clang fp contract(off)
     const float *pc = coords + (size_t)bi * 3 * n;
     for (int i = tid; i < n; i += T) {
-      const float x = pc[i], y = pc[n + i], z = pc[2 * n + i];
-      const float xl = floorf(x), yl = floorf(y), zl = floorf(z);
-      const float x1 = x - xl, y1 = y - yl, z1 = z - zl;
-      const float x0 = 1.0f - x1, y0 = 1.0f - y1, z0 = 1.0f - z1;
-      const float w000 = x0 * y0 * z0, w001 = x0 * y0 * z1, w010 = x0 * y1 * z0, w011 = x0 * y1 * z1,
-                  w100 = x1 * y0 * z0, w101 = x1 * y0 * z1, w110 = x1 * y1 * z0, w111 = x1 * y1 * z1;
-      const int sx = x1 > 0 ? r2 : 0, sy = y1 > 0 ? r : 0, sz = z1 > 0 ? 1 : 0;
-      const int i000 = (int)xl * r2 + (int)yl * r + (int)zl;
-      const int i001 = i000 + sz, i010 = i000 + sy, i011 = i010 + sz;
-      const int i100 = i000 + sx, i101 = i100 + sz, i110 = i100 + sy, i111 = i110 + sz;
+      const TrilinearCorners tc = trilinear_corners(pc[i], pc[n + i], pc[2 * n + i], r);
       for (int cl = 0; cl < nc; ++cl) {
         const int ci = c0 + cl;
         const float *v = vals + (size_t)cl * r3;
         // corners with weight 0 (frac == 0 on an axis) alias an in-grid cell: their value is finite and multiplies 0
-        float cv[8] = {v[i000], v[i001], v[i010], v[i011], v[i100], v[i101], v[i110], v[i111]};
+        float cv[8] = {v[tc.i[0]], v[tc.i[1]], v[tc.i[2]], v[tc.i[3]], v[tc.i[4]], v[tc.i[5]], v[tc.i[6]], v[tc.i[7]]};
         lds_settle8(cv);  // all eight LDS reads have landed before the first use (common.h)
-        float acc = w000 * cv[0];
-        acc += w001 * cv[1];
-        acc += w010 * cv[2];
-        acc += w011 * cv[3];
-        acc += w100 * cv[4];
-        acc += w101 * cv[5];
-        acc += w110 * cv[6];
-        acc += w111 * cv[7];
+        float acc = trilinear_sum(tc.w, cv);
         if (add) {
           float av = add[(size_t)bi * bs_a + (size_t)ci * ld_a + i];
           if (add_coef) {
@@ -1857,7 +1807,7 @@ __global__ void devox_fused_kernel(int b, int cslots, int pblocks, int c, int n,
                                    const float *__restrict__ grid, const float *__restrict__ gate,
                                    const float *__restrict__ add, long long bs_a, int ld_a, float *__restrict__ out,
                                    long long bs_o, int ld_o) {
-#pragma clang fp contract(off)  // same unfused order as the stand-alone operator and the oracle
+#pragma clang fp contract(off)  // unfused, as the stand-alone operator and the oracle (corners and sum: trilinear.h)
   // XCD-aware 1-D launch: unit = (shape, channel slot); all point blocks of a unit get the same workgroup id mod 8, so the
   // unit's voxel rows (r^3 floats per channel) are pulled into ONE XCD's L2 instead of all eight
   const int span = 8 * pblocks, wg = blockIdx.x;
@@ -1868,27 +1818,11 @@ __global__ void devox_fused_kernel(int b, int cslots, int pblocks, int c, int n,
   if (i >= n) return;
   const int r2 = r * r, r3 = r2 * r;
   const float *pc = coords + (size_t)bi * 3 * n;
-  const float x = pc[i], y = pc[n + i], z = pc[2 * n + i];
-  const float xl = floorf(x), yl = floorf(y), zl = floorf(z);
-  const float x1 = x - xl, y1 = y - yl, z1 = z - zl;
-  const float x0 = 1.0f - x1, y0 = 1.0f - y1, z0 = 1.0f - z1;
-  const float w000 = x0 * y0 * z0, w001 = x0 * y0 * z1, w010 = x0 * y1 * z0, w011 = x0 * y1 * z1,
-              w100 = x1 * y0 * z0, w101 = x1 * y0 * z1, w110 = x1 * y1 * z0, w111 = x1 * y1 * z1;
-  const int sx = x1 > 0 ? r2 : 0, sy = y1 > 0 ? r : 0, sz = z1 > 0 ? 1 : 0;
-  const int i000 = (int)xl * r2 + (int)yl * r + (int)zl;
-  const int i001 = i000 + sz, i010 = i000 + sy, i011 = i010 + sz;
-  const int i100 = i000 + sx, i101 = i100 + sz, i110 = i100 + sy, i111 = i110 + sz;
+  const TrilinearCorners tc = trilinear_corners(pc[i], pc[n + i], pc[2 * n + i], r);
   for (int ci = c_first; ci < c; ci += cslots) {
     const float *g = grid + ((size_t)bi * c + ci) * r3;
     const float s = gate ? gate[(size_t)bi * c + ci] : 1.0f;
-    float acc = w000 * (g[i000] * s);
-    acc += w001 * (g[i001] * s);
-    acc += w010 * (g[i010] * s);
-    acc += w011 * (g[i011] * s);
-    acc += w100 * (g[i100] * s);
-    acc += w101 * (g[i101] * s);
-    acc += w110 * (g[i110] * s);
-    acc += w111 * (g[i111] * s);
+    float acc = trilinear_sum_of(tc.w, [&](int k) { return g[tc.i[k]] * s; });
     if (add) acc += add[(size_t)bi * bs_a + (size_t)ci * ld_a + i];
     out[(size_t)bi * bs_o + (size_t)ci * ld_o + i] = acc;
   }

@@ -25,6 +25,7 @@
 
 #include "../../../include/bdm_hip.h"
 #include "../common.h"
+#include "../gn_rule.h"
 #include "../pointwise_common.h"
 #include "../s3_split.h"
 
@@ -76,17 +77,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void p
 #pragma unroll
     for (int o = 1; o < 32; o <<= 1) { a += __shfl_xor(a, o, 64); q += __shfl_xor(q, o, 64); }
     if (l == 0 && g < gn.in_G) {
-      const double cnt = (double)cgi * N, mean = a / cnt;
-      double var = q / cnt - mean * mean;
-      if (var < 0) var = 0;
-      s_mr[2 * g] = (float)mean;
-      s_mr[2 * g + 1] = (float)(1.0 / sqrt(var + (double)gn.in_eps));
+      gn_mean_rstd(a, q, (double)cgi * N, gn.in_eps, s_mr[2 * g], s_mr[2 * g + 1]);
     }
     __syncthreads();
     for (int k = tid; k < K; k += 256) {
       const int gk = k / cgi;
-      const float ak = gn.in_gamma[k] * s_mr[2 * gk + 1];
-      coef_s[k] = make_float2(ak, gn.in_beta[k] - s_mr[2 * gk] * ak);
+      coef_s[k] = gn_affine(gn.in_gamma[k], s_mr[2 * gk + 1], gn.in_beta[k], s_mr[2 * gk]);
     }
     // (visible to every wave after the first barrier of the K loop)
   }

@@ -48,7 +48,7 @@ __global__ void sparse_fused_pack_kernel(int cout, int cin, const float *__restr
     for (int j = 0; j < 8; ++j) {
       const int ci = g * 8 + j;
       const float v = ci < cin ? w[((size_t)co * cin + ci) * 27 + tap] * scale[co] : 0.f;  // exact scaling
-      split2s(v, h[j], l[j]);
+      split2(v, h[j], l[j]);
     }
     unsigned short *ph = wq + ((((size_t)g * 27 + tap) * 2 + 0) * cout + co) * 8;
     unsigned short *pl = wq + ((((size_t)g * 27 + tap) * 2 + 1) * cout + co) * 8;
@@ -61,7 +61,7 @@ extern "C" int bdm_sparse_conv_fused_pack_weights(int cout, int cin, const float
                                                   float *inv_scale, void *stream) {
   BDM_REQUIRE(cout >= 1 && cin >= 1 && scale_ws != nullptr && inv_scale != nullptr, "sparse_conv_fused_pack_weights: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(sparse_fused_weight_scale_kernel, dim3(cout), dim3(256), 0, s, cout, cin, w, scale_ws, inv_scale);
+  h2_weight_scale(cout, cin, w, scale_ws, inv_scale, s);
   hipLaunchKernelGGL(sparse_fused_pack_kernel, dim3(512), dim3(256), 0, s, cout, cin, w, scale_ws, (unsigned short *)packed);
   return launch_status("sparse_conv_fused_pack_weights");
 }

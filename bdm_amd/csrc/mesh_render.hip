@@ -2,8 +2,8 @@
 // restates pytorch3d's MeshRasterizer at faces_per_pixel = 1, blur_radius = 0 and a Gouraud / flat shader; pytorch3d is not
 // installed, so the rule is this project's own text: "parity unpinned").
 //
-// The rule in one paragraph: vertices are projected in float32, operation by operation (no FMA contraction in this file, division
-// correctly rounded), and snapped to 1/256 pixel; coverage is decided by three int64 edge functions at the pixel centre with a
+// The rule in one paragraph: vertices are projected in float32, operation by operation (camera.h; no FMA contraction, and in this
+// file division correctly rounded), and snapped to 1/256 pixel; coverage is decided by three int64 edge functions at the pixel centre with a
 // half-plane rule for centres ON an edge; depth and barycentrics are float32 quotients of those integers; the pixel keeps the
 // smallest (bits of z) << 32 | face index.  Nothing depends on execution order: the only atomic is an integer minimum.
 //
@@ -23,6 +23,7 @@
 // The tile-binned form of render.hip (one workgroup per tile streams ALL faces) needs no atomics but reads an 88 000-face mesh
 // 196 times at 224 x 224; here every face is read once and costs its own box.
 #include "../../include/bdm_hip.h"
+#include "camera.h"
 #include "common.h"
 
 #include <limits.h>
@@ -69,20 +70,10 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_vertex_kernel(int b, int su
                                                                    const long long *__restrict__ vert_first, int4 *__restrict__ vrec) {
   const int i = blockIdx.x * MESH_THREADS + threadIdx.x;  // the grid covers sum_v < 2^31 exactly once
   if (i >= sum_v) return;
-  const float *c = cams + (size_t)mesh_of_row(vert_first, b, i) * 16;
+  const Camera c = load_camera(cams, (size_t)mesh_of_row(vert_first, b, i));
   const float *p = verts + (size_t)i * 3;
-  const float x = p[0], y = p[1], z = p[2];
-  const float xv = x * c[0] + y * c[3] + z * c[6] + c[9];
-  const float yv = x * c[1] + y * c[4] + z * c[7] + c[10];
-  const float zv = x * c[2] + y * c[5] + z * c[8] + c[11];
-  float u, v;
-  if (ortho) {
-    u = c[12] * xv + c[14];
-    v = c[13] * yv + c[15];
-  } else {
-    u = c[12] * xv / zv + c[14];
-    v = c[13] * yv / zv + c[15];
-  }
+  float u, v, zv;
+  project_point(c, p[0], p[1], p[2], ortho, u, v, zv);
   const float px = ((1.f - u) * half_w) * (float)MESH_SNAP, py = ((1.f - v) * half_h) * (float)MESH_SNAP;
   // NaN fails every comparison; fabsf(inf) <= 2^22 is false
   const bool usable = zv > 0.f && zv < INFINITY && fabsf(px) <= MESH_GUARD && fabsf(py) <= MESH_GUARD;

@@ -16,6 +16,7 @@
 
 #include "../../include/bdm_hip.h"
 #include "common.h"
+#include "trilinear.h"
 
 // The whole file is compiled without multiply-add contraction (also -ffp-contract=off in the
 // Makefile): __fmul_rn/__fadd_rn are plain '*' and '+' in ROCm's headers and would otherwise
@@ -1106,29 +1107,10 @@ __global__ void devox_kernel(int c, int n, int r, const float *__restrict__ coor
   if (i >= n) return;
   const int r2 = r * r, r3 = r2 * r;
   const float *pc = coords + (size_t)bi * 3 * n;
-  const float x = pc[i], y = pc[n + i], z = pc[2 * n + i];
-  const float xl = floorf(x), yl = floorf(y), zl = floorf(z);
-  const float x1 = x - xl, y1 = y - yl, z1 = z - zl;
-  const float x0 = 1.0f - x1, y0 = 1.0f - y1, z0 = 1.0f - z1;
-  const float x0y0 = __fmul_rn(x0, y0), x0y1 = __fmul_rn(x0, y1), x1y0 = __fmul_rn(x1, y0), x1y1 = __fmul_rn(x1, y1);
-  const float w000 = __fmul_rn(x0y0, z0), w001 = __fmul_rn(x0y0, z1), w010 = __fmul_rn(x0y1, z0),
-              w011 = __fmul_rn(x0y1, z1), w100 = __fmul_rn(x1y0, z0), w101 = __fmul_rn(x1y0, z1),
-              w110 = __fmul_rn(x1y1, z0), w111 = __fmul_rn(x1y1, z1);
-  const int sx = x1 > 0 ? r2 : 0, sy = y1 > 0 ? r : 0, sz = z1 > 0 ? 1 : 0;
-  const int i000 = (int)xl * r2 + (int)yl * r + (int)zl;
-  const int i001 = i000 + sz, i010 = i000 + sy, i011 = i010 + sz;
-  const int i100 = i000 + sx, i101 = i100 + sz, i110 = i100 + sy, i111 = i110 + sz;
+  const TrilinearCorners tc = trilinear_corners(pc[i], pc[n + i], pc[2 * n + i], r);
   for (int ci = blockIdx.y; ci < c; ci += gridDim.y) {
     const float *g = grid + ((size_t)bi * c + ci) * r3;
-    float acc = __fmul_rn(w000, g[i000]);
-    acc = __fadd_rn(acc, __fmul_rn(w001, g[i001]));
-    acc = __fadd_rn(acc, __fmul_rn(w010, g[i010]));
-    acc = __fadd_rn(acc, __fmul_rn(w011, g[i011]));
-    acc = __fadd_rn(acc, __fmul_rn(w100, g[i100]));
-    acc = __fadd_rn(acc, __fmul_rn(w101, g[i101]));
-    acc = __fadd_rn(acc, __fmul_rn(w110, g[i110]));
-    acc = __fadd_rn(acc, __fmul_rn(w111, g[i111]));
-    out[((size_t)bi * c + ci) * n + i] = acc;
+    out[((size_t)bi * c + ci) * n + i] = trilinear_sum_of(tc.w, [&](int k) { return g[tc.i[k]]; });
   }
 }
 

@@ -19,29 +19,16 @@
 
 #include "../../include/bdm_hip.h"
 #include "common.h"
+#include "gn_rule.h"
+#include "h2_split.h"
 #include "se_fc.h"
+#include "trilinear.h"
 
 using namespace bdm;
 
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 
 namespace {
-
-__device__ __forceinline__ void split2c(float v, unsigned short &h, unsigned short &l) {
-  v = fminf(fmaxf(v, -65504.f), 65504.f);
-  const _Float16 hi = (_Float16)v;
-  const _Float16 lo = (_Float16)(v - (float)hi);
-  h = __builtin_bit_cast(unsigned short, hi);
-  l = __builtin_bit_cast(unsigned short, lo);
-}
-
-__device__ __forceinline__ void split_rec(const float v[8], uint4 &ph, uint4 &pl) {
-  unsigned short h[8], l[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) split2c(v[j], h[j], l[j]);
-  ph.x = h[0] | (h[1] << 16); ph.y = h[2] | (h[3] << 16); ph.z = h[4] | (h[5] << 16); ph.w = h[6] | (h[7] << 16);
-  pl.x = l[0] | (l[1] << 16); pl.y = l[2] | (l[3] << 16); pl.z = l[4] | (l[5] << 16); pl.w = l[6] | (l[7] << 16);
-}
 
 // mean / rstd of ALL G <= 64 groups of shape `bi` at once: 32 lanes per group add slices l, l + 32, ... and butterfly (a fixed order);
 // 256 threads take 8 groups per round.  Results in s_mean / s_rstd (valid after the call's trailing barrier).
@@ -56,13 +43,7 @@ __device__ __forceinline__ void all_group_stats(const double *__restrict__ parti
       for (int sl = l; sl < S; sl += 32) { a += pp[2 * sl]; q += pp[2 * sl + 1]; }
     }
     a = half32_sum(a); q = half32_sum(q);   // (DPP row sums + readlanes: bit-identical to the xor butterfly over the group's 32 lanes)
-    if (l == 0 && g < G) {
-      const double mu = a / count;
-      double var = q / count - mu * mu;
-      if (var < 0) var = 0;
-      s_mean[g] = (float)mu;
-      s_rstd[g] = (float)(1.0 / sqrt(var + (double)eps));
-    }
+    if (l == 0 && g < G) gn_mean_rstd(a, q, count, eps, s_mean[g], s_rstd[g]);
   }
   __syncthreads();
 }
@@ -145,7 +126,7 @@ __global__ __launch_bounds__(256) void to_h2_rows_kernel(int C, int V, int G, in
       sat |= !(fabsf(fill[j]) <= 65504.f);
     }
     uint4 ph, pl;
-    split_rec(fill, ph, pl);
+    split2_record(fill, ph, pl);
     const_h2[((size_t)bi * C8 + c8) * 2 + 0] = ph;
     const_h2[((size_t)bi * C8 + c8) * 2 + 1] = pl;
     const f16x8 hh = *reinterpret_cast<const f16x8 *>(&ph), ll = *reinterpret_cast<const f16x8 *>(&pl);
@@ -165,7 +146,7 @@ __global__ __launch_bounds__(256) void to_h2_rows_kernel(int C, int V, int G, in
         sat |= !(fabsf(val[u]) <= 65504.f);
       }
       uint4 ph, pl;
-      split_rec(val, ph, pl);
+      split2_record(val, ph, pl);
       rows_h2[(((size_t)bi * C8 + c8) * 2 + 0) * n_rows_max + j] = ph;
       rows_h2[(((size_t)bi * C8 + c8) * 2 + 1) * n_rows_max + j] = pl;
     };
@@ -198,11 +179,7 @@ extern "C" int bdm_group_norm_to_h2_rows(int b, int c, int v, int groups, const 
                   partial != nullptr && slices >= 1 && x != nullptr && dil_list != nullptr && tile_start != nullptr && tiles_max >= 1 &&
                   n_rows_max >= 1 && rows_h2 && const_h2 && const_f32,
               "group_norm_to_h2_rows: bad arguments (<= 256 channels)");
-  {
-    int ex = 0;
-    BDM_REQUIRE(act_scale > 0.f && act_scale < INFINITY && frexpf(act_scale, &ex) == 0.5f,
-                "group_norm_to_h2_rows: act_scale must be a power of two (got %g)", (double)act_scale);
-  }
+  BDM_REQUIRE(h2_scale_is_pow2(act_scale), "group_norm_to_h2_rows: act_scale must be a power of two (got %g)", (double)act_scale);
   if (b == 0) return BDM_OK;
   dim3 grid(cdiv(n_rows_max, 512), b);
   hipLaunchKernelGGL(to_h2_rows_kernel, grid, dim3(256), 0, (hipStream_t)stream, c, v, groups, slices, n_rows_max, tiles_max, dense_in, x,
@@ -306,9 +283,9 @@ __global__ __launch_bounds__(256) void se_rows_partial_kernel(int c, int V, int 
   const int cg = c / G;
   all_group_stats(partial, bi, G, S, (double)cg * V, eps, s_mean, s_rstd);
   for (int ch = tid; ch < c; ch += blockDim.x) {
-    const float ga = gamma[ch] * s_rstd[ch / cg];
-    s_a[ch] = ga;
-    s_b[ch] = beta[ch] - s_mean[ch / cg] * ga;
+    const float2 ab = gn_affine(gamma[ch], s_rstd[ch / cg], beta[ch], s_mean[ch / cg]);
+    s_a[ch] = ab.x;
+    s_b[ch] = ab.y;
   }
   __syncthreads();
   if (slab == 0) {
@@ -320,11 +297,9 @@ __global__ __launch_bounds__(256) void se_rows_partial_kernel(int c, int V, int 
         double a = 0.0, q = 0.0;
         const double *p = pf.partial + ((size_t)bi * pf.G + gp) * pf.S * 2;
         for (int s = 0; s < pf.S; ++s) { a += p[2 * s]; q += p[2 * s + 1]; }
-        const double cnt = (double)cgp * pf.l, mu = a / cnt;
-        double var = q / cnt - mu * mu;
-        if (var < 0) var = 0;
-        const float ga = pf.gamma[ch] * (float)(1.0 / sqrt(var + (double)pf.eps));
-        pf_coef[(size_t)bi * c + ch] = make_float2(ga, pf.beta[ch] - (float)mu * ga);
+        float mu, rstd;
+        gn_mean_rstd(a, q, (double)cgp * pf.l, pf.eps, mu, rstd);
+        pf_coef[(size_t)bi * c + ch] = gn_affine(pf.gamma[ch], rstd, pf.beta[ch], mu);
       }
     }
   }
@@ -465,17 +440,9 @@ __global__ __launch_bounds__(256) void devox_rows_kernel(int c, int n, int r, in
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     const int i = min(p0 + t * 16 + ps, n - 1);
-    const float x = pc[i], y = pc[n + i], z = pc[2 * n + i];
-    const float xl = floorf(x), yl = floorf(y), zl = floorf(z);
-    const float x1 = x - xl, y1 = y - yl, z1 = z - zl;
-    const float x0 = 1.0f - x1, y0 = 1.0f - y1, z0 = 1.0f - z1;
-    w8[t][0] = x0 * y0 * z0; w8[t][1] = x0 * y0 * z1; w8[t][2] = x0 * y1 * z0; w8[t][3] = x0 * y1 * z1;
-    w8[t][4] = x1 * y0 * z0; w8[t][5] = x1 * y0 * z1; w8[t][6] = x1 * y1 * z0; w8[t][7] = x1 * y1 * z1;
-    const int sx = x1 > 0 ? r2 : 0, sy = y1 > 0 ? r : 0, sz = z1 > 0 ? 1 : 0;
-    const int i000 = (int)xl * r2 + (int)yl * r + (int)zl;
-    const int idx[8] = {i000, i000 + sz, i000 + sy, i000 + sy + sz, i000 + sx, i000 + sx + sz, i000 + sx + sy, i000 + sx + sy + sz};
+    const TrilinearCorners tc = trilinear_corners(pc[i], pc[n + i], pc[2 * n + i], r);
 #pragma unroll
-    for (int q = 0; q < 8; ++q) j8[t][q] = di[idx[q]];
+    for (int q = 0; q < 8; ++q) { w8[t][q] = tc.w[q]; j8[t][q] = di[tc.i[q]]; }
   }
   for (int c0 = 0; c0 < c; c0 += 64) {
     const int ch = c0 + 4 * l16;
@@ -498,11 +465,11 @@ __global__ __launch_bounds__(256) void devox_rows_kernel(int c, int n, int r, in
           const float4 g = j >= 0 ? *reinterpret_cast<const float4 *>(rb + (size_t)j * c + ch) : *reinterpret_cast<const float4 *>(cv + ch);
           const float wq = w8[t][q];
           if (q == 0) {
-            acc.x = wq * (swishf(g.x * ga.x + gb.x) * gs.x); acc.y = wq * (swishf(g.y * ga.y + gb.y) * gs.y);
-            acc.z = wq * (swishf(g.z * ga.z + gb.z) * gs.z); acc.w = wq * (swishf(g.w * ga.w + gb.w) * gs.w);
+            acc.x = wq * gn_swish_gate(g.x, ga.x, gb.x, gs.x); acc.y = wq * gn_swish_gate(g.y, ga.y, gb.y, gs.y);
+            acc.z = wq * gn_swish_gate(g.z, ga.z, gb.z, gs.z); acc.w = wq * gn_swish_gate(g.w, ga.w, gb.w, gs.w);
           } else {
-            acc.x += wq * (swishf(g.x * ga.x + gb.x) * gs.x); acc.y += wq * (swishf(g.y * ga.y + gb.y) * gs.y);
-            acc.z += wq * (swishf(g.z * ga.z + gb.z) * gs.z); acc.w += wq * (swishf(g.w * ga.w + gb.w) * gs.w);
+            acc.x += wq * gn_swish_gate(g.x, ga.x, gb.x, gs.x); acc.y += wq * gn_swish_gate(g.y, ga.y, gb.y, gs.y);
+            acc.z += wq * gn_swish_gate(g.z, ga.z, gb.z, gs.z); acc.w += wq * gn_swish_gate(g.w, ga.w, gb.w, gs.w);
           }
         }
       }

@@ -25,6 +25,7 @@
 #include "../../include/bdm_hip.h"
 #include "common.h"
 #include "se_fc.h"
+#include "trilinear.h"
 
 using namespace bdm;
 
@@ -67,7 +68,7 @@ __global__ __launch_bounds__(TAIL_T) void pv_tail_small_kernel(int c, int n, int
   __syncthreads();
   {
 #pragma clang fp contract(off)
-    // ---- per cell: GroupNorm-2 + Swish + gate, once (devox_gn_lds_kernel's expression) ------------------------------------------
+    // ---- per cell: GroupNorm-2 + Swish + gate, once (gn_swish_gate, trilinear.h) ----------------------------------------------
     for (int cl = 0; cl < TAIL_CS; ++cl) {
       const int ci = c0 + cl;
       const float2 ab = coef[(size_t)bi * c + ci];
@@ -76,8 +77,7 @@ __global__ __launch_bounds__(TAIL_T) void pv_tail_small_kernel(int c, int n, int
       float4 *v4 = reinterpret_cast<float4 *>(vals + (size_t)cl * r3);
       for (int e = tid; e < r3 / 4; e += TAIL_T) {
         const float4 g = g4[e];
-        v4[e] = make_float4(swishf(g.x * ab.x + ab.y) * s, swishf(g.y * ab.x + ab.y) * s, swishf(g.z * ab.x + ab.y) * s,
-                            swishf(g.w * ab.x + ab.y) * s);
+        v4[e] = gn_swish_gate(g, ab, s);
       }
     }
   }
@@ -88,27 +88,11 @@ __global__ __launch_bounds__(TAIL_T) void pv_tail_small_kernel(int c, int n, int
     const float *pc = coords + (size_t)bi * 3 * n;
     for (int item = tid; item < n * TAIL_CS; item += TAIL_T) {
       const int cl = item / n, i = item - cl * n, ci = c0 + cl;
-      const float x = pc[i], y = pc[n + i], z = pc[2 * n + i];
-      const float xl = floorf(x), yl = floorf(y), zl = floorf(z);
-      const float x1 = x - xl, y1 = y - yl, z1 = z - zl;
-      const float x0 = 1.0f - x1, y0 = 1.0f - y1, z0 = 1.0f - z1;
-      const float w000 = x0 * y0 * z0, w001 = x0 * y0 * z1, w010 = x0 * y1 * z0, w011 = x0 * y1 * z1,
-                  w100 = x1 * y0 * z0, w101 = x1 * y0 * z1, w110 = x1 * y1 * z0, w111 = x1 * y1 * z1;
-      const int sx = x1 > 0 ? r2 : 0, sy = y1 > 0 ? r : 0, sz = z1 > 0 ? 1 : 0;
-      const int i000 = (int)xl * r2 + (int)yl * r + (int)zl;
-      const int i001 = i000 + sz, i010 = i000 + sy, i011 = i010 + sz;
-      const int i100 = i000 + sx, i101 = i100 + sz, i110 = i100 + sy, i111 = i110 + sz;
+      const TrilinearCorners tc = trilinear_corners(pc[i], pc[n + i], pc[2 * n + i], r);
       const float *v = vals + (size_t)cl * r3;
-      float cv[8] = {v[i000], v[i001], v[i010], v[i011], v[i100], v[i101], v[i110], v[i111]};
+      float cv[8] = {v[tc.i[0]], v[tc.i[1]], v[tc.i[2]], v[tc.i[3]], v[tc.i[4]], v[tc.i[5]], v[tc.i[6]], v[tc.i[7]]};
       lds_settle8(cv);
-      float acc = w000 * cv[0];
-      acc += w001 * cv[1];
-      acc += w010 * cv[2];
-      acc += w011 * cv[3];
-      acc += w100 * cv[4];
-      acc += w101 * cv[5];
-      acc += w110 * cv[6];
-      acc += w111 * cv[7];
+      float acc = trilinear_sum(tc.w, cv);
       if (add) {
         float av = add[(size_t)bi * bs_a + (size_t)ci * ld_a + i];
         if (add_coef) {
@@ -267,39 +251,22 @@ __global__ __launch_bounds__(TAIL_T) void pv_tail_small_fast_kernel(int c, int n
         const float s = s_gate[ccl[it]];
         const float4 g = cell[it];
         const float2 ab = cab[it];
-        reinterpret_cast<float4 *>(vals + (size_t)ccl[it] * r3)[ce[it]] =
-            make_float4(swishf(g.x * ab.x + ab.y) * s, swishf(g.y * ab.x + ab.y) * s, swishf(g.z * ab.x + ab.y) * s, swishf(g.w * ab.x + ab.y) * s);
+        reinterpret_cast<float4 *>(vals + (size_t)ccl[it] * r3)[ce[it]] = gn_swish_gate(g, ab, s);
       }
     }
   }
   __syncthreads();
   {
 #pragma clang fp contract(off)
-    const float x = px, y = py, z = pz;
-    const float xl = floorf(x), yl = floorf(y), zl = floorf(z);
-    const float x1 = x - xl, y1 = y - yl, z1 = z - zl;
-    const float x0 = 1.0f - x1, y0 = 1.0f - y1, z0 = 1.0f - z1;
-    const float w000 = x0 * y0 * z0, w001 = x0 * y0 * z1, w010 = x0 * y1 * z0, w011 = x0 * y1 * z1,
-                w100 = x1 * y0 * z0, w101 = x1 * y0 * z1, w110 = x1 * y1 * z0, w111 = x1 * y1 * z1;
-    const int sx = x1 > 0 ? r2 : 0, sy = y1 > 0 ? r : 0, sz = z1 > 0 ? 1 : 0;
-    const int i000 = (int)xl * r2 + (int)yl * r + (int)zl;
-    const int i001 = i000 + sz, i010 = i000 + sy, i011 = i010 + sz;
-    const int i100 = i000 + sx, i101 = i100 + sz, i110 = i100 + sy, i111 = i110 + sz;
+    const TrilinearCorners tc = trilinear_corners(px, py, pz, r);
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int cl = cln + u * CL;
       if (cl < TAIL_CS && pok) {
         const float *v = vals + (size_t)cl * r3;
-        float cv[8] = {v[i000], v[i001], v[i010], v[i011], v[i100], v[i101], v[i110], v[i111]};
+        float cv[8] = {v[tc.i[0]], v[tc.i[1]], v[tc.i[2]], v[tc.i[3]], v[tc.i[4]], v[tc.i[5]], v[tc.i[6]], v[tc.i[7]]};
         lds_settle8(cv);
-        float acc = w000 * cv[0];
-        acc += w001 * cv[1];
-        acc += w010 * cv[2];
-        acc += w011 * cv[3];
-        acc += w100 * cv[4];
-        acc += w101 * cv[5];
-        acc += w110 * cv[6];
-        acc += w111 * cv[7];
+        float acc = trilinear_sum(tc.w, cv);
         if (add) {
           float a2 = av[u];
           if (add_coef) a2 = swishf(a2 * apf[u].x + apf[u].y);

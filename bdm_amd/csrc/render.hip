@@ -2,9 +2,8 @@
 // (the reference renders with pytorch3d: experiments/diffusion_utils.py:185-295, PointsRasterizer + NormWeightedCompositor /
 // AlphaCompositor; pytorch3d is a third-party dependency that is not installed here, so its rules are restated: "parity unpinned").
 //
-// Projection and pixel centres are those of sampler_ops.hip, in the same arithmetic (no FMA contraction in this file):
-//   X_view = X_world R + T;  perspective ndc = focal * X_view.xy / X_view.z + pp;  orthographic ndc = focal * X_view.xy + pp;
-//   pixel (yi, xi) has its centre at ndc (x, y) = (1 - (2 xi + 1)/W, 1 - (2 yi + 1)/H)   (+X left, +Y up).
+// Projection and pixel centres are camera.h's, the one definition sampler_ops.hip and mesh_render.hip use as well (no FMA
+// contraction there, none in this file).
 // For H != W this is the per-axis convention of this project (each axis spans [-1, 1]); pytorch3d scales the longer axis by the
 // aspect ratio instead -- a documented departure.
 // Selection: point p is a candidate of a pixel when dx*dx + dy*dy < radius*radius (float32 product) and z >= 0 (NaN and
@@ -26,6 +25,7 @@
 // of the shape (16384 points = 64 loads per thread), which is why the count / scan / fill binning passes are not worth having at
 // these sizes.
 #include "../../include/bdm_hip.h"
+#include "camera.h"
 #include "common.h"
 
 #include <limits.h>
@@ -45,20 +45,10 @@ using namespace bdm;
 __global__ void render_project_kernel(long long total, int ortho, const float *__restrict__ pts, const float *__restrict__ cams,
                                       int n, float4 *__restrict__ proj) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    const float *c = cams + (size_t)(i / n) * 16;
+    const Camera c = load_camera(cams, (size_t)(i / n));
     const float *p = pts + (size_t)i * 3;
-    const float x = p[0], y = p[1], z = p[2];
-    const float xv = x * c[0] + y * c[3] + z * c[6] + c[9];
-    const float yv = x * c[1] + y * c[4] + z * c[7] + c[10];
-    const float zv = x * c[2] + y * c[5] + z * c[8] + c[11];
-    float u, v;
-    if (ortho) {
-      u = c[12] * xv + c[14];
-      v = c[13] * yv + c[15];
-    } else {
-      u = c[12] * xv / zv + c[14];
-      v = c[13] * yv / zv + c[15];
-    }
+    float u, v, zv;
+    project_point(c, p[0], p[1], p[2], ortho, u, v, zv);
     proj[i] = make_float4(u, v, zv, 0.f);
   }
 }
@@ -90,11 +80,11 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_tile_kernel(int n, int 
   const int x0 = (tile % tiles_x) * RENDER_TILE, y0 = (tile / tiles_x) * RENDER_TILE;
   const int xi = x0 + (tid & (RENDER_TILE - 1)), yi = y0 + (tid / RENDER_TILE);
   const bool inside = xi < W && yi < H;
-  const float xf = 1.f - (2.f * xi + 1.f) / W, yf = 1.f - (2.f * yi + 1.f) / H;
+  const float xf = pixel_centre(xi, W), yf = pixel_centre(yi, H);
   // NDC centres of the tile's first and last pixel inside the image, per axis
   const int x1 = min(x0 + RENDER_TILE, W) - 1, y1 = min(y0 + RENDER_TILE, H) - 1;
-  const float tx0 = 1.f - (2.f * x0 + 1.f) / W, tx1 = 1.f - (2.f * x1 + 1.f) / W;
-  const float ty0 = 1.f - (2.f * y0 + 1.f) / H, ty1 = 1.f - (2.f * y1 + 1.f) / H;
+  const float tx0 = pixel_centre(x0, W), tx1 = pixel_centre(x1, W);
+  const float ty0 = pixel_centre(y0, H), ty1 = pixel_centre(y1, H);
 
   float kz[K], kd[K];
   int ki[K];

@@ -16,6 +16,7 @@
 
 #include "../../include/bdm_hip.h"
 #include "common.h"
+#include "gn_rule.h"
 
 using namespace bdm;
 
@@ -49,13 +50,7 @@ __device__ __forceinline__ void group_stats8(const double *__restrict__ partial,
     for (int i = 0; i + span < 8; i += 2 * span) { va[i] += va[i + span]; vq[i] += vq[i + span]; }
   double a = va[0], q = vq[0];
   a = half32_sum(a); q = half32_sum(q);   // (bit-identical to the xor butterfly over the group's 32 lanes)
-  if (l == 0 && g < G) {
-    const double mu = a / count;
-    double var = q / count - mu * mu;
-    if (var < 0) var = 0;
-    s_mean[g] = (float)mu;
-    s_rstd[g] = (float)(1.0 / sqrt(var + (double)eps));
-  }
+  if (l == 0 && g < G) gn_mean_rstd(a, q, count, eps, s_mean[g], s_rstd[g]);
   __syncthreads();
 }
 

@@ -7,6 +7,7 @@
 //                         (model/projection_model.py:127-157,179-231; pytorch3d PointsRasterizer)
 // Elementwise arithmetic mirrors torch's op-by-op rounding (no FMA contraction in this file).
 #include "../../include/bdm_hip.h"
+#include "camera.h"
 #include "common.h"
 
 #pragma clang fp contract(off)
@@ -159,34 +160,13 @@ extern "C" int bdm_blend_select(long long num_points, const float *recon, const 
 // -------------------------------------------------------------------------------------
 // Projection conditioning
 // -------------------------------------------------------------------------------------
-// Points are projected with a PerspectiveCameras model (row-vector convention:
-// X_view = X_world R + T; ndc = focal * X_view.xy / X_view.z + principal_point) and rasterised
-// with the naive PointsRasterizer rule: pixel (yi, xi) has its centre at
-// ndc (x, y) = (1 - (2 xi + 1)/W, 1 - (2 yi + 1)/H)  (+X left, +Y up); a point covers the pixel
+// Points are projected with a PerspectiveCameras model and rasterised with the naive PointsRasterizer rule
+// (projection and pixel centres: camera.h); a point covers the pixel
 // when dx^2 + dy^2 < radius^2 and z >= 0; the pixel keeps the point with the smallest z
 // (earliest index on ties).  A point then takes the feature vector of the LAST pixel (row-major)
 // it owns -- the sequential semantics of the reference's duplicate-index assignment
 // (projection_model.py:152-153); points that own no pixel get zeros.
-struct Cam { float r[9]; float t[3]; float f[2]; float p[2]; };
 
-__device__ __forceinline__ void project(const Cam &c, float x, float y, float z, float &u, float &v, float &d) {
-  const float xv = x * c.r[0] + y * c.r[3] + z * c.r[6] + c.t[0];
-  const float yv = x * c.r[1] + y * c.r[4] + z * c.r[7] + c.t[1];
-  const float zv = x * c.r[2] + y * c.r[5] + z * c.r[8] + c.t[2];
-  u = c.f[0] * xv / zv + c.p[0];
-  v = c.f[1] * yv / zv + c.p[1];
-  d = zv;
-}
-__device__ __forceinline__ Cam load_cam(const float *cams, int bi) {
-  Cam c;
-  const float *p = cams + (size_t)bi * 16;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) c.r[i] = p[i];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) c.t[i] = p[9 + i];
-  c.f[0] = p[12]; c.f[1] = p[13]; c.p[0] = p[14]; c.p[1] = p[15];
-  return c;
-}
 // nearest pixel index of an NDC coordinate, clamped in FLOAT to [-4, size+4] before the conversion: points that project
 // far outside the image (or at infinity, z -> 0+) would otherwise overflow the int conversion and the window loops
 __device__ __forceinline__ int nearest_pixel(float ndc, int size) {
@@ -204,10 +184,10 @@ __global__ void raster_splat_kernel(int n, int H, int W, float radius2, const fl
                                     const float *__restrict__ cams, unsigned long long *__restrict__ zbuf) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x, bi = blockIdx.y;
   if (i >= n) return;
-  const Cam c = load_cam(cams, bi);
+  const Camera c = load_camera(cams, bi);
   const float *p = pts + ((size_t)bi * n + i) * 3;
   float u, v, d;
-  project(c, p[0], p[1], p[2], u, v, d);
+  project_point(c, p[0], p[1], p[2], 0, u, v, d);
   if (!(d >= 0.f)) return;  // behind the camera (or NaN)
   // nearest pixel column/row:  u = 1 - (2 xi + 1)/W  ->  xi = ((1 - u) W - 1) / 2
   const int xc = nearest_pixel(u, W), yc = nearest_pixel(v, H);
@@ -215,11 +195,11 @@ __global__ void raster_splat_kernel(int n, int H, int W, float radius2, const fl
   const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)i;
   for (int yi = yc - RAST_WIN; yi <= yc + RAST_WIN; ++yi) {
     if (yi < 0 || yi >= H) continue;
-    const float yf = 1.f - (2.f * yi + 1.f) / H;
+    const float yf = pixel_centre(yi, H);
     const float dy = yf - v;
     for (int xi = xc - RAST_WIN; xi <= xc + RAST_WIN; ++xi) {
       if (xi < 0 || xi >= W) continue;
-      const float xf = 1.f - (2.f * xi + 1.f) / W;
+      const float xf = pixel_centre(xi, W);
       const float dx = xf - u;
       if (dx * dx + dy * dy < radius2) atomicMin(&zb[(size_t)yi * W + xi], key);
     }
@@ -231,10 +211,10 @@ __global__ void raster_owner_kernel(int n, int H, int W, float radius2, const fl
                                     int *__restrict__ pix_of_point) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x, bi = blockIdx.y;
   if (i >= n) return;
-  const Cam c = load_cam(cams, bi);
+  const Camera c = load_camera(cams, bi);
   const float *p = pts + ((size_t)bi * n + i) * 3;
   float u, v, d;
-  project(c, p[0], p[1], p[2], u, v, d);
+  project_point(c, p[0], p[1], p[2], 0, u, v, d);
   int owner = -1;
   if (d >= 0.f) {
     const int xc = nearest_pixel(u, W), yc = nearest_pixel(v, H);

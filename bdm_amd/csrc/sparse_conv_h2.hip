@@ -110,7 +110,7 @@ __global__ void sparse_gemm_h2_pack_kernel(int cout, int cin, const float *__res
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int ci = g * 8 + j;
-      split2s(ci < cin ? w[((size_t)co * cin + ci) * 27 + tap] * scale[co] : 0.f, h[j], l[j]);
+      split2(ci < cin ? w[((size_t)co * cin + ci) * 27 + tap] * scale[co] : 0.f, h[j], l[j]);
     }
     unsigned short *ph = wq + (((size_t)g * 2 + 0) * n27 + col) * 8, *pl = wq + (((size_t)g * 2 + 1) * n27 + col) * 8;
 #pragma unroll
@@ -122,7 +122,7 @@ extern "C" int bdm_sparse_conv_pack_weights_h2(int cout, int cin, const float *w
                                                float *inv_scale, void *stream) {
   BDM_REQUIRE(cout >= 1 && cin >= 1 && scale_ws != nullptr && inv_scale != nullptr, "sparse_conv_pack_weights_h2: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(sparse_fused_weight_scale_kernel, dim3(cout), dim3(256), 0, s, cout, cin, w, scale_ws, inv_scale);
+  h2_weight_scale(cout, cin, w, scale_ws, inv_scale, s);
   hipLaunchKernelGGL(sparse_gemm_h2_pack_kernel, dim3(512), dim3(256), 0, s, cout, cin, w, scale_ws, (unsigned short *)packed);
   return launch_status("sparse_conv_pack_weights_h2");
 }
