@@ -1,0 +1,512 @@
+// mesh_metrics.hip -- scoring triangle meshes: area-weighted surface samples and the squared distance from points to the nearest
+// face, as gfx950 kernels (bdm_hip.h section 14; restates pytorch3d's sample_points_from_meshes and the
+// point-to-face half of point_mesh_face_distance; pytorch3d is not installed, so the rule is this project's own text).
+//
+// The rule in one paragraph: everything a face contributes (edges, normal n, nn = n . n, squared edge lengths) is float32, rounded
+// operation by operation.  The sampler turns the doubled areas sqrt(nn) into integers q_i = rint(a_i / amax * 2^30), scans them in
+// int64 and picks the face of a sample by the high half of (64 random bits) x (total); the distance is the minimum over the faces
+// of min(three segment distances, plane distance if the point projects inside), the lowest face index winning ties.  Nothing
+// depends on execution order: the sums are integers, the only atomic is an integer maximum.
+//
+// Kernels.
+//   mm_offsets_kernel   the two host offset arrays travel as launch arguments, 32 entries per launch, into the workspace.
+//   mm_area_kernel      one thread per face: a = sqrt(nn) (0 = invalid) into the workspace, atomicMax of its bits per mesh.
+//   mm_count_write_kernel<false>  one workgroup per MM_THREADS faces: the sum of their q.
+//   mm_scan_kernel      one workgroup per mesh: exclusive scan of the workgroup sums in place, the total.
+//   mm_count_write_kernel<true>   one workgroup per MM_THREADS faces: q again, scanned inside the workgroup, plus its offset -> C.
+//   mm_sample_kernel    one thread per sample: Philox words, binary search in C, barycentric point and the face's unit normal.
+//   mm_record_kernel    one thread per face: the 64-byte record (v0, v1, v2, n, nn, l2_0 .. l2_2), nn = 0 for an invalid face.
+//   mm_dist_kernel      one thread per point, one workgroup per MM_THREADS points: the records of MM_TILE faces at a time go through
+//                       LDS, component-major (four float4 planes), and every lane reads the SAME record (a broadcast read: no bank
+//                       conflict, one ds_read_b128 per 16 bytes for the whole wave); the running (sqdist, face) stays in registers.
+#include "../../include/bdm_hip.h"
+#include "common.h"
+
+#include <limits.h>
+
+#pragma clang fp contract(off)
+
+using namespace bdm;
+
+#define MM_THREADS 256
+#define MM_TILE 256                       // faces per LDS tile of mm_dist_kernel: 16 KiB
+#define MM_MAX_FACES (1 << 24)            // per mesh: C_last <= 2^54
+#define MM_MAX_B 65535                    // gridDim.y
+#define MM_OFFSETS_PER_LAUNCH 32
+#define MM_Q_ONE 1073741824.f             // 2^30
+
+namespace {
+
+struct MmOffsetChunk {
+  long long v[MM_OFFSETS_PER_LAUNCH], f[MM_OFFSETS_PER_LAUNCH];
+};
+
+__global__ void mm_offsets_kernel(MmOffsetChunk chunk, int first, int count, long long *__restrict__ vert_first,
+                                  long long *__restrict__ face_first) {
+  const int i = threadIdx.x;
+  if (i < count) {  // count <= MM_OFFSETS_PER_LAUNCH, first + count <= b + 1
+    vert_first[first + i] = chunk.v[i];
+    face_first[first + i] = chunk.f[i];
+  }
+}
+
+__device__ __forceinline__ bool mm_finite(float x) { return fabsf(x) < INFINITY; }   // false for NaN
+__device__ __forceinline__ float mm_dot(float ax, float ay, float az, float bx, float by, float bz) {
+  return (ax * bx + ay * by) + az * bz;
+}
+
+struct MmFace {
+  float v0x, v0y, v0z, v1x, v1y, v1z, v2x, v2y, v2z;
+  float nx, ny, nz, nn;   // nn == 0: invalid
+};
+
+// face `row` of the packed array, of a mesh whose vertices start at vbase and number nv.  false (and f.nn = 0) = invalid.
+__device__ __forceinline__ bool mm_face_load(const float *__restrict__ verts, const int *__restrict__ faces, long long row,
+                                             long long vbase, long long nv, MmFace &f) {
+  f.nn = 0.f;
+  const int *fp = faces + (size_t)row * 3;
+  const int i0 = fp[0], i1 = fp[1], i2 = fp[2];
+  if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= nv || i1 >= nv || i2 >= nv) return false;
+  const float *a = verts + (size_t)(vbase + i0) * 3, *b = verts + (size_t)(vbase + i1) * 3, *c = verts + (size_t)(vbase + i2) * 3;
+  f.v0x = a[0]; f.v0y = a[1]; f.v0z = a[2];
+  f.v1x = b[0]; f.v1y = b[1]; f.v1z = b[2];
+  f.v2x = c[0]; f.v2y = c[1]; f.v2z = c[2];
+  if (!(mm_finite(f.v0x) && mm_finite(f.v0y) && mm_finite(f.v0z) && mm_finite(f.v1x) && mm_finite(f.v1y) && mm_finite(f.v1z) &&
+        mm_finite(f.v2x) && mm_finite(f.v2y) && mm_finite(f.v2z)))
+    return false;
+  const float ex = f.v1x - f.v0x, ey = f.v1y - f.v0y, ez = f.v1z - f.v0z;   // e_0
+  const float gx = f.v2x - f.v0x, gy = f.v2y - f.v0y, gz = f.v2z - f.v0z;   // g
+  f.nx = ey * gz - ez * gy;
+  f.ny = ez * gx - ex * gz;
+  f.nz = ex * gy - ey * gx;
+  const float nn = mm_dot(f.nx, f.ny, f.nz, f.nx, f.ny, f.nz);
+  if (!(nn > 0.f && nn < INFINITY)) return false;
+  f.nn = nn;
+  return true;
+}
+
+// ---- sampler ----------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MM_THREADS) void mm_area_kernel(const float *__restrict__ verts, const int *__restrict__ faces,
+                                                             const long long *__restrict__ vert_first,
+                                                             const long long *__restrict__ face_first, float *__restrict__ area,
+                                                             unsigned int *__restrict__ amax_bits) {
+  const int m = blockIdx.y;
+  const long long base = face_first[m], nf = face_first[m + 1] - base;
+  const long long i = (long long)blockIdx.x * MM_THREADS + threadIdx.x;
+  if (i >= nf) return;
+  MmFace f;
+  const long long vbase = vert_first[m];
+  const float a = mm_face_load(verts, faces, base + i, vbase, vert_first[m + 1] - vbase, f) ? sqrtf(f.nn) : 0.f;
+  area[base + i] = a;
+  if (a > 0.f) atomicMax(amax_bits + m, __float_as_uint(a));   // non-negative floats order like their bit patterns
+}
+
+__device__ __forceinline__ long long mm_weight(float a, float amax) {
+  return a > 0.f ? (long long)rintf((a / amax) * MM_Q_ONE) : 0ll;   // a > 0 implies amax >= a > 0
+}
+
+// inclusive scan of one value per thread over the workgroup (Hillis-Steele in LDS) -> this thread's prefix; buf: MM_THREADS entries
+__device__ __forceinline__ long long mm_block_scan(long long v, long long *buf) {
+  const int t = threadIdx.x;
+  buf[t] = v;
+  __syncthreads();
+  for (int off = 1; off < MM_THREADS; off <<= 1) {
+    const long long add = t >= off ? buf[t - off] : 0ll;
+    __syncthreads();
+    buf[t] += add;
+    __syncthreads();
+  }
+  const long long r = buf[t];
+  __syncthreads();   // buf is free again
+  return r;
+}
+
+template <bool WRITE>
+__global__ __launch_bounds__(MM_THREADS) void mm_count_write_kernel(int nb_max, const long long *__restrict__ face_first,
+                                                                    const float *__restrict__ area,
+                                                                    const unsigned int *__restrict__ amax_bits,
+                                                                    long long *__restrict__ bsum, long long *__restrict__ cum) {
+  __shared__ long long buf[MM_THREADS];
+  const int m = blockIdx.y;
+  const long long base = face_first[m], nf = face_first[m + 1] - base;
+  const long long first = (long long)blockIdx.x * MM_THREADS;
+  if (first >= nf) return;   // the whole workgroup: no barrier is left waiting
+  const long long i = first + threadIdx.x;
+  const float amax = __uint_as_float(amax_bits[m]);
+  const long long q = i < nf ? mm_weight(area[base + i], amax) : 0ll;
+  const long long incl = mm_block_scan(q, buf);
+  if (WRITE) {
+    if (i < nf) cum[base + i] = bsum[(size_t)m * nb_max + blockIdx.x] + incl;
+  } else if (threadIdx.x == MM_THREADS - 1) {
+    bsum[(size_t)m * nb_max + blockIdx.x] = incl;
+  }
+}
+
+// one workgroup per mesh: bsum[m][0 .. nb) -> its exclusive scan, in place; total[m] = the sum (C_last)
+__global__ __launch_bounds__(MM_THREADS) void mm_scan_kernel(int nb_max, const long long *__restrict__ face_first,
+                                                             long long *__restrict__ bsum, long long *__restrict__ total) {
+  __shared__ long long buf[MM_THREADS];
+  const int m = blockIdx.x;
+  const long long nf = face_first[m + 1] - face_first[m];
+  const int nb = (int)((nf + MM_THREADS - 1) / MM_THREADS);   // <= nb_max
+  long long *a = bsum + (size_t)m * nb_max;
+  long long carry = 0;
+  for (int c0 = 0; c0 < nb; c0 += MM_THREADS) {   // uniform trip count
+    const int i = c0 + threadIdx.x;
+    const long long v = i < nb ? a[i] : 0ll;
+    const long long incl = mm_block_scan(v, buf);
+    if (i < nb) a[i] = carry + incl - v;
+    buf[threadIdx.x] = incl;
+    __syncthreads();
+    carry += buf[MM_THREADS - 1];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) total[m] = carry;
+}
+
+struct U4 { uint32_t v[4]; };
+
+// Philox4x32-10 as rng_ops.hip states it (Salmon et al., SC'11)
+__device__ __forceinline__ U4 mm_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+  const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(M0, c0), lo0 = M0 * c0;
+    const uint32_t hi1 = __umulhi(M1, c2), lo1 = M1 * c2;
+    const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
+    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
+    k0 += W0; k1 += W1;
+  }
+  U4 o;
+  o.v[0] = c0; o.v[1] = c1; o.v[2] = c2; o.v[3] = c3;
+  return o;
+}
+
+__global__ __launch_bounds__(MM_THREADS) void mm_sample_kernel(int s, const float *__restrict__ verts, const int *__restrict__ faces,
+                                                               const long long *__restrict__ vert_first,
+                                                               const long long *__restrict__ face_first,
+                                                               const long long *__restrict__ cum, const long long *__restrict__ total,
+                                                               const unsigned long long *__restrict__ keys, uint32_t draw,
+                                                               uint32_t purpose, float *__restrict__ points,
+                                                               int *__restrict__ face_idx, float *__restrict__ normals) {
+  const int m = blockIdx.y;
+  const long long j = (long long)blockIdx.x * MM_THREADS + threadIdx.x;   // 64-bit: the last workgroup may reach past 2^31 - 1
+  if (j >= s) return;
+  const size_t o = (size_t)m * s + j;
+  const long long base = face_first[m], nf = face_first[m + 1] - base;
+  const unsigned long long c_last = (unsigned long long)total[m];
+  float px = 0.f, py = 0.f, pz = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
+  int face = -1;
+  if (c_last != 0) {
+    const unsigned long long key = keys[m];
+    const U4 w = mm_philox((uint32_t)j, 0u, draw, purpose, (uint32_t)key, (uint32_t)(key >> 32));
+    const long long t = (long long)__umul64hi(((unsigned long long)w.v[0] << 32) | w.v[1], c_last);   // < c_last <= 2^54
+    const long long *c = cum + base;
+    long long lo = 0, hi = nf - 1;   // invariant: the answer lies in [lo, hi]; c[nf - 1] = c_last > t
+    for (int step = 0; step < 32 && lo < hi; ++step) {
+      const long long mid = lo + ((hi - lo) >> 1);
+      if (c[mid] > t) hi = mid; else lo = mid + 1;
+    }
+    face = (int)lo;
+    MmFace f;
+    const long long vbase = vert_first[m];
+    mm_face_load(verts, faces, base + lo, vbase, vert_first[m + 1] - vbase, f);   // q > 0: the face is valid
+    const float u1 = (float)(w.v[2] >> 8) * 5.9604644775390625e-08f, u2 = (float)(w.v[3] >> 8) * 5.9604644775390625e-08f;
+    const float su = sqrtf(u1);
+    const float b0 = 1.f - su, b1 = su * (1.f - u2), b2 = su * u2;
+    px = (b0 * f.v0x + b1 * f.v1x) + b2 * f.v2x;
+    py = (b0 * f.v0y + b1 * f.v1y) + b2 * f.v2y;
+    pz = (b0 * f.v0z + b1 * f.v1z) + b2 * f.v2z;
+    const float a = sqrtf(f.nn);
+    nx = f.nx / a; ny = f.ny / a; nz = f.nz / a;
+  }
+  points[o * 3] = px; points[o * 3 + 1] = py; points[o * 3 + 2] = pz;
+  if (face_idx) face_idx[o] = face;
+  if (normals) { normals[o * 3] = nx; normals[o * 3 + 1] = ny; normals[o * 3 + 2] = nz; }
+}
+
+// ---- distance ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MM_THREADS) void mm_record_kernel(const float *__restrict__ verts, const int *__restrict__ faces,
+                                                               const long long *__restrict__ vert_first,
+                                                               const long long *__restrict__ face_first, float4 *__restrict__ rec) {
+  const int m = blockIdx.y;
+  const long long base = face_first[m], nf = face_first[m + 1] - base;
+  const long long i = (long long)blockIdx.x * MM_THREADS + threadIdx.x;
+  if (i >= nf) return;
+  MmFace f;
+  const long long vbase = vert_first[m];
+  float4 *r = rec + (size_t)(base + i) * 4;
+  if (!mm_face_load(verts, faces, base + i, vbase, vert_first[m + 1] - vbase, f)) {
+    r[0] = r[1] = r[2] = r[3] = make_float4(0.f, 0.f, 0.f, 0.f);
+    return;
+  }
+  const float e0x = f.v1x - f.v0x, e0y = f.v1y - f.v0y, e0z = f.v1z - f.v0z;
+  const float e1x = f.v2x - f.v1x, e1y = f.v2y - f.v1y, e1z = f.v2z - f.v1z;
+  const float e2x = f.v0x - f.v2x, e2y = f.v0y - f.v2y, e2z = f.v0z - f.v2z;
+  r[0] = make_float4(f.v0x, f.v0y, f.v0z, f.v1x);
+  r[1] = make_float4(f.v1y, f.v1z, f.v2x, f.v2y);
+  r[2] = make_float4(f.v2z, f.nx, f.ny, f.nz);
+  r[3] = make_float4(f.nn, mm_dot(e0x, e0y, e0z, e0x, e0y, e0z), mm_dot(e1x, e1y, e1z, e1x, e1y, e1z), mm_dot(e2x, e2y, e2z, e2x, e2y, e2z));
+}
+
+// squared distance from x to the segment a + t e, t in [0, 1] (section 14's "Segment")
+__device__ __forceinline__ float mm_segment(float x, float y, float z, float ax, float ay, float az, float ex, float ey, float ez, float l2) {
+  const float rx = x - ax, ry = y - ay, rz = z - az;
+  const float h = mm_dot(ex, ey, ez, rx, ry, rz);
+  float t = l2 == 0.f ? 0.f : h / l2;
+  t = t > 0.f ? t : 0.f;
+  t = t < 1.f ? t : 1.f;
+  const float wx = x - (ax + t * ex), wy = y - (ay + t * ey), wz = z - (az + t * ez);
+  return mm_dot(wx, wy, wz, wx, wy, wz);
+}
+
+// s_i of the inside test: dot(n, cross(e, x - a))
+__device__ __forceinline__ float mm_side(float x, float y, float z, float ax, float ay, float az, float ex, float ey, float ez, float nx,
+                                         float ny, float nz) {
+  const float rx = x - ax, ry = y - ay, rz = z - az;
+  return mm_dot(nx, ny, nz, ey * rz - ez * ry, ez * rx - ex * rz, ex * ry - ey * rx);
+}
+
+__global__ __launch_bounds__(MM_THREADS) void mm_dist_kernel(int p, const float *__restrict__ points, const int *__restrict__ order,
+                                                             const float4 *__restrict__ rec, const long long *__restrict__ face_first,
+                                                             float *__restrict__ sqdist, int *__restrict__ face_idx) {
+  __shared__ float4 tile[4][MM_TILE];   // component-major: plane c holds float4 c of every record of the tile
+  const int m = blockIdx.y;
+  const long long k = (long long)blockIdx.x * MM_THREADS + threadIdx.x;   // 64-bit: the last workgroup may reach past 2^31 - 1
+  const long long base = face_first[m];
+  const int nf = (int)(face_first[m + 1] - base);   // <= 2^24
+  bool live = k < p;
+  int pt = 0;
+  if (live) {
+    pt = order ? order[(size_t)m * p + k] : (int)k;
+    live = pt >= 0 && pt < p;
+  }
+  float x = 0.f, y = 0.f, z = 0.f;
+  if (live) {
+    const float *q = points + ((size_t)m * p + pt) * 3;
+    x = q[0]; y = q[1]; z = q[2];
+  }
+  float best = INFINITY;
+  int idx = -1;
+  for (int t0 = 0; t0 < nf; t0 += MM_TILE) {   // uniform over the workgroup
+    __syncthreads();   // the previous tile has been read by everybody
+    const int mine = t0 + (int)threadIdx.x;   // MM_TILE == MM_THREADS: one record per thread
+    if (mine < nf) {
+      const float4 *r = rec + (size_t)(base + mine) * 4;
+      tile[0][threadIdx.x] = r[0]; tile[1][threadIdx.x] = r[1]; tile[2][threadIdx.x] = r[2]; tile[3][threadIdx.x] = r[3];
+    }
+    __syncthreads();
+    const int cnt = nf - t0 < MM_TILE ? nf - t0 : MM_TILE;
+    for (int j = 0; j < cnt; ++j) {
+      const float4 r3 = tile[3][j];
+      if (r3.x == 0.f) continue;   // invalid face: the same for every lane
+      const float4 r0 = tile[0][j], r1 = tile[1][j], r2 = tile[2][j];
+      const float v0x = r0.x, v0y = r0.y, v0z = r0.z, v1x = r0.w, v1y = r1.x, v1z = r1.y, v2x = r1.z, v2y = r1.w, v2z = r2.x;
+      const float nx = r2.y, ny = r2.z, nz = r2.w, nn = r3.x;
+      const float e0x = v1x - v0x, e0y = v1y - v0y, e0z = v1z - v0z;
+      const float e1x = v2x - v1x, e1y = v2y - v1y, e1z = v2z - v1z;
+      const float e2x = v0x - v2x, e2y = v0y - v2y, e2z = v0z - v2z;
+      float d = mm_segment(x, y, z, v0x, v0y, v0z, e0x, e0y, e0z, r3.y);
+      const float d1 = mm_segment(x, y, z, v1x, v1y, v1z, e1x, e1y, e1z, r3.z);
+      const float d2 = mm_segment(x, y, z, v2x, v2y, v2z, e2x, e2y, e2z, r3.w);
+      d = d1 < d ? d1 : d;
+      d = d2 < d ? d2 : d;
+      const float s0 = mm_side(x, y, z, v0x, v0y, v0z, e0x, e0y, e0z, nx, ny, nz);
+      const float s1 = mm_side(x, y, z, v1x, v1y, v1z, e1x, e1y, e1z, nx, ny, nz);
+      const float s2 = mm_side(x, y, z, v2x, v2y, v2z, e2x, e2y, e2z, nx, ny, nz);
+      if (s0 >= 0.f && s1 >= 0.f && s2 >= 0.f) {
+        const float kk = mm_dot(nx, ny, nz, x - v0x, y - v0y, z - v0z);
+        const float dp = (kk * kk) / nn;
+        d = dp < d ? dp : d;
+      }
+      if (d < best) { best = d; idx = t0 + j; }   // ascending face order: the first of equal distances stays
+    }
+  }
+  if (!live) return;
+  if (!(mm_finite(x) && mm_finite(y) && mm_finite(z))) { best = INFINITY; idx = -1; }
+  const size_t o = (size_t)m * p + pt;
+  sqdist[o] = best;
+  face_idx[o] = idx;
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------------
+bool mm_overlap(const void *a, size_t na, const void *b, size_t nb) {
+  if (!a || !b || na == 0 || nb == 0) return false;
+  const char *pa = (const char *)a, *pb = (const char *)b;
+  return pa < pb + nb && pb < pa + na;
+}
+
+size_t mm_align(size_t x) { return (x + 15) & ~(size_t)15; }
+
+struct MmSampleWs {
+  long long *vert_first, *face_first;  // [b + 1] each
+  long long *total;                    // [b]
+  unsigned int *amax_bits;             // [b]
+  long long *bsum;                     // [b][nb_max]
+  long long *cum;                      // [sum_f]
+  float *area;                         // [sum_f]
+  int nb_max;
+  size_t bytes;
+};
+
+MmSampleWs mm_sample_ws(void *ws, int b, long long sum_f, long long max_faces) {
+  MmSampleWs w;
+  char *p = (char *)ws;
+  size_t off = 0;
+  w.nb_max = (int)((max_faces + MM_THREADS - 1) / MM_THREADS);
+  w.vert_first = (long long *)(p + off); off += sizeof(long long) * (size_t)(b + 1);
+  w.face_first = (long long *)(p + off); off += sizeof(long long) * (size_t)(b + 1);
+  w.total = (long long *)(p + off); off += sizeof(long long) * (size_t)b;
+  w.bsum = (long long *)(p + off); off += sizeof(long long) * (size_t)b * w.nb_max;
+  w.cum = (long long *)(p + off); off += sizeof(long long) * (size_t)sum_f;
+  w.amax_bits = (unsigned int *)(p + off); off += sizeof(unsigned int) * (size_t)b;
+  w.area = (float *)(p + off); off += sizeof(float) * (size_t)sum_f;
+  w.bytes = mm_align(off);
+  return w;
+}
+
+struct MmDistWs {
+  float4 *rec;                         // [sum_f][4]
+  long long *vert_first, *face_first;  // [b + 1] each
+  size_t bytes;
+};
+
+MmDistWs mm_dist_ws(void *ws, int b, long long sum_f) {
+  MmDistWs w;
+  char *p = (char *)ws;
+  const size_t rec_bytes = 64 * (size_t)sum_f;
+  w.rec = (float4 *)p;
+  w.vert_first = (long long *)(p + rec_bytes);
+  w.face_first = w.vert_first + (b + 1);
+  w.bytes = mm_align(rec_bytes + 2 * sizeof(long long) * (size_t)(b + 1));
+  return w;
+}
+
+// the checks on the offset arrays both entry points share -> 0, or 1 with the error set; max_f = the largest face count
+int mm_check_offsets(const char *what, int b, const long long *vert_first, const long long *face_first, long long &max_f) {
+  BDM_REQUIRE(vert_first[0] == 0 && face_first[0] == 0, "%s: the offsets must start at 0", what);
+  max_f = 0;
+  for (int m = 0; m < b; ++m) {
+    BDM_REQUIRE(vert_first[m + 1] >= vert_first[m] && face_first[m + 1] >= face_first[m], "%s: offsets decrease at mesh %d", what, m);
+    const long long nf = face_first[m + 1] - face_first[m];
+    BDM_REQUIRE(nf <= MM_MAX_FACES, "%s: mesh %d has %lld faces, more than %d", what, m, nf, MM_MAX_FACES);
+    if (nf > max_f) max_f = nf;
+  }
+  BDM_REQUIRE(vert_first[b] <= INT_MAX && face_first[b] <= INT_MAX, "%s: %lld vertices or %lld faces reach 2^31", what, vert_first[b],
+              face_first[b]);
+  return BDM_OK;
+}
+
+void mm_send_offsets(int b, const long long *vert_first, const long long *face_first, long long *dev_v, long long *dev_f, hipStream_t s) {
+  for (int first = 0; first <= b; first += MM_OFFSETS_PER_LAUNCH) {
+    MmOffsetChunk chunk;
+    const int count = (b + 1 - first) < MM_OFFSETS_PER_LAUNCH ? (b + 1 - first) : MM_OFFSETS_PER_LAUNCH;
+    for (int i = 0; i < MM_OFFSETS_PER_LAUNCH; ++i) {
+      chunk.v[i] = i < count ? vert_first[first + i] : 0;
+      chunk.f[i] = i < count ? face_first[first + i] : 0;
+    }
+    hipLaunchKernelGGL(mm_offsets_kernel, dim3(1), dim3(64), 0, s, chunk, first, count, dev_v, dev_f);
+  }
+}
+
+bool mm_sizes_ok(int b, long long sum_f) { return b >= 0 && b <= MM_MAX_B && sum_f >= 0 && sum_f <= INT_MAX; }
+
+}  // namespace
+
+extern "C" size_t bdm_mesh_sample_workspace_bytes(int b, long long sum_f, long long max_faces) {
+  if (!mm_sizes_ok(b, sum_f) || max_faces < 0 || max_faces > MM_MAX_FACES || max_faces > sum_f) return 0;
+  return mm_sample_ws(nullptr, b, sum_f, max_faces).bytes;
+}
+
+extern "C" int bdm_mesh_sample_points(int b, int s, long long max_faces, const float *verts, const int *faces,
+                                      const long long *vert_first, const long long *face_first, const unsigned long long *keys,
+                                      unsigned int draw, unsigned int purpose, float *points, int *face_idx, float *normals,
+                                      void *workspace, void *stream) {
+  BDM_REQUIRE(b >= 0 && b <= MM_MAX_B, "mesh_sample_points: batch size %d outside 0 .. %d", b, MM_MAX_B);
+  BDM_REQUIRE(s >= 0, "mesh_sample_points: negative sample count");
+  BDM_REQUIRE((long long)b * s <= INT_MAX, "mesh_sample_points: %d meshes of %d samples reach 2^31", b, s);
+  if (b == 0 || s == 0) return BDM_OK;
+  BDM_REQUIRE(verts && faces && vert_first && face_first && keys && points && workspace,
+              "mesh_sample_points: an input, the points or the workspace is NULL");
+  BDM_REQUIRE(((uintptr_t)workspace & 15) == 0, "mesh_sample_points: the workspace is not 16-byte aligned");
+  long long max_f = 0;
+  if (mm_check_offsets("mesh_sample_points", b, vert_first, face_first, max_f) != BDM_OK) return BDM_ERR_ARG;
+  BDM_REQUIRE(max_faces == max_f, "mesh_sample_points: max_faces = %lld, the largest mesh has %lld", max_faces, max_f);
+  const long long sum_v = vert_first[b], sum_f = face_first[b];
+  const MmSampleWs ws = mm_sample_ws(workspace, b, sum_f, max_f);
+  const size_t n = (size_t)b * s;
+  const void *in[3] = {verts, faces, keys};
+  const size_t in_bytes[3] = {12 * (size_t)sum_v, 12 * (size_t)sum_f, 8 * (size_t)b};
+  const void *out[4] = {points, face_idx, normals, workspace};
+  const size_t out_bytes[4] = {12 * n, 4 * n, 12 * n, ws.bytes};
+  for (int o = 0; o < 4; ++o) {
+    for (int i = 0; i < 3; ++i)
+      BDM_REQUIRE(!mm_overlap(out[o], out_bytes[o], in[i], in_bytes[i]), "mesh_sample_points: output %d overlaps input %d", o, i);
+    for (int q = o + 1; q < 4; ++q)
+      BDM_REQUIRE(!mm_overlap(out[o], out_bytes[o], out[q], out_bytes[q]), "mesh_sample_points: outputs %d and %d overlap", o, q);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  mm_send_offsets(b, vert_first, face_first, ws.vert_first, ws.face_first, st);
+  if (hipMemsetAsync(ws.amax_bits, 0, sizeof(unsigned int) * (size_t)b, st) != hipSuccess) return launch_status("mesh_sample_points (memset)");
+  if (ws.nb_max > 0) {
+    const dim3 grid((unsigned)ws.nb_max, (unsigned)b);
+    hipLaunchKernelGGL(mm_area_kernel, grid, dim3(MM_THREADS), 0, st, verts, faces, ws.vert_first, ws.face_first, ws.area, ws.amax_bits);
+    hipLaunchKernelGGL(mm_count_write_kernel<false>, grid, dim3(MM_THREADS), 0, st, ws.nb_max, ws.face_first, ws.area, ws.amax_bits,
+                       ws.bsum, ws.cum);
+  }
+  hipLaunchKernelGGL(mm_scan_kernel, dim3((unsigned)b), dim3(MM_THREADS), 0, st, ws.nb_max, ws.face_first, ws.bsum, ws.total);
+  if (ws.nb_max > 0)
+    hipLaunchKernelGGL(mm_count_write_kernel<true>, dim3((unsigned)ws.nb_max, (unsigned)b), dim3(MM_THREADS), 0, st, ws.nb_max,
+                       ws.face_first, ws.area, ws.amax_bits, ws.bsum, ws.cum);
+  hipLaunchKernelGGL(mm_sample_kernel, dim3((unsigned)cdivll(s, MM_THREADS), (unsigned)b), dim3(MM_THREADS), 0, st, s, verts, faces,
+                     ws.vert_first, ws.face_first, ws.cum, ws.total, keys, draw, purpose, points, face_idx, normals);
+  return launch_status("mesh_sample_points");
+}
+
+extern "C" size_t bdm_point_mesh_distance_workspace_bytes(int b, long long sum_f) {
+  if (!mm_sizes_ok(b, sum_f)) return 0;
+  return mm_dist_ws(nullptr, b, sum_f).bytes;
+}
+
+extern "C" int bdm_point_mesh_distance_variant(int b, int p, long long sum_f, int has_order) {
+  (void)has_order;
+  if (!mm_sizes_ok(b, sum_f) || p < 0 || (long long)b * p > INT_MAX) return 0;
+  return 1;   // the exhaustive form: the only one built (bdm_hip.h section 14)
+}
+
+extern "C" int bdm_point_mesh_distance(int b, int p, int form, const float *verts, const int *faces, const long long *vert_first,
+                                       const long long *face_first, const float *points, const int *order, float *sqdist,
+                                       int *face_idx, void *workspace, void *stream) {
+  BDM_REQUIRE(b >= 0 && b <= MM_MAX_B, "point_mesh_distance: batch size %d outside 0 .. %d", b, MM_MAX_B);
+  BDM_REQUIRE(p >= 0, "point_mesh_distance: negative point count");
+  BDM_REQUIRE((long long)b * p <= INT_MAX, "point_mesh_distance: %d meshes of %d points reach 2^31", b, p);
+  BDM_REQUIRE(form != 2, "point_mesh_distance: the culled form is not built (no margin keeps its bits: bdm_hip.h section 14)");
+  BDM_REQUIRE(form == 0 || form == 1, "point_mesh_distance: form %d is none of 0 (chooser), 1 (exhaustive)", form);
+  if (b == 0 || p == 0) return BDM_OK;
+  BDM_REQUIRE(verts && faces && vert_first && face_first && points && sqdist && face_idx && workspace,
+              "point_mesh_distance: an input, an output or the workspace is NULL");
+  BDM_REQUIRE(((uintptr_t)workspace & 15) == 0, "point_mesh_distance: the workspace is not 16-byte aligned");
+  long long max_f = 0;
+  if (mm_check_offsets("point_mesh_distance", b, vert_first, face_first, max_f) != BDM_OK) return BDM_ERR_ARG;
+  const long long sum_v = vert_first[b], sum_f = face_first[b];
+  const MmDistWs ws = mm_dist_ws(workspace, b, sum_f);
+  const size_t n = (size_t)b * p;
+  const void *in[4] = {verts, faces, points, order};
+  const size_t in_bytes[4] = {12 * (size_t)sum_v, 12 * (size_t)sum_f, 12 * n, 4 * n};
+  const void *out[3] = {sqdist, face_idx, workspace};
+  const size_t out_bytes[3] = {4 * n, 4 * n, ws.bytes};
+  for (int o = 0; o < 3; ++o) {
+    for (int i = 0; i < 4; ++i)
+      BDM_REQUIRE(!mm_overlap(out[o], out_bytes[o], in[i], in_bytes[i]), "point_mesh_distance: output %d overlaps input %d", o, i);
+    for (int q = o + 1; q < 3; ++q)
+      BDM_REQUIRE(!mm_overlap(out[o], out_bytes[o], out[q], out_bytes[q]), "point_mesh_distance: outputs %d and %d overlap", o, q);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  mm_send_offsets(b, vert_first, face_first, ws.vert_first, ws.face_first, st);
+  if (max_f > 0)
+    hipLaunchKernelGGL(mm_record_kernel, dim3((unsigned)cdivll(max_f, MM_THREADS), (unsigned)b), dim3(MM_THREADS), 0, st, verts, faces,
+                       ws.vert_first, ws.face_first, ws.rec);
+  hipLaunchKernelGGL(mm_dist_kernel, dim3((unsigned)cdivll(p, MM_THREADS), (unsigned)b), dim3(MM_THREADS), 0, st, p, points, order, ws.rec,
+                     ws.face_first, sqdist, face_idx);
+  return launch_status("point_mesh_distance");
+}

@@ -1,0 +1,235 @@
+"""Scoring triangle meshes on the HIP path: area-weighted surface samples (pytorch3d's sample_points_from_meshes) and the squared
+distance from points to the nearest face (the point-to-face half of pytorch3d's point_mesh_face_distance), restated from their
+published behaviour (bdm_mesh_sample_points / bdm_point_mesh_distance, csrc/mesh_metrics.hip; the rule is stated in
+include/bdm_hip.h section 14 and DESIGN.md section 18), and the reconstruction metrics of a tree of meshes built on the two.
+
+    python -m bdm_amd.mesh_metrics --mesh_dir D --gt_dir D [--num-samples S] [--seed K] [--batch-size 16]
+
+samples every mesh .ply of mesh_dir that has a ground-truth cloud at the same relative path of gt_dir and prints one JSON line:
+CD x 1e3 and F1@0.01 of the samples against the ground truth (bdm_amd.evaluation's protocol), and the distance from the ground-truth
+points to the mesh itself, which is free of sampling noise."""
+import argparse
+import json
+import sys
+from pathlib import Path
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import ops, rng
+
+MAX_FACES, MAX_B = 1 << 24, 65535   # limits of bdm_hip.h section 14
+FORMS = {None: 0, "exhaustive": 1}   # the culled form is not built (no margin keeps its bits: DESIGN.md section 18)
+
+
+def _mesh_lists(meshes):
+    """A Meshes or a (verts_list, faces_list) pair -> (verts_list, faces_list), checked as cameras.Meshes checks them."""
+    from .cameras import Meshes
+    if hasattr(meshes, "verts_list") and hasattr(meshes, "faces_list"):
+        return meshes.verts_list(), meshes.faces_list()
+    if isinstance(meshes, (tuple, list)) and len(meshes) == 2 and isinstance(meshes[0], (list, tuple)):
+        m = Meshes(list(meshes[0]), list(meshes[1]))   # raises ValueError for float or bool faces and bad shapes
+        return m.verts_list(), m.faces_list()
+    raise ValueError(f"expected a Meshes or a (verts_list, faces_list) pair, got {type(meshes).__name__}")
+
+
+def _packed(verts_list, faces_list):
+    """The ABI's form of a batch -> (verts, faces, vert_first, face_first, max_faces); an empty side still gets one (unread) row."""
+    nv, nf = [int(v.shape[0]) for v in verts_list], [int(f.shape[0]) for f in faces_list]
+    if len(nv) > MAX_B:
+        raise ValueError(f"{len(nv)} meshes exceed {MAX_B}: split the batch")
+    if nf and max(nf) > MAX_FACES:
+        raise ValueError(f"a mesh of {max(nf)} faces exceeds {MAX_FACES}")
+    if sum(nv) >= 2 ** 31 or sum(nf) >= 2 ** 31:
+        raise ValueError("the batch reaches 2^31 vertices or faces: split it")
+    dev = verts_list[0].device
+    L.ptr(verts_list[0])   # refuses host tensors before anything is allocated
+    verts = L.f32(torch.cat([v.float() for v in verts_list])) if sum(nv) else torch.zeros(1, 3, device=dev)
+    # indices beyond int32 cannot be vertex indices: they become -1, an invalid face under the rule, instead of wrapping around
+    faces = torch.cat([(torch.where((f >= 0) & (f < 2 ** 31), f, -1) if f.dtype == torch.int64 else f).int() for f in faces_list]).contiguous() \
+        if sum(nf) else torch.zeros(1, 3, dtype=torch.int32, device=dev)
+    vert_first = torch.tensor([0] + nv, dtype=torch.int64).cumsum(0)   # host arrays: the call reads them before it returns
+    face_first = torch.tensor([0] + nf, dtype=torch.int64).cumsum(0)
+    return verts, faces.to(dev), vert_first, face_first, (max(nf) if nf else 0)
+
+
+@torch.no_grad()
+def sample_points_from_meshes(meshes, num_samples=10000, return_normals=False, *, seed=0, first_index=0, return_face_idx=False):
+    """pytorch3d's sample_points_from_meshes: `num_samples` area-weighted surface points per mesh -> (B, S, 3) on the meshes' device,
+    then the unit face normals (B, S, 3) if return_normals, then the face index within the mesh (B, S) int64 if return_face_idx.
+    Mesh m draws from the Philox stream keyed rng.shape_key(seed, first_index + m), purpose rng.MESH: its samples do not depend on
+    its batch slot.  A mesh without a valid face yields zeros (and face index -1), as pytorch3d does for empty meshes.
+    Bad arguments raise ValueError before any launch."""
+    verts_list, faces_list = _mesh_lists(meshes)
+    S = int(num_samples)
+    if S < 1:
+        raise ValueError(f"num_samples={num_samples} is not positive")
+    B = len(verts_list)
+    if B * S >= 2 ** 31:
+        raise ValueError(f"{B} meshes of {S} samples reach 2^31: split the batch")
+    if B == 0:
+        out = (torch.zeros(0, S, 3),) + ((torch.zeros(0, S, 3),) if return_normals else ()) + \
+            ((torch.zeros(0, S, dtype=torch.int64),) if return_face_idx else ())
+        return out if len(out) > 1 else out[0]
+    verts, faces, vert_first, face_first, max_f = _packed(verts_list, faces_list)
+    dev = verts.device
+    keys = [rng.shape_key(seed, int(first_index) + m) for m in range(B)]
+    keys = torch.tensor([k - (1 << 64) if k >= (1 << 63) else k for k in keys], dtype=torch.int64).to(dev)
+    points = torch.empty(B, S, 3, dtype=torch.float32, device=dev)
+    normals = torch.empty(B, S, 3, dtype=torch.float32, device=dev) if return_normals else None
+    face_idx = torch.empty(B, S, dtype=torch.int32, device=dev) if return_face_idx else None
+    lib = L.lib()
+    ws = ops.workspace(lib.bdm_mesh_sample_workspace_bytes(B, int(face_first[-1]), max_f), dev, "mesh_sample")
+    L.check(lib.bdm_mesh_sample_points(B, S, max_f, L.ptr(verts), L.ptr(faces), vert_first.data_ptr(), face_first.data_ptr(), L.ptr(keys), 0,
+                                       rng.MESH, L.ptr(points), L.ptr(face_idx), L.ptr(normals), L.ptr(ws), L.stream()), "mesh_sample_points")
+    out = (points,) + ((normals,) if return_normals else ()) + ((face_idx.long(),) if return_face_idx else ())
+    return out if len(out) > 1 else out[0]
+
+
+def morton_order(points, bits=10):
+    """(B, P) int32 permutation: every cloud's points in Morton order of their coordinates quantised to `bits` bits per axis over the
+    cloud's bounding box (torch integer operations and one sort on the points' device)."""
+    p = torch.nan_to_num(points.float(), nan=0.0, posinf=0.0, neginf=0.0)
+    lo, hi = p.min(dim=1, keepdim=True).values, p.max(dim=1, keepdim=True).values
+    top = (1 << bits) - 1
+    cell = ((p - lo) / (hi - lo).clamp_min(1e-30) * top).long().clamp(0, top)
+    code = torch.zeros(cell.shape[:2], dtype=torch.int64, device=points.device)
+    for b in range(bits):
+        for axis in range(3):
+            code |= ((cell[..., axis] >> b) & 1) << (3 * b + axis)
+    return torch.sort(code, dim=1, stable=True).indices.int()
+
+
+@torch.no_grad()
+def point_mesh_sqdist(meshes, points, *, form=None, order=None):
+    """(sqdist (B, P) float32, face_idx (B, P) int64): for every point of `points` ((B, P, 3) or a Pointclouds of equal sizes) the
+    squared distance to the nearest valid face of mesh b and that face's index within the mesh (the lowest among equal distances).
+    A point with a non-finite coordinate, and every point of a mesh without a valid face, gets (+inf, -1).
+    form: None (the chooser) or "exhaustive".  order: None (natural), "morton", or a (B, P) integer permutation -- which thread takes
+    which point; the result does not depend on it.  Bad arguments raise ValueError before any launch."""
+    verts_list, faces_list = _mesh_lists(meshes)
+    if hasattr(points, "points_padded"):
+        points = points.points_padded()
+    if form not in FORMS:
+        raise ValueError(f"form={form!r} is none of {list(FORMS)} (the culled form is not built)")
+    if not torch.is_tensor(points) or points.dim() != 3 or points.shape[2] != 3 or not points.is_floating_point():
+        raise ValueError("expected a Pointclouds or a floating-point (B, P, 3) tensor")
+    B, P, _ = points.shape
+    if B != len(verts_list):
+        raise ValueError(f"{B} clouds for {len(verts_list)} meshes")
+    if B * P >= 2 ** 31:
+        raise ValueError(f"{B} clouds of {P} points reach 2^31: split the batch")
+    if torch.is_tensor(order) and (tuple(order.shape) != (B, P) or order.is_floating_point() or order.dtype == torch.bool):
+        raise ValueError(f"order must be a (B, P) = ({B}, {P}) integer permutation")
+    if order is not None and not torch.is_tensor(order) and order != "morton":
+        raise ValueError(f"order={order!r} is none of None, 'morton', a (B, P) integer tensor")
+    if B == 0 or P == 0:
+        return torch.zeros(B, P, device=points.device), torch.zeros(B, P, dtype=torch.int64, device=points.device)
+    verts, faces, vert_first, face_first, _ = _packed(verts_list, faces_list)
+    dev = verts.device
+    points = L.f32(points.float().to(dev))
+    if isinstance(order, str):
+        order = morton_order(points)
+    sqdist = torch.full((B, P), float("inf"), dtype=torch.float32, device=dev)   # (an order that is no permutation leaves these)
+    face_idx = torch.full((B, P), -1, dtype=torch.int32, device=dev)
+    order = None if order is None else L.i32(order.to(dev))
+    lib = L.lib()
+    ws = ops.workspace(lib.bdm_point_mesh_distance_workspace_bytes(B, int(face_first[-1])), dev, "mesh_distance")
+    L.check(lib.bdm_point_mesh_distance(B, P, FORMS[form], L.ptr(verts), L.ptr(faces), vert_first.data_ptr(), face_first.data_ptr(),
+                                        L.ptr(points), L.ptr(order), L.ptr(sqdist), L.ptr(face_idx), L.ptr(ws), L.stream()),
+            "point_mesh_distance")
+    return sqdist, face_idx.long()
+
+
+def compose_scores(rows):
+    """[(cd_x1000, f1, gt sqdist (n,) float64 array) or None for an empty mesh] -> the dictionary evaluate_mesh_dirs returns."""
+    kept = [r for r in rows if r is not None]
+    nan = float("nan")
+    return {"num": len(rows), "cd_x1000": float(np.mean([r[0] for r in kept])) if kept else nan,
+            "f1_at_0.01": float(np.mean([r[1] for r in kept])) if kept else nan,
+            "gt_to_surface_x1000": float(np.mean([r[2].mean() for r in kept])) * 1000.0 if kept else nan,
+            "gt_within_0.01": float(np.mean([(r[2] < 0.01).mean() for r in kept])) if kept else nan, "empty": len(rows) - len(kept)}
+
+
+def evaluate_mesh_dirs(mesh_dir, gt_dir, num_samples=None, seed=0, batch_size=16, device="cuda"):
+    """For every mesh .ply under mesh_dir with a ground-truth cloud .ply at the same relative path under gt_dir (in sorted path
+    order; file i samples from the stream of shape index i): as many surface samples as the ground truth has points (or
+    num_samples), scored by evaluation.chamfer_distance_x1000 and evaluation.f1_score under evaluation.evaluate_dirs' centring.
+    -> {"num", "cd_x1000", "f1_at_0.01", "gt_to_surface_x1000" (mean squared distance from the UNCENTRED ground-truth points to the mesh,
+    x 1000), "gt_within_0.01" (share of ground-truth points with squared distance below 0.01), "empty" (meshes without a valid face:
+    counted in num, left out of the means)}."""
+    from .evaluation import chamfer_distance_x1000, f1_score
+    from .io import load_mesh_ply, load_pointcloud_ply
+    mesh_dir, gt_dir = Path(mesh_dir), Path(gt_dir)
+    if batch_size < 1:
+        raise ValueError("batch_size must be positive")
+    if num_samples is not None and int(num_samples) < 1:
+        raise ValueError(f"num_samples={num_samples} is not positive")
+    items = []
+    for path in sorted(mesh_dir.rglob("*.ply")):
+        rel = path.relative_to(mesh_dir)
+        if (gt_dir / rel).exists():
+            items.append((len(items), path, gt_dir / rel))
+    rows = [None] * len(items)
+    groups = {}   # ground-truth point count -> items: one batch holds clouds of one size
+    loaded = {}
+    for i, path, gt_path in items:
+        loaded[i] = (load_mesh_ply(path), load_pointcloud_ply(gt_path))
+        groups.setdefault(loaded[i][1].shape[0], []).append(i)
+    for n_gt, members in sorted(groups.items()):
+        for lo in range(0, len(members), batch_size):
+            # consecutive file indices form one call (first_index + m must be the file's index); others go alone
+            chunk = members[lo:lo + batch_size]
+            runs, run = [], [chunk[0]]
+            for i in chunk[1:]:
+                if i == run[-1] + 1:
+                    run.append(i)
+                else:
+                    runs.append(run)
+                    run = [i]
+            runs.append(run)
+            for run in runs:
+                verts = [torch.from_numpy(loaded[i][0][0]).to(device) for i in run]
+                faces = [torch.from_numpy(loaded[i][0][1]).to(device) for i in run]
+                gt = torch.stack([torch.from_numpy(loaded[i][1]) for i in run]).to(device)
+                S = n_gt if num_samples is None else int(num_samples)
+                samples, fidx = sample_points_from_meshes((verts, faces), S, seed=seed, first_index=run[0], return_face_idx=True)
+                sq, _ = point_mesh_sqdist((verts, faces), gt)
+                sq, empty = sq.double().cpu().numpy(), (fidx < 0).all(dim=1).cpu().tolist()
+                for j, i in enumerate(run):
+                    if empty[j]:
+                        continue
+                    # one cloud at a time: torch's mean (the centring) sums in an order that depends on the batch size, and a file's
+                    # score must not depend on what it was batched with
+                    s, g = samples[j:j + 1], gt[j:j + 1]
+                    rows[i] = (float(chamfer_distance_x1000(s, g)[0]),
+                               float(f1_score(s - s.mean(1, keepdim=True), g - g.mean(1, keepdim=True))[0]), sq[j])
+    return compose_scores(rows)
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m bdm_amd.mesh_metrics",
+                                 description="CD x 1e3, F1@0.01 and point-to-surface distance of mesh .ply trees against gt cloud trees")
+    ap.add_argument("--mesh_dir", required=True, help="directory tree of triangle-mesh .ply files")
+    ap.add_argument("--gt_dir", required=True, help="directory tree of ground-truth .ply clouds with the same relative paths")
+    ap.add_argument("--num-samples", type=int, default=None, help="surface samples per mesh (default: as many as the ground truth has points)")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--batch-size", type=int, default=16)
+    args = ap.parse_args(argv)
+    if args.batch_size < 1 or (args.num_samples is not None and args.num_samples < 1):
+        ap.error("--batch-size and --num-samples must be positive")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    if not torch.cuda.is_available():
+        raise L.BdmHipError("bdm_amd.mesh_metrics needs a HIP device (no CPU fallback)")
+    result = evaluate_mesh_dirs(args.mesh_dir, args.gt_dir, args.num_samples, args.seed, args.batch_size)
+    print(json.dumps(result))
+    return result
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

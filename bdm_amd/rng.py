@@ -13,6 +13,7 @@ from . import _lib as L
 MASK64 = (1 << 64) - 1
 # purposes (word 3 of the Philox counter): independent sub-streams of one shape
 INIT, PC2, PVD, MASK, FUSE = 0, 1, 2, 3, 4
+MESH = 5  # surface samples of a mesh (bdm_amd/mesh_metrics.py): element j of the draw is sample j
 
 
 def shape_key(seed: int, shape_index: int) -> int:

@@ -1077,6 +1077,86 @@ int bdm_render_meshes(int b, int h, int w, int c, int ortho, int cull, const flo
                       const float *vert_features, const float *face_features, const float *background, int *pix_to_face,
                       float *zbuf, float *bary, float *image, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * 14. Mesh metrics (csrc/mesh_metrics.hip): area-weighted surface samples of triangle meshes and the squared distance from points
+ *     to the nearest face of a mesh; restates pytorch3d's sample_points_from_meshes and the point-to-face half of
+ *     point_mesh_face_distance from their published behaviour (pytorch3d is not installed: parity unpinned).  DESIGN.md section 18.
+ * ---------------------------------------------------------------------------------- */
+/* Meshes: verts, faces, vert_first, face_first exactly as bdm_render_meshes takes them (packed, indices within the mesh, the two
+ *   offset arrays of b + 1 int64 in HOST memory, read during the call and free afterwards).
+ * All float32 arithmetic is rounded operation by operation (no FMA contraction), in the order written, division and square root
+ *   correctly rounded; fl() is left out below.  dot(a, b) = (ax bx + ay by) + az bz.
+ *   cross(a, b) = (ay bz - az by, az bx - ax bz, ax by - ay bx), each component one subtraction of two products.
+ * Face quantities (functions of the face alone): v0, v1, v2 its vertices in the face's order; e_i = v_{i+1} - v_i per component
+ *   (indices mod 3), l2_i = dot(e_i, e_i); g = v2 - v0; n = cross(e_0, g); nn = dot(n, n).
+ * Valid face: its three indices lie in [0, V), its nine coordinates are finite, and nn > 0 and nn < +inf.  Every other face is
+ *   invalid: it weighs 0 in the sampler and is ignored by the distance (indices that are out of range are treated as an invalid
+ *   face by the rule, not refused: the call cannot see them without reading device memory).
+ *
+ * bdm_mesh_sample_points: s samples per mesh.
+ *   Weights: a_i = sqrt(nn_i) (twice the area), 0 for an invalid face.  amax = the maximum of a over the mesh (exact: an integer
+ *     atomic maximum on the bit pattern of the non-negative floats).  q_i = (int64) rint((a_i / amax) * 1073741824.f), rint rounding
+ *     half to even, and q_i = 0 for an invalid face: 0 <= q_i <= 2^30.  C_i = q_0 + ... + q_i within the mesh, int64, exact (count /
+ *     scan / write in separate launches; no workgroup waits on another).  C_last = C_{F-1}.
+ *   Sample j of mesh m: (w0, w1, w2, w3) = Philox4x32-10(key = keys[m], counter = (j, 0, draw, purpose)), the convention of
+ *     bdm_philox_normal (counter words in that order, key = (low, high) half of the 64-bit key).
+ *     t = floor(((w0 << 32 | w1) * C_last) / 2^64) (the high half of the 128-bit product): 0 <= t < C_last.
+ *     The face is the first i with C_i > t (a face with q_i == 0 is never chosen).
+ *     u1 = float(w2 >> 8) * 2^-24, u2 = float(w3 >> 8) * 2^-24 (both exact, in [0, 1)); su = sqrt(u1);
+ *     b0 = 1 - su, b1 = su * (1 - u2), b2 = su * u2; point = ((b0 v0 + b1 v1) + b2 v2) per component.
+ *     normal = n / a per component, of the chosen face.
+ *   Outputs: points (b, s, 3); face_idx (b, s) int32, the index within the mesh (may be NULL); normals (b, s, 3) (may be NULL).
+ *   Empty mesh (C_last == 0: no face, or no valid one): points 0, normals 0, face_idx -1 (pytorch3d's behaviour for empty meshes).
+ *   keys: b 64-bit keys on the device.  max_faces: the largest face count of the batch (it sizes the scan; a value that is not
+ *     exactly that maximum is refused).
+ *   Limits: 0 <= b <= 65535 (b == 0 or s == 0 launches nothing and returns 0), 1 <= s, b s < 2^31, every mesh has at most 2^24
+ *     faces (so C_last <= 2^54), sum V and sum F < 2^31, offsets non-decreasing from 0, no NULL among verts, faces, vert_first,
+ *     face_first, keys, points and the workspace, no output and no part of the workspace overlapping an input or each other.
+ *     Outside these the call returns 1 and launches nothing.
+ *   workspace: bdm_mesh_sample_workspace_bytes(b, sum_f, max_faces) bytes (0 for sizes outside the limits), 16-byte aligned, contents
+ *     irrelevant before.
+ *
+ * bdm_point_mesh_distance: for every point of points (b, p, 3), against the faces of its own mesh.
+ *   Per (point x, valid face):
+ *     Segment i (a = v_i, e = e_i, l2 = l2_i): r = x - a; h = dot(e, r); t = 0 if l2 == 0, otherwise h / l2, then t = 0 unless
+ *       t > 0, then t = 1 unless t < 1 (a clamp to [0, 1] under which a NaN becomes 0);
+ *       c = a + t e per component; w = x - c; d_i = dot(w, w).
+ *     d_e = d_0; d_e = d_1 if d_1 < d_e; d_e = d_2 if d_2 < d_e.
+ *     Inside test: s_i = dot(n, cross(e_i, x - v_i)); the point is inside iff s_0 >= 0 and s_1 >= 0 and s_2 >= 0.
+ *     Plane: k = dot(n, x - v0); d_p = (k k) / nn.  d = d_p if the point is inside and d_p < d_e, otherwise d = d_e.
+ *   sqdist (b, p) = the smallest d over the valid faces of the mesh, face_idx (b, p) int32 = the face that has it, the lowest index
+ *     among equal d: the pair is the minimum of (d, index) in lexicographic order, so it does not depend on how the faces are tiled
+ *     or visited.  Overflow: a face whose d is NaN or +inf is never chosen.
+ *   A point with a non-finite coordinate gets sqdist = +inf and face_idx = -1; so does every point of a mesh without a valid face
+ *     (or whose every d overflowed).
+ *   order (b, p) int32, may be NULL: thread k of mesh m handles point order[m p + k] and writes that point's two results; NULL is
+ *     the natural order.  It exists so that neighbouring lanes can be given neighbouring points; the bits of the result do not
+ *     depend on it.  An entry outside [0, p) is skipped (nothing is read or written for it); if order is not a permutation, the
+ *     points it leaves out keep whatever the outputs held.
+ *   form: 0 = the chooser, 1 = exhaustive (every point visits every face of its mesh).  2 = culled by tile boxes is NOT BUILT and
+ *     is refused: the rule's plane term has no lower bound in terms of the true distance (for a sliver face the computed n is
+ *     rounding noise and the inside test passes far along the sliver's axis, where d_p can be 0), so no margin can be argued under
+ *     which skipping a tile keeps every bit.  bdm_point_mesh_distance_variant returns the form the chooser
+ *     takes for these sizes (always 1 in this implementation), 0 for sizes outside the limits.
+ *   Limits: 0 <= b <= 65535 (b == 0 or p == 0 launches nothing and returns 0), b p < 2^31, every mesh has at most 2^24 faces, sum V
+ *     and sum F < 2^31, offsets non-decreasing from 0, form in {0, 1}, no NULL among verts, faces, vert_first, face_first, points,
+ *     sqdist, face_idx and the workspace, no output and no part of the workspace overlapping an input or each other.  Outside these
+ *     the call returns 1 and launches nothing.
+ *   workspace: bdm_point_mesh_distance_workspace_bytes(b, sum_f) bytes (0 outside the limits), 16-byte aligned, contents irrelevant before: one
+ *     64-byte record per face (v0, v1, v2, n, nn, l2_0 .. l2_2; nn = 0 marks an invalid face) and the two offset arrays.
+ * Determinism (both): one integer atomic maximum per face (the sampler's amax), no floating-point atomics, no workgroup waits on
+ *   another, every loop is bounded by a launch argument or a face count; mesh j of a batch has the bits of that mesh alone, and
+ *   so has a repeated call. */
+size_t bdm_mesh_sample_workspace_bytes(int b, long long sum_f, long long max_faces);
+int bdm_mesh_sample_points(int b, int s, long long max_faces, const float *verts, const int *faces, const long long *vert_first,
+                           const long long *face_first, const unsigned long long *keys, unsigned int draw, unsigned int purpose,
+                           float *points, int *face_idx, float *normals, void *workspace, void *stream);
+size_t bdm_point_mesh_distance_workspace_bytes(int b, long long sum_f);
+int bdm_point_mesh_distance_variant(int b, int p, long long sum_f, int has_order);
+int bdm_point_mesh_distance(int b, int p, int form, const float *verts, const int *faces, const long long *vert_first,
+                            const long long *face_first, const float *points, const int *order, float *sqdist, int *face_idx,
+                            void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
