@@ -42,6 +42,9 @@ class RunConfig:  # structured.py:14-56
     # it exists, and how: "smooth" (Gouraud from vertex normals), "flat" (one colour per face) or "none" (black silhouettes)
     render_mesh_subdir: str = "pred_mesh"
     render_mesh_shading: str = "smooth"
+    # the tree of meshes with vertex colours (python -m bdm_amd.mesh_color --out_dir) that main_render.py draws lit, with the colours
+    # as albedo, when it exists ("none" as the mesh shading is drawn as "smooth" there: unlit colours would hide the surface)
+    render_colored_mesh_subdir: str = "colored_mesh"
     save_dir: Optional[str] = None
     # not in the reference: "reference" = its draws (CPU generator for the initial cloud and the blend masks, the device's
     # global generator for DDPM / PVD noise, seeded seed + rank); "per_shape" = Philox streams keyed by (seed, global

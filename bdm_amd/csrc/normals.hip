@@ -11,12 +11,14 @@
 // order, so "strictly below the k-th key" and "behind every equal key" order the list by (d2, j) without j taking part in a
 // comparison.  A non-finite point is stored as NaN: its d2 is NaN against every query, and a NaN pattern is above the list's
 // initial key 0x7f800001 in the unsigned comparison, while +inf (a finite pair whose distance overflows) is below it.
+// The key and the list step are knn_list.h's, shared with the two-set search of knn.hip.
 //
 // Then, per query, lane l fetches neighbour l, the wave forms the mean difference and the six central second moments with
 // fixed-order wave sums (no atomics: the bits do not depend on the batch or the launch), and every lane runs the same Jacobi
 // iteration (normals_eig.h).  The file is compiled with -ffp-contract=off (Makefile): the distance arithmetic defines indices.
 #include "common.h"
 #include "bdm_hip.h"
+#include "knn_list.h"
 #include "normals_eig.h"
 
 namespace bdm {
@@ -26,12 +28,7 @@ constexpr int NRM_WAVES = NRM_THREADS / 64;
 constexpr int NRM_QPW = 4;                        // queries per wave
 constexpr int NRM_QPB = NRM_WAVES * NRM_QPW;      // queries per workgroup
 constexpr int NRM_TILE = 1024;                    // candidates per LDS tile: 3 planes of 4 KiB
-constexpr unsigned int NRM_EMPTY = 0x7f800001u;   // key of an unused list entry: above +inf, below or equal to every NaN pattern
-
-// lane l <- lane l - 1 (lane 0 <- 0): DPP wave_shr:1
-__device__ __forceinline__ unsigned int lane_shr1(unsigned int v) {
-  return (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xF, 0xF, false);
-}
+constexpr unsigned int NRM_EMPTY = KNN_EMPTY;     // key of an unused list entry (knn_list.h, shared with knn.hip)
 
 __global__ __launch_bounds__(NRM_THREADS) void estimate_normals_kernel(int n, int k, int orient, int blocks_per_cloud,
                                                                        const float *__restrict__ points,
@@ -73,22 +70,7 @@ __global__ __launch_bounds__(NRM_THREADS) void estimate_normals_kernel(int n, in
       const float cx = sx[s + lane], cy = sy[s + lane], cz = sz[s + lane];
 #pragma unroll
       for (int q = 0; q < NRM_QPW; ++q) {
-        const float dx = cx - qx[q], dy = cy - qy[q], dz = cz - qz[q];
-        const unsigned int key = __float_as_uint(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
-        unsigned long long hits = __ballot(key < thr[q]);
-        while (hits) {  // wave-uniform
-          const int src = __builtin_ctzll(hits);
-          hits &= hits - 1;
-          const unsigned int kc = (unsigned int)__builtin_amdgcn_readlane((int)key, src);
-          if (kc < thr[q]) {  // an earlier insertion of this step may have lowered the k-th key
-            const unsigned int pk = lane_shr1(lkey[q]);
-            const int pj = (int)lane_shr1((unsigned int)lidx[q]);
-            const bool behind = lkey[q] > kc && lane < k, shift = pk > kc;  // lane 0 reads key 0: never a shift
-            lidx[q] = behind ? (shift ? pj : base + s + src) : lidx[q];
-            lkey[q] = behind ? (shift ? pk : kc) : lkey[q];
-            thr[q] = (unsigned int)__builtin_amdgcn_readlane((int)lkey[q], k - 1);
-          }
-        }
+        knn_list_step(knn_key(cx, cy, cz, qx[q], qy[q], qz[q]), base + s, k, lane, lkey[q], lidx[q], thr[q]);  // knn_list.h
       }
     }
   }

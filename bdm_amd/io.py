@@ -86,44 +86,66 @@ def _ply_vertex_props(head):
     return props
 
 
-def save_mesh_ply(verts, faces, path):
+def save_mesh_ply(verts, faces, path, colors=None):
     """Binary little-endian PLY of a triangle mesh: float32 x, y, z per vertex, then per face a uchar count (3) and three int32
-    vertex indices (`property list uchar int vertex_indices`: what MeshLab, Open3D and pytorch3d read)."""
+    vertex indices (`property list uchar int vertex_indices`: what MeshLab, Open3D and pytorch3d read).
+    colors (V, 3) in [0, 1]: uchar red, green, blue per vertex as well, under save_pointcloud_ply_rgb's conversion
+    rint(clip(c, 0, 1) * 255); without colours the file is what it was before the argument existed."""
     v = np.ascontiguousarray(np.asarray(verts, dtype="<f4").reshape(-1, 3))
     f = np.asarray(faces).reshape(-1, 3)
     if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
         raise ValueError(f"face indices outside 0..{v.shape[0] - 1}")
     rec = np.empty(f.shape[0], dtype=[("count", "u1"), ("idx", "<i4", 3)])
     rec["count"], rec["idx"] = 3, f
+    color_props = ""
+    if colors is not None:
+        col = np.asarray(colors, dtype=np.float64).reshape(-1, 3)
+        if col.shape[0] != v.shape[0]:
+            raise ValueError(f"{v.shape[0]} vertices but {col.shape[0]} colours")
+        vrec = np.empty(v.shape[0], dtype=[("xyz", "<f4", 3), ("rgb", "u1", 3)])
+        vrec["xyz"] = v
+        vrec["rgb"] = np.rint(np.clip(col, 0.0, 1.0) * 255.0).astype(np.uint8)
+        v, color_props = vrec, "property uchar red\nproperty uchar green\nproperty uchar blue\n"
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     header = (f"ply\nformat binary_little_endian 1.0\nelement vertex {v.shape[0]}\nproperty float x\nproperty float y\n"
-              f"property float z\nelement face {f.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n")
+              f"property float z\n{color_props}element face {f.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n")
     with open(path, "wb") as out:
         out.write(header.encode("ascii"))
         out.write(v.tobytes())
         out.write(rec.tobytes())
 
 
-def load_mesh_ply(path):
+def load_mesh_ply(path, with_colors=False):
     """(verts (V, 3) float32, faces (F, 3) int64) from a binary little-endian PLY in save_mesh_ply's form: a vertex element that
-    holds float x, y, z only, then triangles as `property list uchar int vertex_indices`."""
+    holds float x, y, z, optionally followed by uchar red, green, blue, then triangles as `property list uchar int vertex_indices`.
+    with_colors=True: (verts, faces, colors), colors (V, 3) float32 in [0, 1], or None for a file that carries none."""
     with open(path, "rb") as f:
         raw = f.read()
     end = raw.index(b"end_header\n") + len(b"end_header\n")
     head = raw[:end].decode("ascii").split("\n")
     if [l for l in head if l.startswith("format")][0].split()[1] != "binary_little_endian":
         raise ValueError(f"{path}: only binary little-endian mesh files are read")
-    if [p[1:] for p in _ply_vertex_props(head)] not in ([["float", c] for c in "xyz"], [["float32", c] for c in "xyz"]):
-        raise ValueError(f"{path}: the vertex element must hold float x, y, z only")
+    props = [p[1:] for p in _ply_vertex_props(head)]
+    xyz = ([["float", c] for c in "xyz"], [["float32", c] for c in "xyz"])
+    rgb = ([["uchar", c] for c in ("red", "green", "blue")], [["uint8", c] for c in ("red", "green", "blue")])
+    colored = len(props) == 6 and props[:3] in xyz and props[3:] in rgb
+    if props not in xyz and not colored:
+        raise ValueError(f"{path}: the vertex element must hold float x, y, z only, or those and uchar red, green, blue")
     faces_line = [l for l in head if l.startswith("element face")]
     if not faces_line or not any(l.split()[:4] in (["property", "list", "uchar", "int"], ["property", "list", "uint8", "int32"]) for l in head):
         raise ValueError(f"{path}: no face element with a `list uchar int` property")
     nv, nf = int([l for l in head if l.startswith("element vertex")][0].split()[-1]), int(faces_line[0].split()[-1])
-    verts = np.frombuffer(raw, dtype="<f4", count=3 * nv, offset=end).reshape(nv, 3).astype(np.float32)
-    rec = np.frombuffer(raw, dtype=[("count", "u1"), ("idx", "<i4", 3)], count=nf, offset=end + 12 * nv)
+    colors = None
+    if colored:
+        vrec = np.frombuffer(raw, dtype=[("xyz", "<f4", 3), ("rgb", "u1", 3)], count=nv, offset=end)
+        verts, colors = vrec["xyz"].astype(np.float32), vrec["rgb"].astype(np.float32) / np.float32(255.0)
+    else:
+        verts = np.frombuffer(raw, dtype="<f4", count=3 * nv, offset=end).reshape(nv, 3).astype(np.float32)
+    rec = np.frombuffer(raw, dtype=[("count", "u1"), ("idx", "<i4", 3)], count=nf, offset=end + (15 if colored else 12) * nv)
     if nf and not (rec["count"] == 3).all():
         raise ValueError(f"{path}: only triangles are read")
-    return verts, rec["idx"].astype(np.int64)
+    faces = rec["idx"].astype(np.int64)
+    return (verts, faces, colors) if with_colors else (verts, faces)
 
 
 def load_pointcloud_ply(path, with_colors=False, with_normals=False):

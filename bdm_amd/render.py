@@ -190,15 +190,23 @@ def rasterize_meshes(cameras, meshes, image_size=224, cull_backfaces=False):
 
 @torch.no_grad()
 def render_mesh_batch(cameras, meshes, image_size=224, shading="smooth", vert_colors=None, background_color=BACKGROUND, ambient=0.3,
-                      cull_backfaces=False):
+                      cull_backfaces=False, vert_albedo=None):
     """Images (B, H, W, 3) of the meshes seen from `cameras` (Perspective- or OrthographicCameras, or a list of single cameras).
     shading="smooth": shade_by_normals(..., two_sided=False) on the vertices and their normals (Meshes.verts_normals_packed),
     Gouraud colours the kernel interpolates; "flat": the same on face centroids and face normals, one colour per face; "none":
-    `vert_colors` (sum V, 3) interpolated, or zeros.  Bad arguments raise ValueError before any launch."""
+    `vert_colors` (sum V, 3) interpolated, or zeros.  vert_albedo (sum V, 3): under "smooth" and "flat" it replaces the constant
+    albedo of shade_by_normals, per vertex; a face's albedo under "flat" is the mean of its three vertices, ((a0 + a1) + a2) / 3.
+    Bad arguments raise ValueError before any launch."""
     if shading not in MESH_SHADINGS:
         raise ValueError(f"shading={shading!r}: expected one of {MESH_SHADINGS}")
     if vert_colors is not None and shading != "none":
         raise ValueError("vert_colors need shading='none'")
+    if vert_albedo is not None:
+        if shading == "none":
+            raise ValueError("vert_albedo needs a lit shading ('smooth' or 'flat'); unlit colours are vert_colors")
+        sum_v = sum(int(v.shape[0]) for v in meshes.verts_list()) if hasattr(meshes, "verts_list") else -1
+        if not torch.is_tensor(vert_albedo) or not vert_albedo.is_floating_point() or tuple(vert_albedo.shape) != (sum_v, 3):
+            raise ValueError(f"vert_albedo must be a floating-point ({sum_v}, 3) tensor")
     if not 0.0 <= float(ambient) <= 1.0:
         raise ValueError(f"ambient={ambient} is outside 0..1")
     cameras, _, _ = _check_mesh_args(cameras, meshes, image_size)
@@ -212,13 +220,20 @@ def render_mesh_batch(cameras, meshes, image_size=224, shading="smooth", vert_co
         else:
             where, normals = verts[meshes.faces_packed().to(verts.device)].mean(dim=1), meshes.faces_normals_packed()
             sizes = [int(f.shape[0]) for f in meshes.faces_list()]
+        albedos = [(0.8, 0.8, 0.8)] * len(sizes)   # shade_by_normals' default
+        if vert_albedo is not None:
+            albedo = vert_albedo.to(verts)
+            if shading == "flat":
+                a = albedo[meshes.faces_packed().to(verts.device)]
+                albedo = ((a[:, 0] + a[:, 1]) + a[:, 2]) / 3.0
+            albedos = torch.split(albedo, sizes)
         if cameras.orthographic:
             # one-sided, shade_by_normals lights an orthographic view along R[:, :, 2], the view axis INTO the screen (pinned by
             # tests/test_orient_host.py): a surface that faces the viewer has n . axis < 0, so the normals go in negated
             normals = -normals
         # shade_by_normals works on (B, n, 3) with one camera per row: one row per mesh, each with its own camera
-        colours = [shade_by_normals(p[None], n[None], _camera_row(cameras, i), ambient=ambient, two_sided=False)[0]
-                   for i, (p, n) in enumerate(zip(torch.split(where, sizes), torch.split(normals, sizes)))]
+        colours = [shade_by_normals(p[None], n[None], _camera_row(cameras, i), ambient=ambient, albedo=al, two_sided=False)[0]
+                   for i, (p, n, al) in enumerate(zip(torch.split(where, sizes), torch.split(normals, sizes), albedos))]
         colours = torch.cat(colours).float().contiguous()
         vert_features, face_features = (colours, None) if shading == "smooth" else (None, colours)
     return _render_meshes(cameras, meshes, image_size, cull_backfaces, vert_features, face_features, background_color, fragments=False)[1]
@@ -231,11 +246,11 @@ def _camera_row(cameras, i):
 
 @torch.no_grad()
 def visualize_mesh_batch(meshes, output_file_image=None, num_frames=1, elev=30, scale_factor=1.0, shading="smooth", image_size=224,
-                         cull_backfaces=False):
+                         cull_backfaces=False, vert_albedo=None):
     """The orbit of visualize_pointcloud_batch_pytorch3d for meshes: `num_frames` orthographic cameras (focal 0.25 * scale_factor)
     at distance 10 and elevation `elev`, every frame lit from its own camera, tiled with make_grid(nrow=int(sqrt(B)), pad_value=1);
     one frame goes to `output_file_image`, with num_frames > 1 frame f goes to <stem>-<f>.png beside it.  Returns the grids
-    (F, C, H', W') on the host."""
+    (F, C, H', W') on the host.  vert_albedo (sum V, 3) is forwarded to render_mesh_batch for every frame."""
     from .cameras import Meshes
     from .io import save_image_png
     F = int(num_frames)
@@ -247,7 +262,8 @@ def visualize_mesh_batch(meshes, output_file_image=None, num_frames=1, elev=30, 
     device = meshes.device
     R, T = look_at_view_transform(dist=10.0, elev=elev, azim=list(range(0, 360, 360 // F)), degrees=True, device=device)
     cameras = OrthographicCameras(focal_length=0.25 * scale_factor, device=device, R=R.repeat_interleave(B, dim=0), T=T.repeat_interleave(B, dim=0))
-    images = render_mesh_batch(cameras, Meshes(meshes.verts_list() * F, meshes.faces_list() * F), image_size, shading, cull_backfaces=cull_backfaces)
+    images = render_mesh_batch(cameras, Meshes(meshes.verts_list() * F, meshes.faces_list() * F), image_size, shading, cull_backfaces=cull_backfaces,
+                               vert_albedo=None if vert_albedo is None else vert_albedo.repeat(F, 1))
     frames = images.reshape(F, B, *images.shape[1:]).permute(0, 1, 4, 2, 3)
     grids = torch.stack([make_grid(f, nrow=int(math.sqrt(B)), pad_value=1) for f in frames], dim=0).detach().cpu()
     if output_file_image is not None:

@@ -1157,6 +1157,55 @@ int bdm_point_mesh_distance(int b, int p, int form, const float *verts, const in
                             const long long *face_first, const float *points, const int *order, float *sqdist, int *face_idx,
                             void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * 15. K nearest neighbours between two point sets and the transfer of attributes through them (csrc/knn.hip); restates
+ *     pytorch3d's knn_points / knn_gather from their published behaviour (pytorch3d is not installed: parity unpinned).
+ *     DESIGN.md section 19.
+ * ---------------------------------------------------------------------------------- */
+/* Layout: queries (sum P, 3) and refs (sum R, 3), packed and point-major.  q_first and r_first are offset arrays of b + 1 int64 in
+ *   HOST memory, taken exactly as bdm_mesh_sample_points takes vert_first (read during the call, free afterwards): entry i owns the
+ *   query rows q_first[i] .. q_first[i + 1] - 1 and the reference rows r_first[i] .. r_first[i + 1] - 1.  Offsets are non-decreasing
+ *   from 0.  A padded (N, P, 3) batch is the case q_first[i] = i P.
+ *
+ * bdm_knn_points: for every query row the K nearest reference rows of the same entry.
+ *   Distance: dx = fl(r_x - q_x), likewise dy and dz; d2 = fl(fl(fl(dx*dx) + fl(dy*dy)) + fl(dz*dz)), no FMA contraction: the order of
+ *     section 10.  The candidates are the reference rows j of the entry, j the index WITHIN the entry.  The neighbourhood is the k
+ *     candidates with the smallest (d2, j), ascending.
+ *   Outputs: idx (sum P, k) int32 and d2 (sum P, k) float32, addressed like the query rows.  Either may be NULL (the other keeps its
+ *     bits; with both NULL nothing is launched).
+ *   Non-finite input: a reference row with a non-finite coordinate is nobody's neighbour; a query with a non-finite coordinate has no
+ *     neighbours.  Two finite points whose d2 overflows to +inf ARE neighbours (d2 = +inf with idx >= 0).
+ *   Short neighbourhoods: a query with m < k neighbours gets its m neighbours in order, then idx = -1 and d2 = +inf.  This holds for
+ *     every entry size, an empty reference set included; there is no n > k requirement (the deliberate difference from section 10,
+ *     whose rows are all-or-nothing).
+ *   Limits: 1 <= k <= 64, 0 <= b <= 65535, sum P, sum R and sum P * k all < 2^31.  No NULL among queries, refs, q_first, r_first and
+ *     the workspace (an empty set still passes a valid pointer, which is not read).  No output and no part of the workspace overlaps
+ *     an input or another output, judged on byte ranges.  b == 0 or sum P == 0 returns 0 without a launch; anything else outside the
+ *     limits returns 1, launches nothing and leaves the outputs untouched.
+ *   workspace: bdm_knn_points_workspace_bytes(b, sum_p, k) bytes (0 outside the limits), 16-byte aligned, contents irrelevant before:
+ *     the two offset arrays.
+ *
+ * bdm_knn_interpolate: attributes attr (sum R, c) float32 of the reference rows carried to out (sum P, c) through an (idx, d2) pair
+ *   that bdm_knn_points wrote for the same two offset arrays; 1 <= c <= 16.
+ *   Entry l of a row takes part iff 0 <= idx_l < R of the entry (an index no search of this entry can have written is skipped, not
+ *     refused: the call cannot see it without reading device memory); m = the number of entries that take part, a_l = attr[idx_l].
+ *   mode = 0, nearest: out = a of the first entry that takes part, copied bit for bit.
+ *   mode = 1, inverse squared distance: w_l = 1 / fl(d2_l + eps), the division correctly rounded; eps is a float argument, eps > 0 and
+ *     finite required.  W = (..((w_0 + w_1) + w_2)..) over the entries that take part, ascending;
+ *     out_c = (..((w_0 a_0c + w_1 a_1c) + w_2 a_2c)..) / W, each product, each sum and the quotient rounded on its own.  An entry with
+ *     d2_l = +inf takes part with w_l = 0 (a row whose every d2 is +inf therefore gets 0 / 0 = NaN).
+ *   m == 0: the row gets fill, a float argument, in every channel.
+ *   Limits and conventions as above (no NULL among attr, idx, d2, out, the offsets and the workspace; mode in {0, 1}).
+ *   workspace: bdm_knn_interpolate_workspace_bytes(b) bytes: the two offset arrays and nothing else.
+ * Determinism (both): no atomics, no workgroup waits on another, every loop is bounded by a launch argument or an entry length;
+ *   entry i of a batch has the bits of that entry alone, and so has a repeated call. */
+size_t bdm_knn_points_workspace_bytes(int b, long long sum_p, int k);
+int bdm_knn_points(int b, int k, const float *queries, const float *refs, const long long *q_first, const long long *r_first,
+                   int *idx, float *d2, void *workspace, void *stream);
+size_t bdm_knn_interpolate_workspace_bytes(int b);
+int bdm_knn_interpolate(int b, int k, int c, int mode, float eps, float fill, const float *attr, const int *idx, const float *d2,
+                        const long long *q_first, const long long *r_first, float *out, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

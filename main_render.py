@@ -13,10 +13,14 @@ Where ${run.render_sample_dir}/${run.render_mesh_subdir} exists (the tree `pytho
 <category>/<name>.ply or <name>-<k>.ply in it is drawn from its entry's camera as renders/mesh/<category>/<stem>.png
 (run.render_mesh_shading = smooth | flat | none), and with run.render_num_frames > 1 its orbit as
 renders/mesh_orbit/<category>/<stem>-<f>.png; a file without a face element is a cloud and is left alone.
+Where ${run.render_sample_dir}/${run.render_colored_mesh_subdir} exists (the tree `python -m bdm_amd.mesh_color` writes), every mesh
+in it that carries vertex colours is drawn lit, its colours as the albedo, as renders/colored_mesh/<category>/<stem>.png, and with
+run.render_num_frames > 1 its orbit as renders/colored_mesh_orbit/<category>/<stem>-<f>.png.
 
     python main_blending.py run.job=sample_bdm_blending dataset=synthetic run.num_samples=1 dataset.max_points=1024
     python main_render.py dataset=synthetic run.render_sample_dir=<the directory the first command printed>
     python -m bdm_amd.surface --in_dir <that directory>/pred --out_dir <that directory>/pred_mesh     (then the line above again)
+    python -m bdm_amd.mesh_color --mesh_dir <that directory>/pred_mesh --color_dir <that directory>/colored --out_dir <that directory>/colored_mesh
 """
 import sys
 from pathlib import Path
@@ -52,20 +56,25 @@ def clouds_of(sample_dir, kind, category, name):
     return hits
 
 
-def meshes_of(sample_dir, subdir, category, name):
+def meshes_of(sample_dir, subdir, category, name, with_colors=False):
     """The triangle meshes of one dataset entry under <sample_dir>/<subdir>: [(path, verts (V, 3) float32, faces (F, 3) int64)] of
-    <name>.ply and <name>-<k>.ply, sorted; a file without a face element is a cloud and is not among them."""
+    <name>.ply and <name>-<k>.ply, sorted; a file without a face element is a cloud and is not among them.
+    with_colors=True: [(path, verts, faces, colors (V, 3) float32)] of the meshes that carry vertex colours only."""
     from bdm_amd.io import load_mesh_ply
     out = []
     for path in clouds_of(sample_dir, subdir, category, name):
         with open(path, "rb") as f:
             head = f.read(4096).split(b"end_header")[0]
         if b"element face" in head:
-            out.append((path, *load_mesh_ply(path)))
+            if not with_colors:
+                out.append((path, *load_mesh_ply(path)))
+            elif b"property uchar red" in head or b"property uint8 red" in head:
+                out.append((path, *load_mesh_ply(path, with_colors=True)))
     return out
 
 
-def render_tree(cfg, batches, render_fn, orbit_fn=None, device="cpu", shade_fn=None, mesh_fn=None, mesh_orbit_fn=None):
+def render_tree(cfg, batches, render_fn, orbit_fn=None, device="cpu", shade_fn=None, mesh_fn=None, mesh_orbit_fn=None,
+                colored_mesh_fn=None, colored_mesh_orbit_fn=None):
     """Walk the dataset, render every cloud found under the sample directory, write renders/<kind>/<category>/<stem>.png; returns
     the paths written.  render_fn(cameras (list of single cameras), points (B, n, 3), colours (B, n, 3) or None) -> images
     (B, H, W, 3) in [0, 1]: one call per batch, kind and distinct point count.  orbit_fn(points (1, n, 3), colours or None,
@@ -74,7 +83,10 @@ def render_tree(cfg, batches, render_fn, orbit_fn=None, device="cpu", shade_fn=N
     their colours from it, once per batch group (a config without the key, or "none", leaves them None as before).
     Where <sample_dir>/<run.render_mesh_subdir> exists: mesh_fn(cameras, verts_list, faces_list) -> images (B, H, W, 3), one call
     per batch, written as renders/mesh/<category>/<stem>.png; mesh_orbit_fn(verts (V, 3), faces (F, 3), path of <stem>.png,
-    num_frames) -> the paths it wrote, per mesh when run.render_num_frames > 1.  Without that directory nothing changes."""
+    num_frames) -> the paths it wrote, per mesh when run.render_num_frames > 1.  Without that directory nothing changes.
+    Where <sample_dir>/<run.render_colored_mesh_subdir> exists: colored_mesh_fn(cameras, verts_list, faces_list, colors_list) ->
+    images, written as renders/colored_mesh/<category>/<stem>.png; colored_mesh_orbit_fn(verts, faces, colors, path, num_frames) ->
+    the paths it wrote under renders/colored_mesh_orbit/.  Without that directory nothing changes either."""
     from bdm_amd.io import load_pointcloud_ply, save_image_png
     root, written = Path(cfg.run.render_sample_dir), []
     shading = getattr(cfg.run, "render_shading", "none")
@@ -86,6 +98,10 @@ def render_tree(cfg, batches, render_fn, orbit_fn=None, device="cpu", shade_fn=N
     with_meshes = bool(mesh_subdir) and (root / mesh_subdir).is_dir()
     if with_meshes and mesh_fn is None:
         raise ValueError(f"{root / mesh_subdir} holds meshes: they need a mesh_fn")
+    colored_subdir = getattr(cfg.run, "render_colored_mesh_subdir", "colored_mesh")
+    with_colored = bool(colored_subdir) and (root / colored_subdir).is_dir()
+    if with_colored and colored_mesh_fn is None:
+        raise ValueError(f"{root / colored_subdir} holds coloured meshes: they need a colored_mesh_fn")
     for batch_idx, batch in enumerate(batches):
         if cfg.run.num_sample_batches is not None and batch_idx >= cfg.run.num_sample_batches:
             break
@@ -139,6 +155,22 @@ def render_tree(cfg, batches, render_fn, orbit_fn=None, device="cpu", shade_fn=N
                     for (i, path, _, _), v, f in zip(found, verts, faces):
                         out = root / "renders" / "mesh_orbit" / batch.sequence_category[i] / f"{path.stem}.png"
                         written += [Path(p) for p in mesh_orbit_fn(v, f, out, cfg.run.render_num_frames)]
+        if with_colored:
+            found = [(i, *item) for i, (name, cat) in enumerate(zip(batch.sequence_name, batch.sequence_category))
+                     for item in meshes_of(root, colored_subdir, cat, name, with_colors=True)]
+            if found:
+                verts = [torch.from_numpy(v).to(device) for _, _, v, _, _ in found]
+                faces = [torch.from_numpy(f).to(device) for _, _, _, f, _ in found]
+                colors = [torch.from_numpy(c).to(device) for _, _, _, _, c in found]
+                images = colored_mesh_fn([cameras[it[0]] for it in found], verts, faces, colors)
+                for (i, path, *_), image in zip(found, images):
+                    out = root / "renders" / "colored_mesh" / batch.sequence_category[i] / f"{path.stem}.png"
+                    save_image_png(image.detach().cpu().permute(2, 0, 1).numpy(), out)
+                    written.append(out)
+                if cfg.run.render_num_frames > 1 and colored_mesh_orbit_fn is not None:
+                    for (i, path, *_), v, f, c in zip(found, verts, faces, colors):
+                        out = root / "renders" / "colored_mesh_orbit" / batch.sequence_category[i] / f"{path.stem}.png"
+                        written += [Path(p) for p in colored_mesh_orbit_fn(v, f, c, out, cfg.run.render_num_frames)]
     return written
 
 
@@ -197,7 +229,20 @@ def main(argv=None):
                                  scale_factor=cfg.model.scale_factor, shading=cfg.run.render_mesh_shading)
         return [path.with_name(f"{path.stem}-{f}.png") for f in range(num_frames)]
 
-    written = render_tree(cfg, get_dataloader(cfg, rank, world), render_fn, orbit_fn, device, shade_fn, mesh_fn, mesh_orbit_fn)
+    lit = "smooth" if cfg.run.render_mesh_shading == "none" else cfg.run.render_mesh_shading   # the colours are an albedo: always lit
+
+    def colored_mesh_fn(cameras, verts, faces, colors):
+        with gpu_turn(device):
+            return render_mesh_batch(cameras, Meshes(verts, faces), shading=lit, vert_albedo=torch.cat(colors)).cpu()
+
+    def colored_mesh_orbit_fn(verts, faces, colors, path, num_frames):
+        with gpu_turn(device):
+            visualize_mesh_batch(Meshes([verts], [faces]), output_file_image=str(path), num_frames=num_frames,
+                                 scale_factor=cfg.model.scale_factor, shading=lit, vert_albedo=colors)
+        return [path.with_name(f"{path.stem}-{f}.png") for f in range(num_frames)]
+
+    written = render_tree(cfg, get_dataloader(cfg, rank, world), render_fn, orbit_fn, device, shade_fn, mesh_fn, mesh_orbit_fn,
+                          colored_mesh_fn, colored_mesh_orbit_fn)
     barrier()
     print(f"rank {rank}: rendered {len(written)} images under {(Path(cfg.run.render_sample_dir) / 'renders').absolute()}")
     return written
