@@ -1,0 +1,300 @@
+"""Cleaning the reconstructed meshes on the HIP path: the vertex adjacency of a packed batch of triangle meshes, its connected
+components, the removal of small floating islands, and pytorch3d's `taubin_smoothing` (ops/mesh_filtering.py) with its name, argument
+order and defaults, over bdm_mesh_adjacency / bdm_mesh_components_* / bdm_mesh_taubin (csrc/mesh_clean.hip; the rule is stated in
+include/bdm_hip.h section 16 and DESIGN.md section 20).  pytorch3d is not installed, so the smoothing is restated from its published
+behaviour ("parity unpinned", as for the normals).
+
+    python -m bdm_amd.mesh_clean --mesh_dir D/pred_mesh --out_dir D/pred_mesh_clean [--min-fraction 0.1] [--min-faces 1]
+                                 [--keep-largest] [--taubin-iters 10] [--lambd 0.53] [--mu -0.34] [--weights inverse_length]
+                                 [--batch-size 16]
+
+walks the mesh .ply files of mesh_dir in sorted order, removes the small components of every mesh, smooths what is left, writes it
+under out_dir at the same relative path (vertex colours are carried along) and prints one JSON line.
+
+Departures from pytorch3d: a vertex without neighbours keeps its position (pytorch3d forms 0 / 0), `weights="uniform"` is an
+extension, no gradients."""
+import argparse
+import json
+import math
+import sys
+from pathlib import Path
+
+import torch
+
+from . import _lib as L
+from . import ops
+from .mesh_metrics import _mesh_lists
+
+MAX_B, MAX_ITER = 65535, 10000   # limits of bdm_hip.h section 16
+WEIGHTS = {"inverse_length": 0, "uniform": 1}
+ROUNDS_PER_CALL = 8   # label rounds between two reads of the `changed` flag
+
+
+def _packed(verts_list, faces_list):
+    """The ABI's form of a batch -> (verts, faces, vert_first, face_first); an empty side still gets one (unread) row."""
+    nv, nf = [int(v.shape[0]) for v in verts_list], [int(f.shape[0]) for f in faces_list]
+    if len(nv) > MAX_B:
+        raise ValueError(f"{len(nv)} meshes exceed {MAX_B}: split the batch")
+    if sum(nv) >= 2 ** 31 - 1 or 6 * sum(nf) >= 2 ** 31:
+        raise ValueError("the batch reaches 2^31 vertices or neighbour entries (six per face): split it")
+    for t in list(verts_list) + list(faces_list):
+        L.ptr(t)   # refuses host tensors before anything is allocated
+    dev = verts_list[0].device
+    verts = L.f32(torch.cat([v.float() for v in verts_list])) if sum(nv) else torch.zeros(1, 3, device=dev)
+    # indices beyond int32 cannot be vertex indices: they become -1, no connected face under the rule, instead of wrapping around
+    faces = torch.cat([(torch.where((f >= 0) & (f < 2 ** 31), f, -1) if f.dtype == torch.int64 else f).int() for f in faces_list]).contiguous() \
+        if sum(nf) else torch.zeros(1, 3, dtype=torch.int32, device=dev)
+    vert_first = torch.tensor([0] + nv, dtype=torch.int64).cumsum(0)   # host arrays: the calls read them before they return
+    face_first = torch.tensor([0] + nf, dtype=torch.int64).cumsum(0)
+    return verts, faces, vert_first, face_first
+
+
+def _adjacency(faces, vert_first, face_first):
+    """One bdm_mesh_adjacency call -> (nbr_first (sum V + 1) int32, nbr (max(6 sum F, 1)) int32, -1 past nbr_first[-1])."""
+    B, sum_v, sum_f, dev = vert_first.numel() - 1, int(vert_first[-1]), int(face_first[-1]), faces.device
+    nbr_first = torch.zeros(sum_v + 1, dtype=torch.int32, device=dev)
+    nbr = torch.full((max(6 * sum_f, 1),), -1, dtype=torch.int32, device=dev)
+    if B == 0 or sum_v == 0:
+        return nbr_first, nbr
+    lib = L.lib()
+    ws = ops.workspace(lib.bdm_mesh_adjacency_workspace_bytes(B, sum_v, sum_f), dev, "mesh_adjacency")
+    L.check(lib.bdm_mesh_adjacency(B, L.ptr(faces), vert_first.data_ptr(), face_first.data_ptr(), L.ptr(nbr_first), L.ptr(nbr), L.ptr(ws),
+                                   L.stream()), "mesh_adjacency")
+    return nbr_first, nbr
+
+
+def _components(faces, vert_first, face_first, nbr_first, nbr, rounds_per_call=None):
+    """init, rounds until the flag is clear, finish -> (vert_comp, face_comp, comp_count, comp_verts, comp_faces, calls); packed int32
+    device tensors as the ABI writes them."""
+    B, sum_v, sum_f, dev = vert_first.numel() - 1, int(vert_first[-1]), int(face_first[-1]), faces.device
+    vert_comp = torch.zeros(sum_v, dtype=torch.int32, device=dev)
+    face_comp = torch.full((sum_f,), -1, dtype=torch.int32, device=dev)
+    comp_count = torch.zeros(B, dtype=torch.int32, device=dev)
+    comp_verts, comp_faces = torch.zeros_like(vert_comp), torch.zeros_like(vert_comp)
+    if B == 0 or sum_v == 0:
+        return vert_comp, face_comp, comp_count, comp_verts, comp_faces, 0
+    rounds = ROUNDS_PER_CALL if rounds_per_call is None else int(rounds_per_call)
+    lib = L.lib()
+    ws = ops.workspace(lib.bdm_mesh_components_workspace_bytes(B, sum_v), dev, "mesh_components")
+    vf, ff = vert_first.data_ptr(), face_first.data_ptr()
+    L.check(lib.bdm_mesh_components_init(B, vf, ff, L.ptr(ws), L.stream()), "mesh_components_init")
+    changed = torch.zeros(1, dtype=torch.int32, device=dev)
+    bound = int((vert_first[1:] - vert_first[:-1]).max())   # a round of plain propagation fixes at least one more vertex
+    calls = 0
+    while True:
+        L.check(lib.bdm_mesh_components_rounds(B, rounds, vf, ff, L.ptr(nbr_first), L.ptr(nbr), L.ptr(changed), L.ptr(ws), L.stream()),
+                "mesh_components_rounds")
+        calls += 1
+        if int(changed.item()) == 0:   # the only synchronisation: one read per call
+            break
+        if calls * rounds > bound + 1:
+            raise L.BdmHipError(f"connected components: labels still change after {calls * rounds} rounds on meshes of at most {bound} vertices")
+    fc = face_comp if sum_f else torch.zeros(1, dtype=torch.int32, device=dev)   # no NULL among the outputs
+    L.check(lib.bdm_mesh_components_finish(B, L.ptr(faces), vf, ff, L.ptr(vert_comp), L.ptr(fc), L.ptr(comp_count), L.ptr(comp_verts),
+                                           L.ptr(comp_faces), L.ptr(ws), L.stream()), "mesh_components_finish")
+    return vert_comp, face_comp, comp_count, comp_verts, comp_faces, calls
+
+
+@torch.no_grad()
+def vertex_adjacency(meshes):
+    """The vertex adjacency of a batch as a CSR over the packed vertices -> (nbr_first (sum V + 1) int32, nbr int32): the neighbours of
+    packed vertex g are nbr[nbr_first[g] : nbr_first[g + 1]], ascending indices WITHIN its mesh, each once.  nbr has the upper bound of
+    six entries per face (no read-back sizes it); the entries from nbr_first[-1] on are -1.  Only faces whose three indices are in range
+    and pairwise different take part."""
+    verts_list, faces_list = _mesh_lists(meshes)
+    if not verts_list:
+        return torch.zeros(1, dtype=torch.int32), torch.zeros(0, dtype=torch.int32)
+    _, faces, vert_first, face_first = _packed(verts_list, faces_list)
+    return _adjacency(faces, vert_first, face_first)
+
+
+@torch.no_grad()
+def connected_components(meshes):
+    """Per mesh (vert_comp (V,) int64, face_comp (F,) int64, comp_verts (C,) int64, comp_faces (C,) int64): the component of every vertex
+    and face (-1 for a face that takes no part: an index out of range or repeated), components ranked by their smallest vertex index,
+    and the vertex and face counts of the C components.  A vertex no face uses is a component of its own."""
+    verts_list, faces_list = _mesh_lists(meshes)
+    if not verts_list:
+        return []
+    _, faces, vert_first, face_first = _packed(verts_list, faces_list)
+    nbr_first, nbr = _adjacency(faces, vert_first, face_first)
+    vert_comp, face_comp, comp_count, comp_verts, comp_faces, _ = _components(faces, vert_first, face_first, nbr_first, nbr)
+    counts = comp_count.cpu().tolist()   # the one read-back
+    nv, nf = (vert_first[1:] - vert_first[:-1]).tolist(), (face_first[1:] - face_first[:-1]).tolist()
+    return [(vc.long(), fc.long(), cv[:c].long(), cf[:c].long())
+            for vc, fc, cv, cf, c in zip(vert_comp.split(nv), face_comp.split(nf), comp_verts.split(nv), comp_faces.split(nv), counts)]
+
+
+def select_components(comp_faces, min_fraction=0.1, min_faces=1, keep_largest=False):
+    """(C,) bool: which components of ONE mesh stay.  A component stays iff comp_faces >= max(min_faces, ceil(min_fraction * the largest
+    comp_faces)); with keep_largest only the component of the most faces stays, the lower rank among equals."""
+    cf = torch.as_tensor(comp_faces).long()
+    if cf.numel() == 0:
+        return torch.zeros(0, dtype=torch.bool, device=cf.device)
+    top = int(cf.max())
+    if keep_largest:
+        keep = torch.zeros_like(cf, dtype=torch.bool)
+        keep[int((cf == top).nonzero()[0])] = True
+        return keep
+    return cf >= max(int(min_faces), math.ceil(min_fraction * top))
+
+
+def compact_mesh(verts, faces, vert_comp, face_comp, keep, colors=None):
+    """The kept vertices and the kept connected faces of one mesh in their original order, re-indexed (a boolean mask and a cumsum:
+    integer torch plumbing on the tensors' device) -> (verts, faces, colors or None)."""
+    vmask = keep[vert_comp] if keep.numel() else torch.zeros(verts.shape[0], dtype=torch.bool, device=verts.device)
+    fmask = face_comp >= 0
+    fmask[fmask.clone()] = keep[face_comp[fmask]]
+    new_index = torch.cumsum(vmask.long(), 0) - 1
+    return verts[vmask], new_index[faces[fmask].long()].to(faces.dtype), (None if colors is None else colors[vmask])
+
+
+def _check_selection(min_fraction, min_faces):
+    if not (isinstance(min_fraction, (int, float)) and 0.0 <= min_fraction <= 1.0):
+        raise ValueError(f"min_fraction={min_fraction!r} is outside 0..1")
+    if isinstance(min_faces, bool) or int(min_faces) != min_faces or min_faces < 0:
+        raise ValueError(f"min_faces={min_faces!r} is not a non-negative integer")
+
+
+@torch.no_grad()
+def remove_small_components(meshes, min_fraction=0.1, min_faces=1, keep_largest=False, colors_list=None, return_info=False):
+    """Drop the small floating islands of every mesh -> (verts_list, faces_list[, colors_list][, info]).  A component is kept iff its
+    face count is >= max(min_faces, ceil(min_fraction * the largest face count of its mesh)); keep_largest keeps the component of the
+    most faces only (the lower rank on a tie).  Kept vertices and faces stay in their original order and are re-indexed; faces with an
+    index out of range or repeated are always dropped; colors_list ((V_i, C) per mesh) is carried along.  A mesh that loses everything
+    becomes a legal empty mesh.  info: per mesh {"components", "removed_components", "removed_vertices", "removed_faces"}."""
+    _check_selection(min_fraction, min_faces)
+    verts_list, faces_list = _mesh_lists(meshes)
+    if colors_list is not None:
+        if not isinstance(colors_list, (list, tuple)) or len(colors_list) != len(verts_list):
+            raise ValueError("colors_list must be a list with one (V_i, C) tensor per mesh")
+        for c, v in zip(colors_list, verts_list):
+            if not torch.is_tensor(c) or c.dim() != 2 or c.shape[0] != v.shape[0]:
+                raise ValueError(f"a colour tensor is not ({v.shape[0]}, C)")
+    out_v, out_f, out_c, info = [], [], [], []
+    comps = connected_components((verts_list, faces_list))
+    for m, (verts, faces, (vert_comp, face_comp, _, comp_faces)) in enumerate(zip(verts_list, faces_list, comps)):
+        keep = select_components(comp_faces.cpu(), min_fraction, min_faces, keep_largest).to(verts.device)
+        v, f, c = compact_mesh(verts, faces, vert_comp, face_comp, keep, None if colors_list is None else colors_list[m])
+        out_v.append(v), out_f.append(f), out_c.append(c)
+        info.append({"components": int(keep.numel()), "removed_components": int((~keep).sum()), "removed_vertices": int(verts.shape[0] - v.shape[0]),
+                     "removed_faces": int(faces.shape[0] - f.shape[0])})
+    out = (out_v, out_f) + ((out_c,) if colors_list is not None else ()) + ((info,) if return_info else ())
+    return out
+
+
+def _check_taubin(lambd, mu, num_iter, weights):
+    if weights not in WEIGHTS:
+        raise ValueError(f"weights={weights!r} is none of {list(WEIGHTS)}")
+    if isinstance(num_iter, bool) or int(num_iter) != num_iter or not 0 <= num_iter <= MAX_ITER:
+        raise ValueError(f"num_iter={num_iter!r} is outside 0..{MAX_ITER}")
+    if not (math.isfinite(lambd) and math.isfinite(mu)):
+        raise ValueError("lambd and mu must be finite")
+
+
+@torch.no_grad()
+def taubin_smoothing(meshes, lambd=0.53, mu=-0.34, num_iter=10, *, weights="inverse_length"):
+    """pytorch3d's taubin_smoothing: num_iter times a Laplacian step with factor lambd, then one with factor mu, each the mean of the
+    neighbours weighted by the inverse edge length (pytorch3d's norm_laplacian) or, weights="uniform", equally -> Meshes with the
+    same faces.  A vertex without neighbours keeps its position.  Bad arguments raise ValueError before any launch."""
+    from .cameras import Meshes
+    _check_taubin(lambd, mu, num_iter, weights)
+    verts_list, faces_list = _mesh_lists(meshes)
+    if not verts_list:
+        return Meshes([], [])
+    verts, faces, vert_first, face_first = _packed(verts_list, faces_list)
+    B, sum_v, dev = len(verts_list), int(vert_first[-1]), verts.device
+    if sum_v == 0:
+        return Meshes([v.float() for v in verts_list], list(faces_list))
+    nbr_first, nbr = _adjacency(faces, vert_first, face_first)
+    out = torch.empty(sum_v, 3, dtype=torch.float32, device=dev)
+    lib = L.lib()
+    ws = ops.workspace(lib.bdm_mesh_taubin_workspace_bytes(B, sum_v), dev, "mesh_taubin")
+    L.check(lib.bdm_mesh_taubin(B, int(num_iter), WEIGHTS[weights], float(lambd), float(mu), L.ptr(verts), vert_first.data_ptr(),
+                                L.ptr(nbr_first), L.ptr(nbr), L.ptr(out), L.ptr(ws), L.stream()), "mesh_taubin")
+    return Meshes(list(out.split((vert_first[1:] - vert_first[:-1]).tolist())), list(faces_list))
+
+
+# ---- command line ------------------------------------------------------------------------------------------------------------------
+def compose_result(files, vertices_in, faces_in, vertices_out, faces_out, components, removed_components):
+    """The dictionary process_tree returns, from its seven sums."""
+    return {"files": files, "vertices_in": vertices_in, "faces_in": faces_in, "vertices_out": vertices_out, "faces_out": faces_out,
+            "components": components, "removed_components": removed_components}
+
+
+def process_tree(mesh_dir, out_dir, clean_fn, batch_size=16):
+    """Walk mesh_dir for mesh .ply files in sorted path order, up to batch_size files per call of clean_fn(verts_list, faces_list,
+    colors_list; host tensors of ragged sizes, a colour entry None for a file that carries none) -> (verts_list, faces_list,
+    colors_list, info as remove_small_components returns it; host tensors), and write out_dir/<same relative path>."""
+    from .io import load_mesh_ply, save_mesh_ply
+    mesh_dir, out_dir = Path(mesh_dir), Path(out_dir)
+    if batch_size < 1:
+        raise ValueError("batch_size must be positive")
+    items = [(path.relative_to(mesh_dir), path) for path in sorted(mesh_dir.rglob("*.ply"))]
+    sums = [0] * 7
+    for lo in range(0, len(items), batch_size):
+        chunk = items[lo:lo + batch_size]
+        loaded = [load_mesh_ply(path, with_colors=True) for _, path in chunk]
+        verts, faces, colors, info = clean_fn([torch.from_numpy(v) for v, _, _ in loaded], [torch.from_numpy(f) for _, f, _ in loaded],
+                                              [None if c is None else torch.from_numpy(c) for _, _, c in loaded])
+        for (rel, _), (v_in, f_in, _), v, f, c, i in zip(chunk, loaded, verts, faces, colors, info):
+            save_mesh_ply(v.numpy(), f.numpy(), out_dir / rel, colors=None if c is None else c.numpy())
+            for k, add in enumerate((1, v_in.shape[0], f_in.shape[0], v.shape[0], f.shape[0], i["components"], i["removed_components"])):
+                sums[k] += int(add)
+    return compose_result(*sums)
+
+
+def clean_batch(verts_list, faces_list, colors_list, device, min_fraction=0.1, min_faces=1, keep_largest=False, taubin_iters=10, lambd=0.53,
+                mu=-0.34, weights="inverse_length"):
+    """process_tree's clean_fn on the HIP path: islands first, smoothing second (taubin_iters == 0 skips it)."""
+    verts, faces = [v.to(device) for v in verts_list], [f.to(device) for f in faces_list]
+    V = [v.shape[0] for v in verts]
+    # files without colours ride along with a zero-width colour tensor, so that one call compacts all of them
+    cols = [torch.zeros(n, 0, device=device) if c is None else c.to(device) for c, n in zip(colors_list, V)]
+    verts, faces, cols, info = remove_small_components((verts, faces), min_fraction, min_faces, keep_largest, colors_list=cols, return_info=True)
+    if taubin_iters:
+        verts = taubin_smoothing((verts, faces), lambd, mu, taubin_iters, weights=weights).verts_list()
+    return ([v.cpu() for v in verts], [f.cpu() for f in faces], [None if c0 is None else c.cpu() for c, c0 in zip(cols, colors_list)], info)
+
+
+def parse_args(argv):
+    ap = argparse.ArgumentParser(prog="python -m bdm_amd.mesh_clean",
+                                 description="write a tree of triangle meshes again without small islands and Taubin-smoothed")
+    ap.add_argument("--mesh_dir", required=True, help="directory tree of triangle-mesh .ply files")
+    ap.add_argument("--out_dir", required=True)
+    ap.add_argument("--min-fraction", type=float, default=0.1, help="a component stays with at least this share of the largest one's faces")
+    ap.add_argument("--min-faces", type=int, default=1)
+    ap.add_argument("--keep-largest", action="store_true")
+    ap.add_argument("--taubin-iters", type=int, default=10, help="0 skips the smoothing")
+    ap.add_argument("--lambd", type=float, default=0.53)
+    ap.add_argument("--mu", type=float, default=-0.34)
+    ap.add_argument("--weights", choices=sorted(WEIGHTS), default="inverse_length")
+    ap.add_argument("--batch-size", type=int, default=16)
+    args = ap.parse_args(argv)
+    if args.batch_size < 1:
+        ap.error("--batch-size must be positive")
+    try:
+        _check_selection(args.min_fraction, args.min_faces)
+        _check_taubin(args.lambd, args.mu, args.taubin_iters, args.weights)
+    except ValueError as e:
+        ap.error(str(e))
+    return args
+
+
+def main(argv=None):
+    args = parse_args(sys.argv[1:] if argv is None else argv)
+    if not torch.cuda.is_available():
+        raise L.BdmHipError("bdm_amd.mesh_clean needs a HIP device (no CPU fallback)")
+    device = torch.device("cuda", torch.cuda.current_device())
+
+    def clean_fn(verts_list, faces_list, colors_list):
+        return clean_batch(verts_list, faces_list, colors_list, device, args.min_fraction, args.min_faces, args.keep_largest, args.taubin_iters,
+                           args.lambd, args.mu, args.weights)
+
+    result = process_tree(args.mesh_dir, args.out_dir, clean_fn, args.batch_size)
+    print(json.dumps(result))
+    return result
+
+
+if __name__ == "__main__":
+    main()

@@ -1206,6 +1206,77 @@ size_t bdm_knn_interpolate_workspace_bytes(int b);
 int bdm_knn_interpolate(int b, int k, int c, int mode, float eps, float fill, const float *attr, const int *idx, const float *d2,
                         const long long *q_first, const long long *r_first, float *out, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * 16. Mesh cleaning (csrc/mesh_clean.hip): the vertex adjacency of a packed batch of triangle meshes, its connected components, and
+ *     Taubin smoothing over it; the smoothing restates pytorch3d's taubin_smoothing (norm_laplacian weights) from its published
+ *     behaviour (pytorch3d is not installed: parity unpinned).  DESIGN.md section 20.
+ * ---------------------------------------------------------------------------------- */
+/* Meshes: verts, faces, vert_first, face_first exactly as bdm_point_mesh_distance takes them (packed, indices within the mesh, the
+ *   two offset arrays of b + 1 int64 in HOST memory, read during the call and free afterwards).
+ * Connected face: its three indices lie in [0, V) of its mesh and are pairwise different.  Coordinates are not looked at (this is
+ *   NOT section 14's valid face).  Every other face is ignored, not refused: the call cannot see it without reading device memory.
+ *
+ * bdm_mesh_adjacency: E(m) = the unordered pairs {a, c} that are a side of a connected face of mesh m.  N(i) = the ascending list of
+ *   the different j with {i, j} in E.  Output, a CSR over the packed vertices: nbr_first (sum V + 1) int32, nbr_first[0] = 0, and
+ *   nbr (6 sum F, the upper bound, allocated by the caller) int32; the list of packed vertex g is nbr[nbr_first[g] .. nbr_first[g + 1])
+ *   and holds indices WITHIN the mesh, as faces does.  Entries of nbr from nbr_first[sum V] on are left untouched.
+ *   The lists are sorted sets, so they do not depend on the order in which faces are visited or slots are claimed (integer atomics
+ *   claim the slots; count, scan and write are separate launches).  A vertex of very high valence is slow (one thread sorts its
+ *   list), never wrong.
+ *   workspace: bdm_mesh_adjacency_workspace_bytes(b, sum_v, sum_f) bytes: the offsets, two counters per vertex, the scan's partial sums
+ *     and the 6 sum F unsorted incidences.
+ *
+ * Components: label(i) = the smallest vertex index within the mesh among the vertices joined to i through E (a vertex without
+ *   neighbours is its own component).  The labels are the unique fixed point of the round
+ *     m_i = min(l_i, l_j for j in N(i));  l'_i = l_{m_i}   (one pointer jump; every read is of the labels before the round)
+ *   started from l_i = i, so the schedule of the rounds does not enter the result.
+ *   bdm_mesh_components_init writes the starting labels into the workspace.  bdm_mesh_components_rounds performs `rounds` >= 1
+ *   rounds and then writes *changed (one int32 on the device) = 1 if its LAST round changed a label, 0 otherwise; the caller
+ *   repeats the call until it reads 0 (at most V of the largest mesh rounds are ever needed: a round of plain propagation fixes
+ *   at least one more vertex).  bdm_mesh_components_finish, valid after a call that left *changed == 0, writes
+ *     vert_comp (sum V) int32: the rank of i's component among the components of its mesh, ordered by their smallest index;
+ *     face_comp (sum F) int32: the component of a connected face's vertices, -1 for every other face;
+ *     comp_count (b) int32; comp_verts, comp_faces (sum V each) int32: row vert_first[m] + c holds the number of vertices and of
+ *       connected faces of component c of mesh m (exact integer sums); the rows c >= comp_count[m] of a mesh are 0.
+ *   All three calls take the same b, offsets and workspace, which has to stay untouched between them.  An entry of nbr outside
+ *   [0, V) is skipped (nbr_first and nbr are meant to be bdm_mesh_adjacency's for the same offsets; they are not checked).
+ *   workspace: bdm_mesh_components_workspace_bytes(b, sum_v) bytes: the offsets, two label arrays, the rank scan and its partial sums.
+ *
+ * bdm_mesh_taubin: num_iter iterations; one iteration is a half-step with factor lambd, then a half-step with factor mu.  Every
+ *   half-step reads the positions of the previous one only (Jacobi).  Half-step with factor f at vertex i with neighbours
+ *   j_1 < ... < j_d, all float32, every operation rounded on its own (no FMA contraction), division and square root correctly rounded:
+ *     dx = x_i - x_j, dy, dz alike;  w_j = 1 / (sqrt((dx dx + dy dy) + dz dz) + 1e-12f) in mode 0 ("inverse_length", pytorch3d's
+ *     norm_laplacian), w_j = 1 in mode 1 ("uniform");
+ *     S = w_{j_1} v_{j_1}, then S = S + w_j v_j in ascending j, per component;  W = w_{j_1}, then W = W + w_j;
+ *     new_i = ((1 - f) v_i) + (f (S / W)) per component, 1 - f rounded once in float32.
+ *   d == 0: new_i = the bits of v_i (pytorch3d would form 0 / 0 here: a deliberate departure).  Nothing is special-cased for
+ *   non-finite coordinates: they spread to the neighbours by the formula (which NaN, sign and payload, is not part of the rule).
+ *   Two coincident neighbours give w = 1 / 1e-12f, finite.  num_iter == 0 copies verts to verts_out.  An entry of nbr outside [0, V)
+ *   is skipped, as above.  verts_out must not alias verts.
+ *   workspace: bdm_mesh_taubin_workspace_bytes(b, sum_v) bytes: the offsets and two arrays of 16-byte rows between which the
+ *     half-steps alternate (one load per neighbour); the last half-step writes verts_out.
+ *
+ * Limits (all): 0 <= b <= 65535, sum V < 2^31, 6 sum F < 2^31 (nbr_first is int32), offsets non-decreasing from 0, rounds >= 1,
+ *   0 <= num_iter <= 10000, mode in {0, 1}, lambd and mu finite, no NULL pointer, the workspace 16-byte aligned, no output and no part
+ *   of the workspace overlapping an input or another output (judged on byte ranges).  b == 0 or sum V == 0 returns 0 and launches
+ *   nothing; anything else outside the limits returns 1, launches nothing and leaves the outputs untouched.  The *_workspace_bytes
+ *   functions return 0 outside the limits.
+ * Determinism (all): integer atomics only (slot claims and counts), no floating-point atomics, no workgroup waits on another, every
+ *   loop is bounded by a launch argument or a segment length; mesh j of a batch has the bits of that mesh alone, and so has a
+ *   repeated call. */
+size_t bdm_mesh_adjacency_workspace_bytes(int b, long long sum_v, long long sum_f);
+int bdm_mesh_adjacency(int b, const int *faces, const long long *vert_first, const long long *face_first, int *nbr_first, int *nbr,
+                       void *workspace, void *stream);
+size_t bdm_mesh_components_workspace_bytes(int b, long long sum_v);
+int bdm_mesh_components_init(int b, const long long *vert_first, const long long *face_first, void *workspace, void *stream);
+int bdm_mesh_components_rounds(int b, int rounds, const long long *vert_first, const long long *face_first, const int *nbr_first,
+                               const int *nbr, int *changed, void *workspace, void *stream);
+int bdm_mesh_components_finish(int b, const int *faces, const long long *vert_first, const long long *face_first, int *vert_comp,
+                               int *face_comp, int *comp_count, int *comp_verts, int *comp_faces, void *workspace, void *stream);
+size_t bdm_mesh_taubin_workspace_bytes(int b, long long sum_v);
+int bdm_mesh_taubin(int b, int num_iter, int mode, float lambd, float mu, const float *verts, const long long *vert_first,
+                    const int *nbr_first, const int *nbr, float *verts_out, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
