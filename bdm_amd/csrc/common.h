@@ -76,6 +76,12 @@ __device__ __forceinline__ float sqdist3(float ax, float ay, float az, float bx,
   return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
 }
 
+#if defined(__HIPCC__)
+// neither NaN nor an infinity (every comparison with NaN is false)
+__device__ __forceinline__ bool finite1(float x) { return fabsf(x) < INFINITY; }
+__device__ __forceinline__ bool finite3(float x, float y, float z) { return finite1(x) && finite1(y) && finite1(z); }
+#endif
+
 // 64-lane reductions on DPP row operations (xor 1, xor 2, half-row mirror, row mirror: four single-pass moves inside a row of 16
 // lanes) + one readlane per row, rows combined in order 0..3: the result is wave-uniform.  The `__shfl_xor` butterflies these replace are
 // six DEPENDENT ds_bpermute round trips through the LDS crossbar per value (twelve for a double) -- measured 5.3 us for the 32 dot products

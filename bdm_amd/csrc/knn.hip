@@ -5,9 +5,9 @@
 // workgroup of four waves streams the entry's reference rows through LDS in tiles of KNN_TILE (x, y, z planes; a non-finite row and
 // the tail are stored as NaN), each lane holds one candidate per step and the neighbour list lives one entry per lane (knn_list.h).
 // blockIdx.y is the batch entry; the starts and lengths of its two sets come from the offset arrays, which travel as launch
-// arguments into the workspace (knn_offsets_kernel, the mechanism of mesh_metrics.hip).  A workgroup whose first query lies past
-// its entry's end leaves as a whole before the first barrier; inside a live workgroup the waves past the end clamp their queries
-// and write nothing, so no barrier sits under a divergent condition.
+// arguments into the workspace (send_offsets, ragged.h).  A workgroup whose first query lies past its entry's end leaves as a whole
+// before the first barrier; inside a live workgroup the waves past the end clamp their queries and write nothing, so no barrier sits
+// under a divergent condition.
 //
 // knn_interpolate_kernel: one thread per (query row, channel) of an entry.  Neighbouring threads hold neighbouring channels of one
 // row, so the gathers of attr rows and the stores are contiguous; the k indices and keys of the row are re-read by its c threads
@@ -15,6 +15,7 @@
 #include "common.h"
 #include "bdm_hip.h"
 #include "knn_list.h"
+#include "ragged.h"
 
 #include <limits.h>
 
@@ -29,26 +30,8 @@ constexpr int KNN_QPB = KNN_WAVES * KNN_QPW;      // queries per workgroup
 constexpr int KNN_TILE = 1024;                    // candidates per LDS tile: 3 planes of 4 KiB
 constexpr int KNN_MAX_B = 65535;                  // gridDim.y
 constexpr int KNN_MAX_C = 16;
-constexpr int KNN_OFFSETS_PER_LAUNCH = 32;
 
 namespace {
-
-struct KnnOffsetChunk {
-  long long q[KNN_OFFSETS_PER_LAUNCH], r[KNN_OFFSETS_PER_LAUNCH];
-};
-
-__global__ void knn_offsets_kernel(KnnOffsetChunk chunk, int first, int count, long long *__restrict__ q_first,
-                                   long long *__restrict__ r_first) {
-  const int i = threadIdx.x;
-  if (i < count) {  // count <= KNN_OFFSETS_PER_LAUNCH, first + count <= b + 1
-    q_first[first + i] = chunk.q[i];
-    r_first[first + i] = chunk.r[i];
-  }
-}
-
-__device__ __forceinline__ bool knn_finite3(float x, float y, float z) {
-  return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;  // false for NaN
-}
 
 __global__ __launch_bounds__(KNN_THREADS) void knn_points_kernel(int k, const float *__restrict__ queries,
                                                                  const float *__restrict__ refs,
@@ -72,7 +55,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_points_kernel(int k, const fl
   for (int q = 0; q < KNN_QPW; ++q) {
     const int qi = min(q0 + q, np - 1);  // a wave's queries past the entry's end repeat the last query and are not written
     qx[q] = qp[3 * (size_t)qi], qy[q] = qp[3 * (size_t)qi + 1], qz[q] = qp[3 * (size_t)qi + 2];
-    if (!knn_finite3(qx[q], qy[q], qz[q])) qx[q] = nan;  // accepts nobody
+    if (!finite3(qx[q], qy[q], qz[q])) qx[q] = nan;  // accepts nobody
     lkey[q] = thr[q] = KNN_EMPTY;
     lidx[q] = -1;
   }
@@ -84,7 +67,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_points_kernel(int k, const fl
       if (t < nr - base) {
         const float *p = rp + 3 * (size_t)(base + t);
         x = p[0], y = p[1], z = p[2];
-        if (!knn_finite3(x, y, z)) x = nan;  // nobody's neighbour
+        if (!finite3(x, y, z)) x = nan;  // nobody's neighbour
       }
       sx[t] = x, sy[t] = y, sz[t] = z;
     }
@@ -145,38 +128,13 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_interpolate_kernel(int k, int
   out[(size_t)row * c + ch] = m == 0 ? fill : (mode == 0 ? first : num / den);
 }
 
-bool knn_overlap(const void *a, size_t na, const void *b, size_t nb) {
-  if (!a || !b || na == 0 || nb == 0) return false;
-  const char *pa = (const char *)a, *pb = (const char *)b;
-  return pa < pb + nb && pb < pa + na;
-}
-
-size_t knn_ws_bytes(int b) { return (2 * sizeof(long long) * (size_t)(b + 1) + 15) & ~(size_t)15; }
-
 // the checks on the offset arrays both entry points share -> 0, or 1 with the error set; max_p = the largest query count
 int knn_check_offsets(const char *what, int b, const long long *q_first, const long long *r_first, long long &max_p) {
-  BDM_REQUIRE(q_first[0] == 0 && r_first[0] == 0, "%s: the offsets must start at 0", what);
-  max_p = 0;
-  for (int i = 0; i < b; ++i) {
-    BDM_REQUIRE(q_first[i + 1] >= q_first[i] && r_first[i + 1] >= r_first[i], "%s: offsets decrease at entry %d", what, i);
-    if (q_first[i + 1] - q_first[i] > max_p) max_p = q_first[i + 1] - q_first[i];
-  }
+  long long max_r = 0;
+  if (check_first(what, "entry", b, q_first, &max_p) != BDM_OK || check_first(what, "entry", b, r_first, &max_r) != BDM_OK) return BDM_ERR_ARG;
   BDM_REQUIRE(q_first[b] <= INT_MAX && r_first[b] <= INT_MAX, "%s: %lld queries or %lld reference rows reach 2^31", what, q_first[b],
               r_first[b]);
   return BDM_OK;
-}
-
-void knn_send_offsets(int b, const long long *q_first, const long long *r_first, void *workspace, hipStream_t s) {
-  long long *dev_q = (long long *)workspace, *dev_r = dev_q + (b + 1);
-  for (int first = 0; first <= b; first += KNN_OFFSETS_PER_LAUNCH) {
-    KnnOffsetChunk chunk;
-    const int count = (b + 1 - first) < KNN_OFFSETS_PER_LAUNCH ? (b + 1 - first) : KNN_OFFSETS_PER_LAUNCH;
-    for (int i = 0; i < KNN_OFFSETS_PER_LAUNCH; ++i) {
-      chunk.q[i] = i < count ? q_first[first + i] : 0;
-      chunk.r[i] = i < count ? r_first[first + i] : 0;
-    }
-    hipLaunchKernelGGL(knn_offsets_kernel, dim3(1), dim3(64), 0, s, chunk, first, count, dev_q, dev_r);
-  }
 }
 
 }  // namespace
@@ -186,7 +144,7 @@ using namespace bdm;
 
 extern "C" size_t bdm_knn_points_workspace_bytes(int b, long long sum_p, int k) {
   if (b < 0 || b > KNN_MAX_B || k < 1 || k > 64 || sum_p < 0 || sum_p > INT_MAX || sum_p * k > INT_MAX) return 0;
-  return knn_ws_bytes(b);
+  return offsets_bytes(b);
 }
 
 extern "C" int bdm_knn_points(int b, int k, const float *queries, const float *refs, const long long *q_first,
@@ -203,20 +161,13 @@ extern "C" int bdm_knn_points(int b, int k, const float *queries, const float *r
   BDM_REQUIRE(queries && refs && workspace, "knn_points: the queries, the reference rows or the workspace is NULL");
   BDM_REQUIRE(((uintptr_t)workspace & 15) == 0, "knn_points: the workspace is not 16-byte aligned");
   const size_t n = (size_t)sum_p * k;
-  const void *in[2] = {queries, refs};
-  const size_t in_bytes[2] = {12 * (size_t)sum_p, 12 * (size_t)sum_r};
-  const void *out[3] = {idx, d2, workspace};
-  const size_t out_bytes[3] = {4 * n, 4 * n, knn_ws_bytes(b)};
-  for (int o = 0; o < 3; ++o) {
-    for (int i = 0; i < 2; ++i)
-      BDM_REQUIRE(!knn_overlap(out[o], out_bytes[o], in[i], in_bytes[i]), "knn_points: output %d overlaps input %d", o, i);
-    for (int q = o + 1; q < 3; ++q)
-      BDM_REQUIRE(!knn_overlap(out[o], out_bytes[o], out[q], out_bytes[q]), "knn_points: outputs %d and %d overlap", o, q);
-  }
+  const Range in[2] = {{queries, 12 * (size_t)sum_p}, {refs, 12 * (size_t)sum_r}};
+  const Range out[3] = {{idx, 4 * n}, {d2, 4 * n}, {workspace, offsets_bytes(b)}};
+  if (check_overlap("knn_points", in, 2, out, 3) != BDM_OK) return BDM_ERR_ARG;
   if (!idx && !d2) return BDM_OK;  // nothing to write
   hipStream_t st = (hipStream_t)stream;
-  knn_send_offsets(b, q_first, r_first, workspace, st);
-  const long long *dev_q = (const long long *)workspace, *dev_r = dev_q + (b + 1);
+  long long *dev_q = (long long *)workspace, *dev_r = dev_q + (b + 1);
+  send_offsets(b, q_first, r_first, dev_q, dev_r, st);
   hipLaunchKernelGGL(knn_points_kernel, dim3((unsigned)cdivll(max_p, KNN_QPB), (unsigned)b), dim3(KNN_THREADS), 0, st, k, queries, refs,
                      dev_q, dev_r, idx, d2);
   return launch_status("knn_points");
@@ -224,7 +175,7 @@ extern "C" int bdm_knn_points(int b, int k, const float *queries, const float *r
 
 extern "C" size_t bdm_knn_interpolate_workspace_bytes(int b) {
   if (b < 0 || b > KNN_MAX_B) return 0;
-  return knn_ws_bytes(b);
+  return offsets_bytes(b);
 }
 
 extern "C" int bdm_knn_interpolate(int b, int k, int c, int mode, float eps, float fill, const float *attr, const int *idx,
@@ -245,17 +196,12 @@ extern "C" int bdm_knn_interpolate(int b, int k, int c, int mode, float eps, flo
   BDM_REQUIRE(attr && idx && d2 && out && workspace, "knn_interpolate: an input, the output or the workspace is NULL");
   BDM_REQUIRE(((uintptr_t)workspace & 15) == 0, "knn_interpolate: the workspace is not 16-byte aligned");
   const size_t n = (size_t)sum_p * k;
-  const void *in[3] = {attr, idx, d2};
-  const size_t in_bytes[3] = {4 * (size_t)sum_r * c, 4 * n, 4 * n};
-  const void *outp[2] = {out, workspace};
-  const size_t out_bytes[2] = {4 * (size_t)sum_p * c, knn_ws_bytes(b)};
-  for (int o = 0; o < 2; ++o)
-    for (int i = 0; i < 3; ++i)
-      BDM_REQUIRE(!knn_overlap(outp[o], out_bytes[o], in[i], in_bytes[i]), "knn_interpolate: output %d overlaps input %d", o, i);
-  BDM_REQUIRE(!knn_overlap(out, out_bytes[0], workspace, out_bytes[1]), "knn_interpolate: the output overlaps the workspace");
+  const Range in[3] = {{attr, 4 * (size_t)sum_r * c}, {idx, 4 * n}, {d2, 4 * n}};
+  const Range outs[2] = {{out, 4 * (size_t)sum_p * c}, {workspace, offsets_bytes(b)}};
+  if (check_overlap("knn_interpolate", in, 3, outs, 2) != BDM_OK) return BDM_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  knn_send_offsets(b, q_first, r_first, workspace, st);
-  const long long *dev_q = (const long long *)workspace, *dev_r = dev_q + (b + 1);
+  long long *dev_q = (long long *)workspace, *dev_r = dev_q + (b + 1);
+  send_offsets(b, q_first, r_first, dev_q, dev_r, st);
   hipLaunchKernelGGL(knn_interpolate_kernel, dim3((unsigned)cdivll(max_p * c, KNN_THREADS), (unsigned)b), dim3(KNN_THREADS), 0, st, k, c,
                      mode, eps, fill, attr, idx, d2, dev_q, dev_r, out);
   return launch_status("knn_interpolate");

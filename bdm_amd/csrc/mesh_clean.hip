@@ -9,7 +9,7 @@
 // order: lists are sorted sets, labels a unique fixed point, counts integer sums, float sums sequential per thread.
 //
 // Kernels.
-//   mc_offsets_kernel      the two host offset arrays travel as launch arguments, 32 entries per launch, into the workspace.
+//   (ragged.h)             send_offsets: the two host offset arrays travel as launch arguments into the workspace.
 //   mc_fill_kernel         an int array set to one value (counters, rows past the component count).
 //   mc_scan_kernel<false>  one workgroup per MC_CHUNK entries: their sum.  mc_scan_top_kernel: one workgroup, the exclusive scan of
 //   mc_scan_kernel<true>   those sums in place.  Then every workgroup scans its entries again, plus its offset: an exclusive scan in place.
@@ -24,6 +24,7 @@
 //                          neighbouring vertices, one 16-byte load per neighbour; LAST writes 12-byte rows to the output.
 #include "../../include/bdm_hip.h"
 #include "common.h"
+#include "ragged.h"
 
 #include <limits.h>
 #include <math.h>
@@ -35,24 +36,10 @@ using namespace bdm;
 #define MC_THREADS 256
 #define MC_CHUNK (4 * MC_THREADS)         // entries per workgroup of the scan
 #define MC_MAX_B 65535                    // gridDim.y
-#define MC_OFFSETS_PER_LAUNCH 32
 #define MC_INSERTION_MAX 32               // longer segments are heap-sorted
 #define MC_MAX_ITER 10000
 
 namespace {
-
-struct McOffsetChunk {
-  long long v[MC_OFFSETS_PER_LAUNCH], f[MC_OFFSETS_PER_LAUNCH];
-};
-
-__global__ void mc_offsets_kernel(McOffsetChunk chunk, int first, int count, long long *__restrict__ vert_first,
-                                  long long *__restrict__ face_first) {
-  const int i = threadIdx.x;
-  if (i < count) {  // count <= MC_OFFSETS_PER_LAUNCH, first + count <= b + 1
-    vert_first[first + i] = chunk.v[i];
-    face_first[first + i] = chunk.f[i];
-  }
-}
 
 __global__ __launch_bounds__(MC_THREADS) void mc_fill_kernel(int *__restrict__ a, long long n, int value) {
   const long long i = (long long)blockIdx.x * MC_THREADS + threadIdx.x;
@@ -60,22 +47,6 @@ __global__ __launch_bounds__(MC_THREADS) void mc_fill_kernel(int *__restrict__ a
 }
 
 // ---- exclusive scan of n int32 entries in place, in three launches ------------------------------------------------------------------
-// inclusive scan of one value per thread over the workgroup (Hillis-Steele in LDS) -> this thread's prefix; buf: MC_THREADS entries
-__device__ __forceinline__ int mc_block_scan(int v, int *buf) {
-  const int t = threadIdx.x;
-  buf[t] = v;
-  __syncthreads();
-  for (int off = 1; off < MC_THREADS; off <<= 1) {
-    const int add = t >= off ? buf[t - off] : 0;
-    __syncthreads();
-    buf[t] += add;
-    __syncthreads();
-  }
-  const int r = buf[t];
-  __syncthreads();   // buf is free again
-  return r;
-}
-
 template <bool WRITE>
 __global__ __launch_bounds__(MC_THREADS) void mc_scan_kernel(int *__restrict__ a, long long n, int *__restrict__ bsum) {
   __shared__ int buf[MC_THREADS];
@@ -84,7 +55,7 @@ __global__ __launch_bounds__(MC_THREADS) void mc_scan_kernel(int *__restrict__ a
 #pragma unroll
   for (int e = 0; e < 4; ++e) v[e] = base + e < n ? a[base + e] : 0;
   const int s = (v[0] + v[1]) + (v[2] + v[3]);
-  const int incl = mc_block_scan(s, buf);
+  const int incl = block_scan<int, MC_THREADS>(s, buf);
   if (WRITE) {
     int run = bsum[blockIdx.x] + incl - s;
 #pragma unroll
@@ -103,7 +74,7 @@ __global__ __launch_bounds__(MC_THREADS) void mc_scan_top_kernel(int *__restrict
   for (int c0 = 0; c0 < nb; c0 += MC_THREADS) {   // uniform trip count
     const int i = c0 + threadIdx.x;
     const int v = i < nb ? bsum[i] : 0;
-    const int incl = mc_block_scan(v, buf);
+    const int incl = block_scan<int, MC_THREADS>(v, buf);
     if (i < nb) bsum[i] = carry + incl - v;
     buf[threadIdx.x] = incl;
     __syncthreads();
@@ -345,14 +316,6 @@ __global__ __launch_bounds__(MC_THREADS) void mc_taubin_kernel(float f, float om
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
-bool mc_overlap(const void *a, size_t na, const void *b, size_t nb) {
-  if (!a || !b || na == 0 || nb == 0) return false;
-  const char *pa = (const char *)a, *pb = (const char *)b;
-  return pa < pb + nb && pb < pa + na;
-}
-
-size_t mc_pad(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
-size_t mc_offsets_bytes(int b) { return mc_pad(2 * sizeof(long long) * (size_t)(b + 1)); }
 long long mc_scan_blocks(long long n) { return cdivll(n, MC_CHUNK); }
 
 bool mc_sizes_ok(int b, long long sum_v, long long sum_f) {
@@ -369,11 +332,11 @@ McAdjWs mc_adj_ws(void *ws, int b, long long sum_v, long long sum_f) {
   char *p = (char *)ws;
   McAdjWs w;
   w.vert_first = (long long *)p, w.face_first = w.vert_first + (b + 1);
-  size_t o = mc_offsets_bytes(b);
-  w.first = (int *)(p + o), o += mc_pad(4 * (size_t)(sum_v + 1));
-  w.cursor = (int *)(p + o), o += mc_pad(4 * (size_t)(sum_v + 1));
-  w.bsum = (int *)(p + o), o += mc_pad(4 * (size_t)mc_scan_blocks(sum_v + 1));
-  w.raw = (int *)(p + o), o += mc_pad(4 * 6 * (size_t)sum_f);
+  size_t o = offsets_bytes(b);
+  w.first = (int *)(p + o), o += align16(4 * (size_t)(sum_v + 1));
+  w.cursor = (int *)(p + o), o += align16(4 * (size_t)(sum_v + 1));
+  w.bsum = (int *)(p + o), o += align16(4 * (size_t)mc_scan_blocks(sum_v + 1));
+  w.raw = (int *)(p + o), o += align16(4 * 6 * (size_t)sum_f);
   w.bytes = o;
   return w;
 }
@@ -388,43 +351,25 @@ McCompWs mc_comp_ws(void *ws, int b, long long sum_v) {
   char *p = (char *)ws;
   McCompWs w;
   w.vert_first = (long long *)p, w.face_first = w.vert_first + (b + 1);
-  size_t o = mc_offsets_bytes(b);
-  w.label = (int *)(p + o), o += mc_pad(4 * (size_t)sum_v);
-  w.label2 = (int *)(p + o), o += mc_pad(4 * (size_t)sum_v);
-  w.rank = (int *)(p + o), o += mc_pad(4 * (size_t)(sum_v + 1));
-  w.bsum = (int *)(p + o), o += mc_pad(4 * (size_t)mc_scan_blocks(sum_v + 1));
+  size_t o = offsets_bytes(b);
+  w.label = (int *)(p + o), o += align16(4 * (size_t)sum_v);
+  w.label2 = (int *)(p + o), o += align16(4 * (size_t)sum_v);
+  w.rank = (int *)(p + o), o += align16(4 * (size_t)(sum_v + 1));
+  w.bsum = (int *)(p + o), o += align16(4 * (size_t)mc_scan_blocks(sum_v + 1));
   w.bytes = o;
   return w;
 }
 
-size_t mc_taubin_bytes(int b, long long sum_v) { return mc_offsets_bytes(b) + 2 * 16 * (size_t)sum_v; }
+size_t mc_taubin_bytes(int b, long long sum_v) { return offsets_bytes(b) + 2 * 16 * (size_t)sum_v; }
 
 // the checks on the offset arrays every entry point shares -> 0, or 1 with the error set; face_first may be NULL (not used by the call)
 int mc_check_offsets(const char *what, int b, const long long *vert_first, const long long *face_first, long long &max_v, long long &max_f) {
-  BDM_REQUIRE(vert_first[0] == 0 && (!face_first || face_first[0] == 0), "%s: the offsets must start at 0", what);
-  max_v = max_f = 0;
-  for (int i = 0; i < b; ++i) {
-    BDM_REQUIRE(vert_first[i + 1] >= vert_first[i] && (!face_first || face_first[i + 1] >= face_first[i]), "%s: offsets decrease at mesh %d",
-                what, i);
-    if (vert_first[i + 1] - vert_first[i] > max_v) max_v = vert_first[i + 1] - vert_first[i];
-    if (face_first && face_first[i + 1] - face_first[i] > max_f) max_f = face_first[i + 1] - face_first[i];
-  }
+  max_f = 0;
+  if (check_first(what, "mesh", b, vert_first, &max_v) != BDM_OK) return BDM_ERR_ARG;
+  if (face_first && check_first(what, "mesh", b, face_first, &max_f) != BDM_OK) return BDM_ERR_ARG;
   BDM_REQUIRE(vert_first[b] < INT_MAX, "%s: %lld vertices reach 2^31", what, vert_first[b]);
   BDM_REQUIRE(!face_first || 6 * face_first[b] <= INT_MAX, "%s: %lld faces: six entries per face reach 2^31", what, face_first[b]);
   return BDM_OK;
-}
-
-void mc_send_offsets(int b, const long long *vert_first, const long long *face_first, void *workspace, hipStream_t s) {
-  long long *dev_v = (long long *)workspace, *dev_f = dev_v + (b + 1);
-  for (int first = 0; first <= b; first += MC_OFFSETS_PER_LAUNCH) {
-    McOffsetChunk chunk;
-    const int count = (b + 1 - first) < MC_OFFSETS_PER_LAUNCH ? (b + 1 - first) : MC_OFFSETS_PER_LAUNCH;
-    for (int i = 0; i < MC_OFFSETS_PER_LAUNCH; ++i) {
-      chunk.v[i] = i < count ? vert_first[first + i] : 0;
-      chunk.f[i] = i < count && face_first ? face_first[first + i] : 0;
-    }
-    hipLaunchKernelGGL(mc_offsets_kernel, dim3(1), dim3(64), 0, s, chunk, first, count, dev_v, dev_f);
-  }
 }
 
 void mc_fill(int *a, long long n, int value, hipStream_t s) {
@@ -454,21 +399,6 @@ int mc_prologue(const char *what, int b, const long long *vert_first, const long
   return BDM_OK;
 }
 
-struct McRange {
-  const void *p;
-  size_t bytes;
-};
-// no output overlaps an input or another output
-int mc_check_overlap(const char *what, const McRange *in, int n_in, const McRange *out, int n_out) {
-  for (int o = 0; o < n_out; ++o) {
-    for (int i = 0; i < n_in; ++i)
-      BDM_REQUIRE(!mc_overlap(out[o].p, out[o].bytes, in[i].p, in[i].bytes), "%s: output %d overlaps input %d", what, o, i);
-    for (int q = o + 1; q < n_out; ++q)
-      BDM_REQUIRE(!mc_overlap(out[o].p, out[o].bytes, out[q].p, out[q].bytes), "%s: outputs %d and %d overlap", what, o, q);
-  }
-  return BDM_OK;
-}
-
 }  // namespace
 
 extern "C" size_t bdm_mesh_adjacency_workspace_bytes(int b, long long sum_v, long long sum_f) {
@@ -485,11 +415,11 @@ extern "C" int bdm_mesh_adjacency(int b, const int *faces, const long long *vert
   const long long sum_v = vert_first[b], sum_f = face_first[b];
   BDM_REQUIRE(faces && nbr_first && nbr, "mesh_adjacency: the faces or an output is NULL");
   const McAdjWs w = mc_adj_ws(workspace, b, sum_v, sum_f);
-  const McRange in[1] = {{faces, 12 * (size_t)sum_f}};
-  const McRange out[3] = {{nbr_first, 4 * (size_t)(sum_v + 1)}, {nbr, 24 * (size_t)sum_f}, {workspace, w.bytes}};
-  if (mc_check_overlap("mesh_adjacency", in, 1, out, 3) != BDM_OK) return BDM_ERR_ARG;
+  const Range in[1] = {{faces, 12 * (size_t)sum_f}};
+  const Range out[3] = {{nbr_first, 4 * (size_t)(sum_v + 1)}, {nbr, 24 * (size_t)sum_f}, {workspace, w.bytes}};
+  if (check_overlap("mesh_adjacency", in, 1, out, 3) != BDM_OK) return BDM_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  mc_send_offsets(b, vert_first, face_first, workspace, st);
+  send_offsets(b, vert_first, face_first, w.vert_first, w.face_first, st);
   mc_fill(w.first, sum_v + 1, 0, st);
   mc_fill(w.cursor, sum_v + 1, 0, st);
   const unsigned flat_v = (unsigned)cdivll(sum_v + 1, MC_THREADS);
@@ -518,7 +448,7 @@ extern "C" int bdm_mesh_components_init(int b, const long long *vert_first, cons
   if (nothing) return BDM_OK;
   const McCompWs w = mc_comp_ws(workspace, b, vert_first[b]);
   hipStream_t st = (hipStream_t)stream;
-  mc_send_offsets(b, vert_first, face_first, workspace, st);
+  send_offsets(b, vert_first, face_first, w.vert_first, w.face_first, st);
   hipLaunchKernelGGL(mc_label_init_kernel, dim3((unsigned)cdivll(max_v, MC_THREADS), (unsigned)b), dim3(MC_THREADS), 0, st, w.vert_first, w.label);
   return launch_status("mesh_components_init");
 }
@@ -533,9 +463,9 @@ extern "C" int bdm_mesh_components_rounds(int b, int rounds, const long long *ve
   const long long sum_v = vert_first[b], sum_f = face_first[b];
   BDM_REQUIRE(nbr_first && nbr && changed, "mesh_components_rounds: the adjacency or the flag is NULL");
   const McCompWs w = mc_comp_ws(workspace, b, sum_v);
-  const McRange in[2] = {{nbr_first, 4 * (size_t)(sum_v + 1)}, {nbr, 24 * (size_t)sum_f}};
-  const McRange out[2] = {{changed, 4}, {workspace, w.bytes}};
-  if (mc_check_overlap("mesh_components_rounds", in, 2, out, 2) != BDM_OK) return BDM_ERR_ARG;
+  const Range in[2] = {{nbr_first, 4 * (size_t)(sum_v + 1)}, {nbr, 24 * (size_t)sum_f}};
+  const Range out[2] = {{changed, 4}, {workspace, w.bytes}};
+  if (check_overlap("mesh_components_rounds", in, 2, out, 2) != BDM_OK) return BDM_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(mc_flag_kernel, dim3(1), dim3(64), 0, st, changed);
   const dim3 grid((unsigned)cdivll(max_v, MC_THREADS), (unsigned)b);
@@ -560,10 +490,10 @@ extern "C" int bdm_mesh_components_finish(int b, const int *faces, const long lo
   const long long sum_v = vert_first[b], sum_f = face_first[b];
   BDM_REQUIRE(faces && vert_comp && face_comp && comp_count && comp_verts && comp_faces, "mesh_components_finish: the faces or an output is NULL");
   const McCompWs w = mc_comp_ws(workspace, b, sum_v);
-  const McRange in[1] = {{faces, 12 * (size_t)sum_f}};
-  const McRange out[6] = {{vert_comp, 4 * (size_t)sum_v}, {face_comp, 4 * (size_t)sum_f}, {comp_count, 4 * (size_t)b},
+  const Range in[1] = {{faces, 12 * (size_t)sum_f}};
+  const Range out[6] = {{vert_comp, 4 * (size_t)sum_v}, {face_comp, 4 * (size_t)sum_f}, {comp_count, 4 * (size_t)b},
                           {comp_verts, 4 * (size_t)sum_v}, {comp_faces, 4 * (size_t)sum_v}, {workspace, w.bytes}};
-  if (mc_check_overlap("mesh_components_finish", in, 1, out, 6) != BDM_OK) return BDM_ERR_ARG;
+  if (check_overlap("mesh_components_finish", in, 1, out, 6) != BDM_OK) return BDM_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid_v((unsigned)cdivll(max_v, MC_THREADS), (unsigned)b);
   hipLaunchKernelGGL(mc_root_kernel, grid_v, dim3(MC_THREADS), 0, st, w.vert_first, sum_v, w.label, w.rank);
@@ -594,18 +524,18 @@ extern "C" int bdm_mesh_taubin(int b, int num_iter, int mode, float lambd, float
   const long long sum_v = vert_first[b];
   BDM_REQUIRE(verts && nbr_first && nbr && verts_out, "mesh_taubin: an input or the output is NULL");
   // the length of nbr is on the device (nbr_first[sum V]); its first entry stands for it in the overlap test
-  const McRange in[3] = {{verts, 12 * (size_t)sum_v}, {nbr_first, 4 * (size_t)(sum_v + 1)}, {nbr, 4}};
-  const McRange out[2] = {{verts_out, 12 * (size_t)sum_v}, {workspace, mc_taubin_bytes(b, sum_v)}};
-  if (mc_check_overlap("mesh_taubin", in, 3, out, 2) != BDM_OK) return BDM_ERR_ARG;
+  const Range in[3] = {{verts, 12 * (size_t)sum_v}, {nbr_first, 4 * (size_t)(sum_v + 1)}, {nbr, 4}};
+  const Range out[2] = {{verts_out, 12 * (size_t)sum_v}, {workspace, mc_taubin_bytes(b, sum_v)}};
+  if (check_overlap("mesh_taubin", in, 3, out, 2) != BDM_OK) return BDM_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   const unsigned flat_v = (unsigned)cdivll(sum_v, MC_THREADS);
   if (num_iter == 0) {
     hipLaunchKernelGGL(mc_copy_rows_kernel, dim3((unsigned)cdivll(3 * sum_v, MC_THREADS)), dim3(MC_THREADS), 0, st, 3 * sum_v, verts, verts_out);
     return launch_status("mesh_taubin");
   }
-  mc_send_offsets(b, vert_first, nullptr, workspace, st);
-  const long long *dev_v = (const long long *)workspace;
-  float4 *rows_a = (float4 *)((char *)workspace + mc_offsets_bytes(b)), *rows_b = rows_a + sum_v;
+  long long *dev_v = (long long *)workspace;
+  send_offsets(b, vert_first, nullptr, dev_v, dev_v + (b + 1), st);
+  float4 *rows_a = (float4 *)((char *)workspace + offsets_bytes(b)), *rows_b = rows_a + sum_v;
   hipLaunchKernelGGL(mc_stage_kernel, dim3(flat_v), dim3(MC_THREADS), 0, st, sum_v, verts, rows_a);
   const dim3 grid((unsigned)cdivll(max_v, MC_THREADS), (unsigned)b);
   const float one_minus[2] = {1.0f - lambd, 1.0f - mu};   // rounded once, in float32

@@ -9,7 +9,7 @@
 // depends on execution order: the sums are integers, the only atomic is an integer maximum.
 //
 // Kernels.
-//   mm_offsets_kernel   the two host offset arrays travel as launch arguments, 32 entries per launch, into the workspace.
+//   (ragged.h)          send_offsets: the two host offset arrays travel as launch arguments into the workspace.
 //   mm_area_kernel      one thread per face: a = sqrt(nn) (0 = invalid) into the workspace, atomicMax of its bits per mesh.
 //   mm_count_write_kernel<false>  one workgroup per MM_THREADS faces: the sum of their q.
 //   mm_scan_kernel      one workgroup per mesh: exclusive scan of the workgroup sums in place, the total.
@@ -21,6 +21,7 @@
 //                       conflict, one ds_read_b128 per 16 bytes for the whole wave); the running (sqdist, face) stays in registers.
 #include "../../include/bdm_hip.h"
 #include "common.h"
+#include "ragged.h"
 
 #include <limits.h>
 
@@ -32,25 +33,10 @@ using namespace bdm;
 #define MM_TILE 256                       // faces per LDS tile of mm_dist_kernel: 16 KiB
 #define MM_MAX_FACES (1 << 24)            // per mesh: C_last <= 2^54
 #define MM_MAX_B 65535                    // gridDim.y
-#define MM_OFFSETS_PER_LAUNCH 32
 #define MM_Q_ONE 1073741824.f             // 2^30
 
 namespace {
 
-struct MmOffsetChunk {
-  long long v[MM_OFFSETS_PER_LAUNCH], f[MM_OFFSETS_PER_LAUNCH];
-};
-
-__global__ void mm_offsets_kernel(MmOffsetChunk chunk, int first, int count, long long *__restrict__ vert_first,
-                                  long long *__restrict__ face_first) {
-  const int i = threadIdx.x;
-  if (i < count) {  // count <= MM_OFFSETS_PER_LAUNCH, first + count <= b + 1
-    vert_first[first + i] = chunk.v[i];
-    face_first[first + i] = chunk.f[i];
-  }
-}
-
-__device__ __forceinline__ bool mm_finite(float x) { return fabsf(x) < INFINITY; }   // false for NaN
 __device__ __forceinline__ float mm_dot(float ax, float ay, float az, float bx, float by, float bz) {
   return (ax * bx + ay * by) + az * bz;
 }
@@ -71,8 +57,8 @@ __device__ __forceinline__ bool mm_face_load(const float *__restrict__ verts, co
   f.v0x = a[0]; f.v0y = a[1]; f.v0z = a[2];
   f.v1x = b[0]; f.v1y = b[1]; f.v1z = b[2];
   f.v2x = c[0]; f.v2y = c[1]; f.v2z = c[2];
-  if (!(mm_finite(f.v0x) && mm_finite(f.v0y) && mm_finite(f.v0z) && mm_finite(f.v1x) && mm_finite(f.v1y) && mm_finite(f.v1z) &&
-        mm_finite(f.v2x) && mm_finite(f.v2y) && mm_finite(f.v2z)))
+  if (!(finite1(f.v0x) && finite1(f.v0y) && finite1(f.v0z) && finite1(f.v1x) && finite1(f.v1y) && finite1(f.v1z) &&
+        finite1(f.v2x) && finite1(f.v2y) && finite1(f.v2z)))
     return false;
   const float ex = f.v1x - f.v0x, ey = f.v1y - f.v0y, ez = f.v1z - f.v0z;   // e_0
   const float gx = f.v2x - f.v0x, gy = f.v2y - f.v0y, gz = f.v2z - f.v0z;   // g
@@ -105,22 +91,6 @@ __device__ __forceinline__ long long mm_weight(float a, float amax) {
   return a > 0.f ? (long long)rintf((a / amax) * MM_Q_ONE) : 0ll;   // a > 0 implies amax >= a > 0
 }
 
-// inclusive scan of one value per thread over the workgroup (Hillis-Steele in LDS) -> this thread's prefix; buf: MM_THREADS entries
-__device__ __forceinline__ long long mm_block_scan(long long v, long long *buf) {
-  const int t = threadIdx.x;
-  buf[t] = v;
-  __syncthreads();
-  for (int off = 1; off < MM_THREADS; off <<= 1) {
-    const long long add = t >= off ? buf[t - off] : 0ll;
-    __syncthreads();
-    buf[t] += add;
-    __syncthreads();
-  }
-  const long long r = buf[t];
-  __syncthreads();   // buf is free again
-  return r;
-}
-
 template <bool WRITE>
 __global__ __launch_bounds__(MM_THREADS) void mm_count_write_kernel(int nb_max, const long long *__restrict__ face_first,
                                                                     const float *__restrict__ area,
@@ -134,7 +104,7 @@ __global__ __launch_bounds__(MM_THREADS) void mm_count_write_kernel(int nb_max, 
   const long long i = first + threadIdx.x;
   const float amax = __uint_as_float(amax_bits[m]);
   const long long q = i < nf ? mm_weight(area[base + i], amax) : 0ll;
-  const long long incl = mm_block_scan(q, buf);
+  const long long incl = block_scan<long long, MM_THREADS>(q, buf);
   if (WRITE) {
     if (i < nf) cum[base + i] = bsum[(size_t)m * nb_max + blockIdx.x] + incl;
   } else if (threadIdx.x == MM_THREADS - 1) {
@@ -154,7 +124,7 @@ __global__ __launch_bounds__(MM_THREADS) void mm_scan_kernel(int nb_max, const l
   for (int c0 = 0; c0 < nb; c0 += MM_THREADS) {   // uniform trip count
     const int i = c0 + threadIdx.x;
     const long long v = i < nb ? a[i] : 0ll;
-    const long long incl = mm_block_scan(v, buf);
+    const long long incl = block_scan<long long, MM_THREADS>(v, buf);
     if (i < nb) a[i] = carry + incl - v;
     buf[threadIdx.x] = incl;
     __syncthreads();
@@ -323,21 +293,13 @@ __global__ __launch_bounds__(MM_THREADS) void mm_dist_kernel(int p, const float 
     }
   }
   if (!live) return;
-  if (!(mm_finite(x) && mm_finite(y) && mm_finite(z))) { best = INFINITY; idx = -1; }
+  if (!(finite1(x) && finite1(y) && finite1(z))) { best = INFINITY; idx = -1; }
   const size_t o = (size_t)m * p + pt;
   sqdist[o] = best;
   face_idx[o] = idx;
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
-bool mm_overlap(const void *a, size_t na, const void *b, size_t nb) {
-  if (!a || !b || na == 0 || nb == 0) return false;
-  const char *pa = (const char *)a, *pb = (const char *)b;
-  return pa < pb + nb && pb < pa + na;
-}
-
-size_t mm_align(size_t x) { return (x + 15) & ~(size_t)15; }
-
 struct MmSampleWs {
   long long *vert_first, *face_first;  // [b + 1] each
   long long *total;                    // [b]
@@ -361,7 +323,7 @@ MmSampleWs mm_sample_ws(void *ws, int b, long long sum_f, long long max_faces) {
   w.cum = (long long *)(p + off); off += sizeof(long long) * (size_t)sum_f;
   w.amax_bits = (unsigned int *)(p + off); off += sizeof(unsigned int) * (size_t)b;
   w.area = (float *)(p + off); off += sizeof(float) * (size_t)sum_f;
-  w.bytes = mm_align(off);
+  w.bytes = align16(off);
   return w;
 }
 
@@ -378,35 +340,18 @@ MmDistWs mm_dist_ws(void *ws, int b, long long sum_f) {
   w.rec = (float4 *)p;
   w.vert_first = (long long *)(p + rec_bytes);
   w.face_first = w.vert_first + (b + 1);
-  w.bytes = mm_align(rec_bytes + 2 * sizeof(long long) * (size_t)(b + 1));
+  w.bytes = rec_bytes + offsets_bytes(b);   // rec_bytes is a multiple of 64
   return w;
 }
 
 // the checks on the offset arrays both entry points share -> 0, or 1 with the error set; max_f = the largest face count
 int mm_check_offsets(const char *what, int b, const long long *vert_first, const long long *face_first, long long &max_f) {
-  BDM_REQUIRE(vert_first[0] == 0 && face_first[0] == 0, "%s: the offsets must start at 0", what);
-  max_f = 0;
-  for (int m = 0; m < b; ++m) {
-    BDM_REQUIRE(vert_first[m + 1] >= vert_first[m] && face_first[m + 1] >= face_first[m], "%s: offsets decrease at mesh %d", what, m);
-    const long long nf = face_first[m + 1] - face_first[m];
-    BDM_REQUIRE(nf <= MM_MAX_FACES, "%s: mesh %d has %lld faces, more than %d", what, m, nf, MM_MAX_FACES);
-    if (nf > max_f) max_f = nf;
-  }
+  long long max_v = 0;
+  if (check_first(what, "mesh", b, vert_first, &max_v) != BDM_OK || check_first(what, "mesh", b, face_first, &max_f) != BDM_OK) return BDM_ERR_ARG;
+  BDM_REQUIRE(max_f <= MM_MAX_FACES, "%s: a mesh has %lld faces, more than %d", what, max_f, MM_MAX_FACES);
   BDM_REQUIRE(vert_first[b] <= INT_MAX && face_first[b] <= INT_MAX, "%s: %lld vertices or %lld faces reach 2^31", what, vert_first[b],
               face_first[b]);
   return BDM_OK;
-}
-
-void mm_send_offsets(int b, const long long *vert_first, const long long *face_first, long long *dev_v, long long *dev_f, hipStream_t s) {
-  for (int first = 0; first <= b; first += MM_OFFSETS_PER_LAUNCH) {
-    MmOffsetChunk chunk;
-    const int count = (b + 1 - first) < MM_OFFSETS_PER_LAUNCH ? (b + 1 - first) : MM_OFFSETS_PER_LAUNCH;
-    for (int i = 0; i < MM_OFFSETS_PER_LAUNCH; ++i) {
-      chunk.v[i] = i < count ? vert_first[first + i] : 0;
-      chunk.f[i] = i < count ? face_first[first + i] : 0;
-    }
-    hipLaunchKernelGGL(mm_offsets_kernel, dim3(1), dim3(64), 0, s, chunk, first, count, dev_v, dev_f);
-  }
 }
 
 bool mm_sizes_ok(int b, long long sum_f) { return b >= 0 && b <= MM_MAX_B && sum_f >= 0 && sum_f <= INT_MAX; }
@@ -435,18 +380,11 @@ extern "C" int bdm_mesh_sample_points(int b, int s, long long max_faces, const f
   const long long sum_v = vert_first[b], sum_f = face_first[b];
   const MmSampleWs ws = mm_sample_ws(workspace, b, sum_f, max_f);
   const size_t n = (size_t)b * s;
-  const void *in[3] = {verts, faces, keys};
-  const size_t in_bytes[3] = {12 * (size_t)sum_v, 12 * (size_t)sum_f, 8 * (size_t)b};
-  const void *out[4] = {points, face_idx, normals, workspace};
-  const size_t out_bytes[4] = {12 * n, 4 * n, 12 * n, ws.bytes};
-  for (int o = 0; o < 4; ++o) {
-    for (int i = 0; i < 3; ++i)
-      BDM_REQUIRE(!mm_overlap(out[o], out_bytes[o], in[i], in_bytes[i]), "mesh_sample_points: output %d overlaps input %d", o, i);
-    for (int q = o + 1; q < 4; ++q)
-      BDM_REQUIRE(!mm_overlap(out[o], out_bytes[o], out[q], out_bytes[q]), "mesh_sample_points: outputs %d and %d overlap", o, q);
-  }
+  const Range in[3] = {{verts, 12 * (size_t)sum_v}, {faces, 12 * (size_t)sum_f}, {keys, 8 * (size_t)b}};
+  const Range out[4] = {{points, 12 * n}, {face_idx, 4 * n}, {normals, 12 * n}, {workspace, ws.bytes}};
+  if (check_overlap("mesh_sample_points", in, 3, out, 4) != BDM_OK) return BDM_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  mm_send_offsets(b, vert_first, face_first, ws.vert_first, ws.face_first, st);
+  send_offsets(b, vert_first, face_first, ws.vert_first, ws.face_first, st);
   if (hipMemsetAsync(ws.amax_bits, 0, sizeof(unsigned int) * (size_t)b, st) != hipSuccess) return launch_status("mesh_sample_points (memset)");
   if (ws.nb_max > 0) {
     const dim3 grid((unsigned)ws.nb_max, (unsigned)b);
@@ -491,18 +429,11 @@ extern "C" int bdm_point_mesh_distance(int b, int p, int form, const float *vert
   const long long sum_v = vert_first[b], sum_f = face_first[b];
   const MmDistWs ws = mm_dist_ws(workspace, b, sum_f);
   const size_t n = (size_t)b * p;
-  const void *in[4] = {verts, faces, points, order};
-  const size_t in_bytes[4] = {12 * (size_t)sum_v, 12 * (size_t)sum_f, 12 * n, 4 * n};
-  const void *out[3] = {sqdist, face_idx, workspace};
-  const size_t out_bytes[3] = {4 * n, 4 * n, ws.bytes};
-  for (int o = 0; o < 3; ++o) {
-    for (int i = 0; i < 4; ++i)
-      BDM_REQUIRE(!mm_overlap(out[o], out_bytes[o], in[i], in_bytes[i]), "point_mesh_distance: output %d overlaps input %d", o, i);
-    for (int q = o + 1; q < 3; ++q)
-      BDM_REQUIRE(!mm_overlap(out[o], out_bytes[o], out[q], out_bytes[q]), "point_mesh_distance: outputs %d and %d overlap", o, q);
-  }
+  const Range in[4] = {{verts, 12 * (size_t)sum_v}, {faces, 12 * (size_t)sum_f}, {points, 12 * n}, {order, 4 * n}};
+  const Range out[3] = {{sqdist, 4 * n}, {face_idx, 4 * n}, {workspace, ws.bytes}};
+  if (check_overlap("point_mesh_distance", in, 4, out, 3) != BDM_OK) return BDM_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  mm_send_offsets(b, vert_first, face_first, ws.vert_first, ws.face_first, st);
+  send_offsets(b, vert_first, face_first, ws.vert_first, ws.face_first, st);
   if (max_f > 0)
     hipLaunchKernelGGL(mm_record_kernel, dim3((unsigned)cdivll(max_f, MM_THREADS), (unsigned)b), dim3(MM_THREADS), 0, st, verts, faces,
                        ws.vert_first, ws.face_first, ws.rec);

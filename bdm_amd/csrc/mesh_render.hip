@@ -7,9 +7,7 @@
 // half-plane rule for centres ON an edge; depth and barycentrics are float32 quotients of those integers; the pixel keeps the
 // smallest (bits of z) << 32 | face index.  Nothing depends on execution order: the only atomic is an integer minimum.
 //
-// Four kernels.
-//   mesh_offsets_kernel   the two host offset arrays travel as launch arguments, 32 entries per launch, into the workspace
-//                         (no host-to-device copy, no synchronisation, safe under stream capture).
+// Three kernels, after send_offsets (ragged.h) has put the two host offset arrays into the workspace.
 //   mesh_vertex_kernel    one thread per vertex: view transform, NDC, screen, snap -> (SX, SY, zv, usable), 16 bytes per vertex.
 //   mesh_raster_kernel    one thread per face: set-up (face_setup), the bounding box of the pixel centres it can cover clamped to
 //                         the image, then every centre of the box through face_pixel and, for a covered one, atomicMin on the
@@ -25,6 +23,7 @@
 #include "../../include/bdm_hip.h"
 #include "camera.h"
 #include "common.h"
+#include "ragged.h"
 
 #include <limits.h>
 
@@ -38,21 +37,7 @@ using namespace bdm;
 #define MESH_MAX_SIDE 4096
 #define MESH_SNAP 256                     // sub-pixel positions per pixel
 #define MESH_GUARD 4194304.f              // 2^22: |SX|, |SY| beyond it make the vertex unusable (edge products stay below 2^48)
-#define MESH_OFFSETS_PER_LAUNCH 32
 #define MESH_EMPTY_KEY 0xFFFFFFFFFFFFFFFFull
-
-struct MeshOffsetChunk {
-  long long v[MESH_OFFSETS_PER_LAUNCH], f[MESH_OFFSETS_PER_LAUNCH];
-};
-
-__global__ void mesh_offsets_kernel(MeshOffsetChunk chunk, int first, int count, long long *__restrict__ vert_first,
-                                    long long *__restrict__ face_first) {
-  const int i = threadIdx.x;
-  if (i < count) {  // count <= MESH_OFFSETS_PER_LAUNCH, first + count <= b + 1
-    vert_first[first + i] = chunk.v[i];
-    face_first[first + i] = chunk.f[i];
-  }
-}
 
 // the mesh that owns packed row `row`: the m in [0, b) with first[m] <= row < first[m + 1] (empty meshes own nothing).
 // first[0] == 0 <= row < first[b]; at most 32 halvings for b < 2^31.
@@ -272,7 +257,7 @@ static MeshWs mesh_ws(void *ws, int b, long long sum_v, int h, int w) {
   MeshWs m;
   char *p = (char *)ws;
   const size_t key_bytes = sizeof(unsigned long long) * (size_t)b * h * w, rec_bytes = sizeof(int4) * (size_t)sum_v;
-  const size_t key_padded = (key_bytes + 15) & ~(size_t)15;  // the records are loaded 16 bytes at a time
+  const size_t key_padded = align16(key_bytes);  // the records are loaded 16 bytes at a time
   m.keys = (unsigned long long *)p;
   m.vrec = (int4 *)(p + key_padded);
   m.vert_first = (long long *)(p + key_padded + rec_bytes);
@@ -284,12 +269,6 @@ static MeshWs mesh_ws(void *ws, int b, long long sum_v, int h, int w) {
 extern "C" size_t bdm_render_meshes_workspace_bytes(int b, long long sum_v, long long sum_f, int h, int w) {
   if (!mesh_sizes_ok(b, sum_v, sum_f, h, w)) return 0;
   return mesh_ws(nullptr, b, sum_v, h, w).bytes;
-}
-
-static bool mesh_overlap(const void *a, size_t na, const void *b, size_t nb) {
-  if (!a || !b || na == 0 || nb == 0) return false;
-  const char *pa = (const char *)a, *pb = (const char *)b;
-  return pa < pb + nb && pb < pa + na;
 }
 
 extern "C" int bdm_render_meshes(int b, int h, int w, int c, int ortho, int cull, const float *verts, const int *faces,
@@ -306,34 +285,19 @@ extern "C" int bdm_render_meshes(int b, int h, int w, int c, int ortho, int cull
   if (b == 0) return BDM_OK;
   BDM_REQUIRE(verts && faces && vert_first && face_first && cameras && workspace, "render_meshes: an input or the workspace is NULL");
   BDM_REQUIRE(image == nullptr || background != nullptr, "render_meshes: an image needs a background colour");
-  BDM_REQUIRE(vert_first[0] == 0 && face_first[0] == 0, "render_meshes: the offsets must start at 0");
-  for (int m = 0; m < b; ++m)
-    BDM_REQUIRE(vert_first[m + 1] >= vert_first[m] && face_first[m + 1] >= face_first[m], "render_meshes: offsets decrease at mesh %d", m);
+  long long max_v = 0, max_f = 0;
+  if (check_first("render_meshes", "mesh", b, vert_first, &max_v) != BDM_OK || check_first("render_meshes", "mesh", b, face_first, &max_f) != BDM_OK)
+    return BDM_ERR_ARG;
   const long long sum_v = vert_first[b], sum_f = face_first[b];
   BDM_REQUIRE(sum_v <= INT_MAX && sum_f <= INT_MAX, "render_meshes: %lld vertices or %lld faces reach 2^31", sum_v, sum_f);
   const MeshWs ws = mesh_ws(workspace, b, sum_v, h, w);
   const size_t pixels = (size_t)b * h * w;
-  const void *in[6] = {verts, faces, cameras, vert_features, face_features, background};
-  const size_t in_bytes[6] = {12 * (size_t)sum_v, 12 * (size_t)sum_f, 64 * (size_t)b, 4 * (size_t)sum_v * c, 4 * (size_t)sum_f * c,
-                              4 * (size_t)c};
-  const void *out[5] = {pix_to_face, zbuf, bary, image, workspace};
-  const size_t out_bytes[5] = {4 * pixels, 4 * pixels, 12 * pixels, 4 * pixels * c, ws.bytes};
-  for (int o = 0; o < 5; ++o) {
-    for (int i = 0; i < 6; ++i)
-      BDM_REQUIRE(!mesh_overlap(out[o], out_bytes[o], in[i], in_bytes[i]), "render_meshes: output %d overlaps input %d", o, i);
-    for (int p = o + 1; p < 5; ++p)
-      BDM_REQUIRE(!mesh_overlap(out[o], out_bytes[o], out[p], out_bytes[p]), "render_meshes: outputs %d and %d overlap", o, p);
-  }
+  const Range in[6] = {{verts, 12 * (size_t)sum_v}, {faces, 12 * (size_t)sum_f}, {cameras, 64 * (size_t)b},
+                       {vert_features, 4 * (size_t)sum_v * c}, {face_features, 4 * (size_t)sum_f * c}, {background, 4 * (size_t)c}};
+  const Range out[5] = {{pix_to_face, 4 * pixels}, {zbuf, 4 * pixels}, {bary, 12 * pixels}, {image, 4 * pixels * c}, {workspace, ws.bytes}};
+  if (check_overlap("render_meshes", in, 6, out, 5) != BDM_OK) return BDM_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  for (int first = 0; first <= b; first += MESH_OFFSETS_PER_LAUNCH) {
-    MeshOffsetChunk chunk;
-    const int count = (b + 1 - first) < MESH_OFFSETS_PER_LAUNCH ? (b + 1 - first) : MESH_OFFSETS_PER_LAUNCH;
-    for (int i = 0; i < MESH_OFFSETS_PER_LAUNCH; ++i) {
-      chunk.v[i] = i < count ? vert_first[first + i] : 0;
-      chunk.f[i] = i < count ? face_first[first + i] : 0;
-    }
-    hipLaunchKernelGGL(mesh_offsets_kernel, dim3(1), dim3(64), 0, s, chunk, first, count, ws.vert_first, ws.face_first);
-  }
+  send_offsets(b, vert_first, face_first, ws.vert_first, ws.face_first, s);
   if (hipMemsetAsync(ws.keys, 0xFF, sizeof(unsigned long long) * pixels, s) != hipSuccess) return launch_status("render_meshes (memset)");
   if (sum_v > 0 && sum_f > 0) {
     hipLaunchKernelGGL(mesh_vertex_kernel, dim3((unsigned)cdivll(sum_v, MESH_THREADS)), dim3(MESH_THREADS), 0, s, b, (int)sum_v, ortho,

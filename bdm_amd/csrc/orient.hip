@@ -25,10 +25,6 @@ __device__ __forceinline__ float dot3(float x, float y, float z, float a, float 
   return __fadd_rn(__fadd_rn(__fmul_rn(x, a), __fmul_rn(y, b)), __fmul_rn(z, c));
 }
 
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-  return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;
-}
-
 // clamp(floor(f), 0, hi) as an integer; NaN -> 0
 __device__ __forceinline__ int floor_clamp(float f, int hi) {
   const float g = floorf(f);

@@ -50,8 +50,6 @@ static inline SurfWs surf_ws(void *ws, int b, int r) {
   return w;
 }
 
-__device__ __forceinline__ bool surf_finite(float x) { return fabsf(x) < INFINITY; }
-
 // rank of a set flag among the set flags of the workgroup (ascending thread index) and their number; all threads call it
 __device__ __forceinline__ int surf_block_rank(bool flag, int &total, int *waves) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -80,8 +78,8 @@ __global__ __launch_bounds__(SRF_WIDE) void surf_box_kernel(int n, int r, int s,
   int valid = 0;
   for (int i = tid; i < n; i += SRF_WIDE) {
     const float x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
-    if (surf_finite(x) && surf_finite(y) && surf_finite(z) && surf_finite(nrm[3 * (size_t)i]) && surf_finite(nrm[3 * (size_t)i + 1]) &&
-        surf_finite(nrm[3 * (size_t)i + 2])) {
+    if (finite1(x) && finite1(y) && finite1(z) && finite1(nrm[3 * (size_t)i]) && finite1(nrm[3 * (size_t)i + 1]) &&
+        finite1(nrm[3 * (size_t)i + 2])) {
       lo[0] = fminf(lo[0], x), lo[1] = fminf(lo[1], y), lo[2] = fminf(lo[2], z);
       hi[0] = fmaxf(hi[0], x), hi[1] = fmaxf(hi[1], y), hi[2] = fmaxf(hi[2], z);
       ++valid;
@@ -132,7 +130,7 @@ __global__ __launch_bounds__(SRF_THREADS) void surf_scatter_kernel(int b, int n,
     const size_t row = ((size_t)cloud * n + i) * 3;
     const float px = points[row], py = points[row + 1], pz = points[row + 2];
     const float nx = normals[row], ny = normals[row + 1], nz = normals[row + 2];
-    if (!(surf_finite(px) && surf_finite(py) && surf_finite(pz) && surf_finite(nx) && surf_finite(ny) && surf_finite(nz))) continue;
+    if (!(finite1(px) && finite1(py) && finite1(pz) && finite1(nx) && finite1(ny) && finite1(nz))) continue;
     const float inv = cp[3];
     const float qx = __fadd_rn(__fmul_rn(__fsub_rn(px, cp[0]), inv), mid), qy = __fadd_rn(__fmul_rn(__fsub_rn(py, cp[1]), inv), mid),
                 qz = __fadd_rn(__fmul_rn(__fsub_rn(pz, cp[2]), inv), mid);

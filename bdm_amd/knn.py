@@ -12,6 +12,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .ragged import first, pack_rows
 
 K_MAX, C_MAX, MAX_B = 64, 16, 65535   # limits of bdm_hip.h section 15
 MODES = {"nearest": 0, "idw": 1}
@@ -40,17 +41,6 @@ def _check_sizes(np_, nr, K):
         raise ValueError(f"{len(np_)} entries exceed {MAX_B}: split the batch")
     if sum(np_) >= 2 ** 31 or sum(nr) >= 2 ** 31 or sum(np_) * K >= 2 ** 31:
         raise ValueError("the batch reaches 2^31 rows or neighbour entries: split it")
-
-
-def _pack(rows_list, width, device):
-    """Packed float32 rows on the device; an empty side still gets one (unread) row: no NULL among the inputs."""
-    if sum(int(t.shape[0]) for t in rows_list) == 0:
-        return torch.zeros(1, width, dtype=torch.float32, device=device)
-    return L.f32(torch.cat([t.float() for t in rows_list]))
-
-
-def _first(counts):
-    return torch.tensor([0] + list(counts), dtype=torch.int64).cumsum(0)   # a host array: the call reads it before it returns
 
 
 def _search(queries, refs, q_first, r_first, K):
@@ -96,7 +86,7 @@ def knn_packed(q_list, r_list, K):
     for t in list(q_list) + list(r_list):
         L.ptr(t)   # refuses host tensors before anything is allocated
     dev = q_list[0].device
-    idx, d2 = _search(_pack(q_list, 3, dev), _pack(r_list, 3, dev), _first(np_), _first(nr), K)
+    idx, d2 = _search(pack_rows(q_list, 3, dev), pack_rows(r_list, 3, dev), first(np_), first(nr), K)
     return list(zip(idx.long().split(np_), d2.split(np_)))
 
 
@@ -155,8 +145,8 @@ def knn_points(p1, p2, lengths1=None, lengths2=None, K=1, version=-1, return_nn=
     dists = torch.zeros(N, P1, K, dtype=torch.float32, device=dev)
     idx = torch.zeros(N, P1, K, dtype=torch.int64, device=dev)
     if N and sum(n1):
-        pi, pd = _search(_pack([p1[i, :n1[i]] for i in range(N)], 3, dev), _pack([p2[i, :n2[i]] for i in range(N)], 3, dev),
-                         _first(n1), _first(n2), K)
+        pi, pd = _search(pack_rows([p1[i, :n1[i]] for i in range(N)], 3, dev), pack_rows([p2[i, :n2[i]] for i in range(N)], 3, dev),
+                         first(n1), first(n2), K)
         absent = pi < 0
         pi, pd = pi.long().masked_fill(absent, 0), pd.masked_fill(absent, 0.0)
         if n1 == [P1] * N:
@@ -196,8 +186,8 @@ def transfer_point_attributes(query_list, ref_list, attr_list, K=3, mode="idw", 
     for t in list(query_list) + list(ref_list) + list(attr_list):
         L.ptr(t)   # refuses host tensors before anything is allocated
     dev = query_list[0].device
-    q_first, r_first = _first(np_), _first(nr)
-    idx, d2 = _search(_pack(query_list, 3, dev), _pack(ref_list, 3, dev), q_first, r_first, K)
-    out = _interpolate(_pack(attr_list, C, dev), idx, d2, q_first, r_first, MODES[mode], eps if mode == "idw" else 1.0, fill)
+    q_first, r_first = first(np_), first(nr)
+    idx, d2 = _search(pack_rows(query_list, 3, dev), pack_rows(ref_list, 3, dev), q_first, r_first, K)
+    out = _interpolate(pack_rows(attr_list, C, dev), idx, d2, q_first, r_first, MODES[mode], eps if mode == "idw" else 1.0, fill)
     outs = list(out.split(np_))
     return (outs, list(zip(idx.long().split(np_), d2.split(np_)))) if return_knn else outs

@@ -23,30 +23,19 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .mesh_metrics import _mesh_lists
+from .ragged import mesh_lists, pack_meshes
 
 MAX_B, MAX_ITER = 65535, 10000   # limits of bdm_hip.h section 16
 WEIGHTS = {"inverse_length": 0, "uniform": 1}
 ROUNDS_PER_CALL = 8   # label rounds between two reads of the `changed` flag
 
 
-def _packed(verts_list, faces_list):
-    """The ABI's form of a batch -> (verts, faces, vert_first, face_first); an empty side still gets one (unread) row."""
-    nv, nf = [int(v.shape[0]) for v in verts_list], [int(f.shape[0]) for f in faces_list]
-    if len(nv) > MAX_B:
-        raise ValueError(f"{len(nv)} meshes exceed {MAX_B}: split the batch")
-    if sum(nv) >= 2 ** 31 - 1 or 6 * sum(nf) >= 2 ** 31:
+def _check_sizes(verts_list, faces_list):
+    """The limits of bdm_hip.h section 16 on a batch, before anything is packed."""
+    if len(verts_list) > MAX_B:
+        raise ValueError(f"{len(verts_list)} meshes exceed {MAX_B}: split the batch")
+    if sum(int(v.shape[0]) for v in verts_list) >= 2 ** 31 - 1 or 6 * sum(int(f.shape[0]) for f in faces_list) >= 2 ** 31:
         raise ValueError("the batch reaches 2^31 vertices or neighbour entries (six per face): split it")
-    for t in list(verts_list) + list(faces_list):
-        L.ptr(t)   # refuses host tensors before anything is allocated
-    dev = verts_list[0].device
-    verts = L.f32(torch.cat([v.float() for v in verts_list])) if sum(nv) else torch.zeros(1, 3, device=dev)
-    # indices beyond int32 cannot be vertex indices: they become -1, no connected face under the rule, instead of wrapping around
-    faces = torch.cat([(torch.where((f >= 0) & (f < 2 ** 31), f, -1) if f.dtype == torch.int64 else f).int() for f in faces_list]).contiguous() \
-        if sum(nf) else torch.zeros(1, 3, dtype=torch.int32, device=dev)
-    vert_first = torch.tensor([0] + nv, dtype=torch.int64).cumsum(0)   # host arrays: the calls read them before they return
-    face_first = torch.tensor([0] + nf, dtype=torch.int64).cumsum(0)
-    return verts, faces, vert_first, face_first
 
 
 def _adjacency(faces, vert_first, face_first):
@@ -101,10 +90,11 @@ def vertex_adjacency(meshes):
     packed vertex g are nbr[nbr_first[g] : nbr_first[g + 1]], ascending indices WITHIN its mesh, each once.  nbr has the upper bound of
     six entries per face (no read-back sizes it); the entries from nbr_first[-1] on are -1.  Only faces whose three indices are in range
     and pairwise different take part."""
-    verts_list, faces_list = _mesh_lists(meshes)
+    verts_list, faces_list = mesh_lists(meshes)
     if not verts_list:
         return torch.zeros(1, dtype=torch.int32), torch.zeros(0, dtype=torch.int32)
-    _, faces, vert_first, face_first = _packed(verts_list, faces_list)
+    _check_sizes(verts_list, faces_list)
+    _, faces, vert_first, face_first = pack_meshes(verts_list, faces_list)
     return _adjacency(faces, vert_first, face_first)
 
 
@@ -113,10 +103,11 @@ def connected_components(meshes):
     """Per mesh (vert_comp (V,) int64, face_comp (F,) int64, comp_verts (C,) int64, comp_faces (C,) int64): the component of every vertex
     and face (-1 for a face that takes no part: an index out of range or repeated), components ranked by their smallest vertex index,
     and the vertex and face counts of the C components.  A vertex no face uses is a component of its own."""
-    verts_list, faces_list = _mesh_lists(meshes)
+    verts_list, faces_list = mesh_lists(meshes)
     if not verts_list:
         return []
-    _, faces, vert_first, face_first = _packed(verts_list, faces_list)
+    _check_sizes(verts_list, faces_list)
+    _, faces, vert_first, face_first = pack_meshes(verts_list, faces_list)
     nbr_first, nbr = _adjacency(faces, vert_first, face_first)
     vert_comp, face_comp, comp_count, comp_verts, comp_faces, _ = _components(faces, vert_first, face_first, nbr_first, nbr)
     counts = comp_count.cpu().tolist()   # the one read-back
@@ -164,7 +155,7 @@ def remove_small_components(meshes, min_fraction=0.1, min_faces=1, keep_largest=
     index out of range or repeated are always dropped; colors_list ((V_i, C) per mesh) is carried along.  A mesh that loses everything
     becomes a legal empty mesh.  info: per mesh {"components", "removed_components", "removed_vertices", "removed_faces"}."""
     _check_selection(min_fraction, min_faces)
-    verts_list, faces_list = _mesh_lists(meshes)
+    verts_list, faces_list = mesh_lists(meshes)
     if colors_list is not None:
         if not isinstance(colors_list, (list, tuple)) or len(colors_list) != len(verts_list):
             raise ValueError("colors_list must be a list with one (V_i, C) tensor per mesh")
@@ -199,10 +190,11 @@ def taubin_smoothing(meshes, lambd=0.53, mu=-0.34, num_iter=10, *, weights="inve
     same faces.  A vertex without neighbours keeps its position.  Bad arguments raise ValueError before any launch."""
     from .cameras import Meshes
     _check_taubin(lambd, mu, num_iter, weights)
-    verts_list, faces_list = _mesh_lists(meshes)
+    verts_list, faces_list = mesh_lists(meshes)
     if not verts_list:
         return Meshes([], [])
-    verts, faces, vert_first, face_first = _packed(verts_list, faces_list)
+    _check_sizes(verts_list, faces_list)
+    verts, faces, vert_first, face_first = pack_meshes(verts_list, faces_list)
     B, sum_v, dev = len(verts_list), int(vert_first[-1]), verts.device
     if sum_v == 0:
         return Meshes([v.float() for v in verts_list], list(faces_list))

@@ -18,24 +18,14 @@ import torch
 
 from . import _lib as L
 from . import ops, rng
+from .ragged import mesh_lists, pack_meshes
 
 MAX_FACES, MAX_B = 1 << 24, 65535   # limits of bdm_hip.h section 14
 FORMS = {None: 0, "exhaustive": 1}   # the culled form is not built (no margin keeps its bits: DESIGN.md section 18)
 
 
-def _mesh_lists(meshes):
-    """A Meshes or a (verts_list, faces_list) pair -> (verts_list, faces_list), checked as cameras.Meshes checks them."""
-    from .cameras import Meshes
-    if hasattr(meshes, "verts_list") and hasattr(meshes, "faces_list"):
-        return meshes.verts_list(), meshes.faces_list()
-    if isinstance(meshes, (tuple, list)) and len(meshes) == 2 and isinstance(meshes[0], (list, tuple)):
-        m = Meshes(list(meshes[0]), list(meshes[1]))   # raises ValueError for float or bool faces and bad shapes
-        return m.verts_list(), m.faces_list()
-    raise ValueError(f"expected a Meshes or a (verts_list, faces_list) pair, got {type(meshes).__name__}")
-
-
-def _packed(verts_list, faces_list):
-    """The ABI's form of a batch -> (verts, faces, vert_first, face_first, max_faces); an empty side still gets one (unread) row."""
+def _check_sizes(verts_list, faces_list):
+    """The limits of bdm_hip.h section 14 on a batch, before anything is packed."""
     nv, nf = [int(v.shape[0]) for v in verts_list], [int(f.shape[0]) for f in faces_list]
     if len(nv) > MAX_B:
         raise ValueError(f"{len(nv)} meshes exceed {MAX_B}: split the batch")
@@ -43,15 +33,6 @@ def _packed(verts_list, faces_list):
         raise ValueError(f"a mesh of {max(nf)} faces exceeds {MAX_FACES}")
     if sum(nv) >= 2 ** 31 or sum(nf) >= 2 ** 31:
         raise ValueError("the batch reaches 2^31 vertices or faces: split it")
-    dev = verts_list[0].device
-    L.ptr(verts_list[0])   # refuses host tensors before anything is allocated
-    verts = L.f32(torch.cat([v.float() for v in verts_list])) if sum(nv) else torch.zeros(1, 3, device=dev)
-    # indices beyond int32 cannot be vertex indices: they become -1, an invalid face under the rule, instead of wrapping around
-    faces = torch.cat([(torch.where((f >= 0) & (f < 2 ** 31), f, -1) if f.dtype == torch.int64 else f).int() for f in faces_list]).contiguous() \
-        if sum(nf) else torch.zeros(1, 3, dtype=torch.int32, device=dev)
-    vert_first = torch.tensor([0] + nv, dtype=torch.int64).cumsum(0)   # host arrays: the call reads them before it returns
-    face_first = torch.tensor([0] + nf, dtype=torch.int64).cumsum(0)
-    return verts, faces.to(dev), vert_first, face_first, (max(nf) if nf else 0)
 
 
 @torch.no_grad()
@@ -61,7 +42,7 @@ def sample_points_from_meshes(meshes, num_samples=10000, return_normals=False, *
     Mesh m draws from the Philox stream keyed rng.shape_key(seed, first_index + m), purpose rng.MESH: its samples do not depend on
     its batch slot.  A mesh without a valid face yields zeros (and face index -1), as pytorch3d does for empty meshes.
     Bad arguments raise ValueError before any launch."""
-    verts_list, faces_list = _mesh_lists(meshes)
+    verts_list, faces_list = mesh_lists(meshes)
     S = int(num_samples)
     if S < 1:
         raise ValueError(f"num_samples={num_samples} is not positive")
@@ -72,8 +53,9 @@ def sample_points_from_meshes(meshes, num_samples=10000, return_normals=False, *
         out = (torch.zeros(0, S, 3),) + ((torch.zeros(0, S, 3),) if return_normals else ()) + \
             ((torch.zeros(0, S, dtype=torch.int64),) if return_face_idx else ())
         return out if len(out) > 1 else out[0]
-    verts, faces, vert_first, face_first, max_f = _packed(verts_list, faces_list)
-    dev = verts.device
+    _check_sizes(verts_list, faces_list)
+    verts, faces, vert_first, face_first = pack_meshes(verts_list, faces_list)
+    dev, max_f = verts.device, int((face_first[1:] - face_first[:-1]).max())
     keys = [rng.shape_key(seed, int(first_index) + m) for m in range(B)]
     keys = torch.tensor([k - (1 << 64) if k >= (1 << 63) else k for k in keys], dtype=torch.int64).to(dev)
     points = torch.empty(B, S, 3, dtype=torch.float32, device=dev)
@@ -108,7 +90,7 @@ def point_mesh_sqdist(meshes, points, *, form=None, order=None):
     A point with a non-finite coordinate, and every point of a mesh without a valid face, gets (+inf, -1).
     form: None (the chooser) or "exhaustive".  order: None (natural), "morton", or a (B, P) integer permutation -- which thread takes
     which point; the result does not depend on it.  Bad arguments raise ValueError before any launch."""
-    verts_list, faces_list = _mesh_lists(meshes)
+    verts_list, faces_list = mesh_lists(meshes)
     if hasattr(points, "points_padded"):
         points = points.points_padded()
     if form not in FORMS:
@@ -126,7 +108,8 @@ def point_mesh_sqdist(meshes, points, *, form=None, order=None):
         raise ValueError(f"order={order!r} is none of None, 'morton', a (B, P) integer tensor")
     if B == 0 or P == 0:
         return torch.zeros(B, P, device=points.device), torch.zeros(B, P, dtype=torch.int64, device=points.device)
-    verts, faces, vert_first, face_first, _ = _packed(verts_list, faces_list)
+    _check_sizes(verts_list, faces_list)
+    verts, faces, vert_first, face_first = pack_meshes(verts_list, faces_list)
     dev = verts.device
     points = L.f32(points.float().to(dev))
     if isinstance(order, str):

@@ -19,6 +19,7 @@ import torch
 from . import _lib as L
 from . import ops
 from .cameras import OrthographicCameras, Pointclouds, join_cameras, look_at_view_transform
+from .ragged import pack_meshes
 
 Fragments = namedtuple("Fragments", ["idx", "zbuf", "dists"])
 COMPOSITORS = {"norm_weighted": 0, "alpha": 1}
@@ -137,8 +138,7 @@ def _render_meshes(cameras, meshes, image_size, cull_backfaces=False, vert_featu
         raise ValueError("vertex features and face features are exclusive")
     B = len(meshes)
     verts_list, faces_list = meshes.verts_list(), meshes.faces_list()
-    nv, nf = [int(v.shape[0]) for v in verts_list], [int(f.shape[0]) for f in faces_list]
-    sum_v, sum_f = sum(nv), sum(nf)
+    sum_v, sum_f = sum(int(v.shape[0]) for v in verts_list), sum(int(f.shape[0]) for f in faces_list)
     bg, C = None, 3
     if background is not None:
         bg = torch.as_tensor(background, dtype=torch.float32).reshape(-1)
@@ -153,12 +153,8 @@ def _render_meshes(cameras, meshes, image_size, cull_backfaces=False, vert_featu
         frag = MeshFragments(torch.zeros(0, H, W, 1, dtype=torch.int64, device=dev), torch.zeros(0, H, W, 1, device=dev),
                              torch.zeros(0, H, W, 1, 3, device=dev)) if fragments else None
         return frag, (None if bg is None else torch.zeros(0, H, W, C, device=dev))
-    dev = verts_list[0].device
-    # the ABI takes no NULL input: an empty batch side still gets one (unread) row
-    verts = L.f32(torch.cat(verts_list)) if sum_v else torch.zeros(1, 3, device=dev)
-    faces = L.i32(torch.cat(faces_list)) if sum_f else torch.zeros(1, 3, dtype=torch.int32, device=dev)
-    vert_first = torch.tensor([0] + nv, dtype=torch.int64).cumsum(0)   # host arrays: the call reads them before it returns
-    face_first = torch.tensor([0] + nf, dtype=torch.int64).cumsum(0)
+    verts, faces, vert_first, face_first = pack_meshes(verts_list, faces_list)
+    dev = verts.device
     cams = cameras.packed().to(dev)
     pix = zbuf = bary = image = None
     if fragments:

@@ -94,6 +94,19 @@ def test_entries_alone_have_their_bits_of_the_batch_and_calls_repeat(hip):
         _assert_equal(f"entry {j} alone", _call_knn(c["q"][j:j + 1], c["r"][j:j + 1], c["k"]), whole[j:j + 1])
 
 
+@pytest.mark.parametrize("b", [31, 32, 33, 65])
+def test_offsets_cross_the_launch_boundary_of_the_upload(hip, b):
+    """The b + 1 offsets of each array travel 32 per launch (csrc/ragged.hip): b + 1 = 32, 33, 34 and 66 are one launch exactly full,
+    one entry and two entries into a second launch, and two entries into a third.  A wrong or missing entry of a later launch
+    mis-addresses every entry behind it.  Entry i: 1 + i % 3 queries and 1 + (i * 7) % 4 reference rows (none for every fifth entry)
+    on the lattice of the "ties" case, whose squared distances are exact in float32."""
+    lattice = K.case("ties")["q"][0][:64]
+    rows = lambda start, n: lattice[(start + torch.arange(n)) % 64]   # noqa: E731
+    q = [rows(3 * i, 1 + i % 3) for i in range(b)]
+    r = [rows(11 * i + 1, 0 if i % 5 == 4 else 1 + (i * 7) % 4) for i in range(b)]
+    _assert_equal(f"b = {b}", _call_knn(q, r, 2), K.knn_batch(q, r, 2))
+
+
 def test_optional_outputs_may_be_null(hip):
     c, want = K.case("edges_k3"), K.case_ref("edges_k3")
     for kept in (("idx",), ("d2",), ()):

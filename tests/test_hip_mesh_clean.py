@@ -242,6 +242,24 @@ def test_smoothing_special_inputs(hip):
         assert R.same_floats(_taubin(p, first, nbr, 3, 0, lambd, mu)[0], R.taubin(v, rf, rn, lambd, mu, 3, 0)), (lambd, mu)
 
 
+def test_33_meshes_cross_the_launch_boundary_of_the_offsets_upload(hip):
+    """b + 1 = 34 offsets are one launch more than the 32 a launch carries (csrc/ragged.hip): a wrong or missing entry of the second
+    launch mis-addresses mesh 32.  Meshes of one triangle and of two triangles on a common side in turn, mesh 16 empty.
+    bdm_mesh_adjacency sends both offset arrays, bdm_mesh_taubin the vertex offsets and no face offsets."""
+    g = torch.Generator().manual_seed(330)
+    one, two = torch.tensor([[0, 1, 2]]), torch.tensor([[0, 1, 2], [2, 1, 3]])
+    meshes = [(torch.rand(3 + i % 2, 3, generator=g), two if i % 2 else one) for i in range(33)]
+    meshes[16] = (torch.zeros(0, 3), torch.zeros(0, 3, dtype=torch.int64))
+    p = Packed(meshes)
+    assert p.b == 33
+    first, nbr = _adjacency(p)
+    refs = [dict(zip(("first", "nbr"), R.adjacency(f, v.shape[0]))) for v, f in meshes]
+    _assert_adjacency(p, first, nbr, refs, "33 meshes")
+    for mode in (0, 1):
+        want = [R.taubin(v, c["first"], c["nbr"], num_iter=1, mode=mode) for (v, _), c in zip(meshes, refs)]
+        _assert_floats(_taubin(p, first, nbr, 1, mode), want, f"33 meshes, mode {mode}")
+
+
 # ---- errors ---------------------------------------------------------------------------------------------------------------------------
 def test_every_documented_limit_returns_1_and_leaves_the_outputs_untouched(hip):
     from bdm_amd import _lib as L

@@ -201,6 +201,26 @@ def test_python_fragments_and_images(hip):
     assert torch.equal(empty, torch.tensor(BACKGROUND).expand(1, 8, 8, 3))                # no face anywhere: the default background
 
 
+def test_face_indices_beyond_int32_are_invalid_not_wrapped(hip):
+    """Face 1 is given as int64 2^32 + (0, 1, 3): cast to int32 it would wrap onto (0, 1, 3), which lies below the side it shares with
+    face 0, nearer to the camera, over pixel centres face 0 does not cover.  It is no face of the mesh: no pixel shows it, and the
+    covered set is that of face 0 alone."""
+    from bdm_amd.cameras import Meshes
+    from bdm_amd.render import rasterize_meshes
+    verts = M.on_centres([[2, 8], [13, 8], [7, 2], [7, 14]], 16, 16)
+    verts[3, 2] = -0.5
+    faces = torch.tensor([[0, 1, 2], [2 ** 32, 2 ** 32 + 1, 2 ** 32 + 3]])
+    assert faces.dtype == torch.int64 and faces[1].int().tolist() == [0, 1, 3]
+    cam = M.ortho_pixel_camera()
+    wrapped = M.render(verts, torch.tensor([[0, 1, 3]]), cam.packed()[0], 16, 16, ortho=True)["pix_to_face"] >= 0
+
+    def pix_to_face(f):
+        return rasterize_meshes(cam.to("cuda"), Meshes([verts.cuda()], [f.cuda()]), image_size=16).pix_to_face[0, :, :, 0].cpu()
+    got, alone = pix_to_face(faces), pix_to_face(faces[:1])
+    assert int((alone >= 0).sum()) > 10 and int((wrapped & (alone < 0)).sum()) > 10   # both triangles are visible, on different pixels
+    assert not bool((got == 1).any()) and torch.equal(got >= 0, alone >= 0)
+
+
 def test_reconstructed_sphere_flat_and_smooth(hip):
     """reconstruct_surface on the 4096-point sphere, drawn: "flat" equals the restatement fed the same face colours; "smooth" is
     checked by what does not depend on the order of the vertex-normal sum: the covered mask, and the range of the colours,

@@ -9,6 +9,7 @@ import torch
 
 import mesh_clean_ref as R
 from bdm_amd import mesh_clean as MC
+from bdm_amd.ragged import mesh_lists
 
 
 def _case(name):
@@ -115,7 +116,7 @@ def test_smoothing_edge_cases_of_the_restatement():
 
 # ---- the island claim -----------------------------------------------------------------------------------------------------------------
 def _ref_connected_components(meshes):
-    verts_list, faces_list = MC._mesh_lists(meshes)
+    verts_list, faces_list = mesh_lists(meshes)
     out = []
     for v, f in zip(verts_list, faces_list):
         c = R.components(f, v.shape[0])
@@ -130,7 +131,7 @@ def ref_kernels(monkeypatch):
 
     def ref_taubin(meshes, lambd=0.53, mu=-0.34, num_iter=10, *, weights="inverse_length"):
         MC._check_taubin(lambd, mu, num_iter, weights)
-        verts_list, faces_list = MC._mesh_lists(meshes)
+        verts_list, faces_list = mesh_lists(meshes)
         out = []
         for v, f in zip(verts_list, faces_list):
             first, nbr = R.adjacency(f, v.shape[0])

@@ -18,6 +18,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bdm_amd import _lib as L  # noqa: E402
 from bdm_amd import mesh_clean as MC  # noqa: E402
+from bdm_amd.ragged import pack_meshes  # noqa: E402
 
 
 def timed_ms(fn, repeats, warmup=3):
@@ -85,7 +86,7 @@ def run(B, iters, repeats):
     normals = estimate_pointcloud_normals(pts, 50, "visibility")
     verts_list, faces_list = reconstruct_surface(pts, normals, resolution=64)
     mesher = timed_ms(lambda: reconstruct_surface(pts, normals, resolution=64), repeats)
-    verts, faces, vert_first, face_first = MC._packed(verts_list, faces_list)
+    verts, faces, vert_first, face_first = pack_meshes(verts_list, faces_list)
     sum_v, sum_f, lib = int(vert_first[-1]), int(face_first[-1]), L.lib()
     vf, ff = vert_first.data_ptr(), face_first.data_ptr()
 

@@ -27,6 +27,7 @@ from bdm_amd import evaluation as E  # noqa: E402
 from bdm_amd import mesh_metrics as MM  # noqa: E402
 from bdm_amd import rng  # noqa: E402
 from bdm_amd import surface as S  # noqa: E402
+from bdm_amd.ragged import pack_meshes  # noqa: E402
 
 TILE, WAVE = 256, 64
 
@@ -77,8 +78,8 @@ def rows(args):
     for b, n, R, s in ((16, 4096, 64, 3), (16, 16384, 128, 3)):
         pts, nrm = shapes(b, n, gen)
         verts_list, faces_list = S.reconstruct_surface(pts, nrm, resolution=R, support=s)
-        verts, faces, vert_first, face_first, max_f = MM._packed(verts_list, faces_list)
-        sum_f = int(face_first[-1])
+        verts, faces, vert_first, face_first = pack_meshes(verts_list, faces_list)
+        sum_f, max_f = int(face_first[-1]), int((face_first[1:] - face_first[:-1]).max())
         morton = MM.morton_order(pts).contiguous()
         natural = torch.arange(n, dtype=torch.int32, device="cuda").repeat(b, 1).contiguous()
         keys = torch.tensor([k - (1 << 64) if k >= (1 << 63) else k for k in (rng.shape_key(0, m) for m in range(b))]).cuda()
