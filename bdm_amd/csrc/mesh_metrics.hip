@@ -16,11 +16,14 @@
 //   mm_count_write_kernel<true>   one workgroup per MM_THREADS faces: q again, scanned inside the workgroup, plus its offset -> C.
 //   mm_sample_kernel    one thread per sample: Philox words, binary search in C, barycentric point and the face's unit normal.
 //   mm_record_kernel    one thread per face: the 64-byte record (v0, v1, v2, n, nn, l2_0 .. l2_2), nn = 0 for an invalid face.
+//                       The record, the face load and the pair rule itself (mm_pair_sqdist) live in point_face.h, which
+//                       face_point.hip shares: one definition for both directions of the distance.
 //   mm_dist_kernel      one thread per point, one workgroup per MM_THREADS points: the records of MM_TILE faces at a time go through
 //                       LDS, component-major (four float4 planes), and every lane reads the SAME record (a broadcast read: no bank
 //                       conflict, one ds_read_b128 per 16 bytes for the whole wave); the running (sqdist, face) stays in registers.
 #include "../../include/bdm_hip.h"
 #include "common.h"
+#include "point_face.h"
 #include "ragged.h"
 
 #include <limits.h>
@@ -36,40 +39,6 @@ using namespace bdm;
 #define MM_Q_ONE 1073741824.f             // 2^30
 
 namespace {
-
-__device__ __forceinline__ float mm_dot(float ax, float ay, float az, float bx, float by, float bz) {
-  return (ax * bx + ay * by) + az * bz;
-}
-
-struct MmFace {
-  float v0x, v0y, v0z, v1x, v1y, v1z, v2x, v2y, v2z;
-  float nx, ny, nz, nn;   // nn == 0: invalid
-};
-
-// face `row` of the packed array, of a mesh whose vertices start at vbase and number nv.  false (and f.nn = 0) = invalid.
-__device__ __forceinline__ bool mm_face_load(const float *__restrict__ verts, const int *__restrict__ faces, long long row,
-                                             long long vbase, long long nv, MmFace &f) {
-  f.nn = 0.f;
-  const int *fp = faces + (size_t)row * 3;
-  const int i0 = fp[0], i1 = fp[1], i2 = fp[2];
-  if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= nv || i1 >= nv || i2 >= nv) return false;
-  const float *a = verts + (size_t)(vbase + i0) * 3, *b = verts + (size_t)(vbase + i1) * 3, *c = verts + (size_t)(vbase + i2) * 3;
-  f.v0x = a[0]; f.v0y = a[1]; f.v0z = a[2];
-  f.v1x = b[0]; f.v1y = b[1]; f.v1z = b[2];
-  f.v2x = c[0]; f.v2y = c[1]; f.v2z = c[2];
-  if (!(finite1(f.v0x) && finite1(f.v0y) && finite1(f.v0z) && finite1(f.v1x) && finite1(f.v1y) && finite1(f.v1z) &&
-        finite1(f.v2x) && finite1(f.v2y) && finite1(f.v2z)))
-    return false;
-  const float ex = f.v1x - f.v0x, ey = f.v1y - f.v0y, ez = f.v1z - f.v0z;   // e_0
-  const float gx = f.v2x - f.v0x, gy = f.v2y - f.v0y, gz = f.v2z - f.v0z;   // g
-  f.nx = ey * gz - ez * gy;
-  f.ny = ez * gx - ex * gz;
-  f.nz = ex * gy - ey * gx;
-  const float nn = mm_dot(f.nx, f.ny, f.nz, f.nx, f.ny, f.nz);
-  if (!(nn > 0.f && nn < INFINITY)) return false;
-  f.nn = nn;
-  return true;
-}
 
 // ---- sampler ----------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MM_THREADS) void mm_area_kernel(const float *__restrict__ verts, const int *__restrict__ faces,
@@ -203,38 +172,8 @@ __global__ __launch_bounds__(MM_THREADS) void mm_record_kernel(const float *__re
   const long long base = face_first[m], nf = face_first[m + 1] - base;
   const long long i = (long long)blockIdx.x * MM_THREADS + threadIdx.x;
   if (i >= nf) return;
-  MmFace f;
   const long long vbase = vert_first[m];
-  float4 *r = rec + (size_t)(base + i) * 4;
-  if (!mm_face_load(verts, faces, base + i, vbase, vert_first[m + 1] - vbase, f)) {
-    r[0] = r[1] = r[2] = r[3] = make_float4(0.f, 0.f, 0.f, 0.f);
-    return;
-  }
-  const float e0x = f.v1x - f.v0x, e0y = f.v1y - f.v0y, e0z = f.v1z - f.v0z;
-  const float e1x = f.v2x - f.v1x, e1y = f.v2y - f.v1y, e1z = f.v2z - f.v1z;
-  const float e2x = f.v0x - f.v2x, e2y = f.v0y - f.v2y, e2z = f.v0z - f.v2z;
-  r[0] = make_float4(f.v0x, f.v0y, f.v0z, f.v1x);
-  r[1] = make_float4(f.v1y, f.v1z, f.v2x, f.v2y);
-  r[2] = make_float4(f.v2z, f.nx, f.ny, f.nz);
-  r[3] = make_float4(f.nn, mm_dot(e0x, e0y, e0z, e0x, e0y, e0z), mm_dot(e1x, e1y, e1z, e1x, e1y, e1z), mm_dot(e2x, e2y, e2z, e2x, e2y, e2z));
-}
-
-// squared distance from x to the segment a + t e, t in [0, 1] (section 14's "Segment")
-__device__ __forceinline__ float mm_segment(float x, float y, float z, float ax, float ay, float az, float ex, float ey, float ez, float l2) {
-  const float rx = x - ax, ry = y - ay, rz = z - az;
-  const float h = mm_dot(ex, ey, ez, rx, ry, rz);
-  float t = l2 == 0.f ? 0.f : h / l2;
-  t = t > 0.f ? t : 0.f;
-  t = t < 1.f ? t : 1.f;
-  const float wx = x - (ax + t * ex), wy = y - (ay + t * ey), wz = z - (az + t * ez);
-  return mm_dot(wx, wy, wz, wx, wy, wz);
-}
-
-// s_i of the inside test: dot(n, cross(e, x - a))
-__device__ __forceinline__ float mm_side(float x, float y, float z, float ax, float ay, float az, float ex, float ey, float ez, float nx,
-                                         float ny, float nz) {
-  const float rx = x - ax, ry = y - ay, rz = z - az;
-  return mm_dot(nx, ny, nz, ey * rz - ez * ry, ez * rx - ex * rz, ex * ry - ey * rx);
+  mm_record_store(verts, faces, base + i, vbase, vert_first[m + 1] - vbase, rec + (size_t)(base + i) * 4);
 }
 
 __global__ __launch_bounds__(MM_THREADS) void mm_dist_kernel(int p, const float *__restrict__ points, const int *__restrict__ order,
@@ -271,24 +210,7 @@ __global__ __launch_bounds__(MM_THREADS) void mm_dist_kernel(int p, const float 
       const float4 r3 = tile[3][j];
       if (r3.x == 0.f) continue;   // invalid face: the same for every lane
       const float4 r0 = tile[0][j], r1 = tile[1][j], r2 = tile[2][j];
-      const float v0x = r0.x, v0y = r0.y, v0z = r0.z, v1x = r0.w, v1y = r1.x, v1z = r1.y, v2x = r1.z, v2y = r1.w, v2z = r2.x;
-      const float nx = r2.y, ny = r2.z, nz = r2.w, nn = r3.x;
-      const float e0x = v1x - v0x, e0y = v1y - v0y, e0z = v1z - v0z;
-      const float e1x = v2x - v1x, e1y = v2y - v1y, e1z = v2z - v1z;
-      const float e2x = v0x - v2x, e2y = v0y - v2y, e2z = v0z - v2z;
-      float d = mm_segment(x, y, z, v0x, v0y, v0z, e0x, e0y, e0z, r3.y);
-      const float d1 = mm_segment(x, y, z, v1x, v1y, v1z, e1x, e1y, e1z, r3.z);
-      const float d2 = mm_segment(x, y, z, v2x, v2y, v2z, e2x, e2y, e2z, r3.w);
-      d = d1 < d ? d1 : d;
-      d = d2 < d ? d2 : d;
-      const float s0 = mm_side(x, y, z, v0x, v0y, v0z, e0x, e0y, e0z, nx, ny, nz);
-      const float s1 = mm_side(x, y, z, v1x, v1y, v1z, e1x, e1y, e1z, nx, ny, nz);
-      const float s2 = mm_side(x, y, z, v2x, v2y, v2z, e2x, e2y, e2z, nx, ny, nz);
-      if (s0 >= 0.f && s1 >= 0.f && s2 >= 0.f) {
-        const float kk = mm_dot(nx, ny, nz, x - v0x, y - v0y, z - v0z);
-        const float dp = (kk * kk) / nn;
-        d = dp < d ? dp : d;
-      }
+      const float d = mm_pair_sqdist(x, y, z, r0, r1, r2, r3);
       if (d < best) { best = d; idx = t0 + j; }   // ascending face order: the first of equal distances stays
     }
   }

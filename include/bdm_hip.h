@@ -1277,6 +1277,61 @@ size_t bdm_mesh_taubin_workspace_bytes(int b, long long sum_v);
 int bdm_mesh_taubin(int b, int num_iter, int mode, float lambd, float mu, const float *verts, const long long *vert_first,
                     const int *nbr_first, const int *nbr, float *verts_out, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * 17. Face-to-point distance (csrc/face_point.hip, csrc/point_face.h): the squared distance from every face of a mesh to the nearest
+ *     point of its cloud -- section 14's pair rule with the roles of the loops exchanged; with section 14's distance it gives
+ *     pytorch3d's symmetric point_mesh_face_distance, restated from its published behaviour (pytorch3d is not installed: parity
+ *     unpinned).  DESIGN.md section 21.
+ * ---------------------------------------------------------------------------------- */
+/* Meshes: verts, faces, vert_first, face_first exactly as bdm_point_mesh_distance takes them.  Clouds are ragged: points (sum P, 3)
+ *   float32, packed and point-major; point_first holds b + 1 int64 in HOST memory under section 15's conventions (read during the
+ *   call, free afterwards; non-decreasing from 0): cloud m owns the rows point_first[m] .. point_first[m + 1] - 1.
+ * d(x, f) is section 14's d of the pair (point x, valid face f), its face quantities, valid faces and arithmetic included: one
+ *   definition (csrc/point_face.h) serves both directions, so the two see the same bits for the same pair.
+ *
+ * bdm_face_point_distance: for a valid face f of mesh m,
+ *   sqdist[f] = the smallest d(x, f) over the points x of cloud m, and point_idx[f] (int32) = the index WITHIN the cloud of the point
+ *     that has it, the lowest index among equal d: the pair is the minimum of (d, index) in lexicographic order, so it does not
+ *     depend on how the cloud is tiled, chunked or visited.
+ *   A pair whose d is NaN or +inf is never chosen.  That covers every point with a non-finite coordinate without a rule of its
+ *     own: t is clamped to [0, 1] (a NaN becomes 0), so c is finite and w = x - c is non-finite in that coordinate, w w is +inf or
+ *     NaN, and so is every d_i and d_e; k has the term n (x - v0) of that coordinate, +-inf or NaN, so d_p is +inf or NaN as well,
+ *     and d_p < d_e is false.
+ *   An invalid face gets (+inf, -1); so does every face of a mesh whose cloud is empty, and a face all of whose d overflowed.
+ *   Outputs are addressed like the packed face rows: sqdist (sum F) float32, point_idx (sum F) int32.
+ * Sign: d never has its sign bit set.  Every branch of the rule ends in dot(w, w), a sum of products of a float with itself, or in
+ *   (k k) / nn with nn > 0; a product of a float with itself is +0 or positive (or NaN), sums of such are not -0, and the quotient of
+ *   a non-negative by a positive is non-negative.  So for the values that can be chosen (finite, non-negative) the bit patterns,
+ *   read as unsigned integers, order like the numbers, and (bits of d) << 32 | index orders like (d, index).
+ * form: 0 = the chooser, 1 = resident (one workgroup per 256 faces of a mesh visits the whole cloud), 2 = split (the tiles of 1024
+ *   points of a cloud are divided over `chunks` workgroups per 256 faces; each thread sends its chunk's minimum, if it found a finite
+ *   d, through one 64-bit integer atomic minimum of the key above into the workspace, preset to bits(+inf) << 32 | 0xFFFFFFFF; a
+ *   last kernel decodes the keys, the untouched preset being (+inf, -1)).  The minimum of integers is order-free: the two forms give
+ *   the same bits.  chunks: 0 = the chooser's count (with form 2: at least 2); 1 .. 65535 with form 2 only (form 1 also takes 1).
+ *   A cloud with fewer tiles than chunks leaves the surplus workgroups idle.
+ * Chooser: bdm_face_point_distance_variant(b, sum_f, sum_p, max_p, workgroups) is a function of sizes alone and queries no device;
+ *   max_p is the largest cloud and workgroups = the sum over the meshes of ceil(F_m / 256), what the resident form keeps busy.  It
+ *   returns 2 iff 0 < workgroups < 2048 (8 per compute unit of an MI355X, whose 256 are a constant here) and max_p > 1024, otherwise
+ *   1; 0 outside the limits.  bdm_face_point_distance_chunks, same arguments: 1 for the resident form, otherwise
+ *   min(ceil(4096 / workgroups), ceil(max_p / 1024), 65535) -- the fewest chunks that reach 16 workgroups per compute unit, at most
+ *   one per tile.  The two constants are measured.
+ * Limits: 0 <= b <= 65535, every mesh has at most 2^24 faces, sum V, sum F and sum P < 2^31, offsets non-decreasing from 0, form in
+ *   {0, 1, 2}, no NULL among verts, faces, points, the three offset arrays, sqdist, point_idx and the workspace (an empty side still
+ *   passes a valid pointer, which is not read), the workspace 16-byte aligned, no output and no part of the workspace overlapping an
+ *   input or each other (judged on byte ranges).  b == 0 or sum F == 0 returns 0 without a launch; anything else outside the limits
+ *   returns 1, launches nothing and leaves the outputs untouched.
+ * workspace: bdm_face_point_distance_workspace_bytes(b, sum_f) bytes (0 outside the limits), contents irrelevant before: section 14's
+ *   64-byte record and one 8-byte key per face, and the offset arrays.
+ * Determinism: one integer atomic minimum per (face, chunk) in the split form, no floating-point atomics, vector atomics on global
+ *   memory only, no workgroup waits on another, every loop is bounded by a launch argument or a count; mesh j of a batch has the
+ *   bits of that mesh alone, and so has a repeated call, under either form and any chunk count. */
+size_t bdm_face_point_distance_workspace_bytes(int b, long long sum_f);
+int bdm_face_point_distance_variant(int b, long long sum_f, long long sum_p, long long max_p, long long workgroups);
+int bdm_face_point_distance_chunks(int b, long long sum_f, long long sum_p, long long max_p, long long workgroups);
+int bdm_face_point_distance(int b, int form, int chunks, const float *verts, const int *faces, const long long *vert_first,
+                            const long long *face_first, const float *points, const long long *point_first, float *sqdist,
+                            int *point_idx, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
