@@ -1332,6 +1332,106 @@ int bdm_face_point_distance(int b, int form, int chunks, const float *verts, con
                             const long long *face_first, const float *points, const long long *point_first, float *sqdist,
                             int *point_idx, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * 18. Rigid and similarity alignment of point clouds (csrc/align.hip, csrc/align_solve.h): the similarity transform of a cloud, the
+ *     closed-form alignment of paired points and iterative closest point; restates pytorch3d's corresponding_points_alignment and
+ *     iterative_closest_point from their published behaviour (pytorch3d is not installed: parity unpinned).  DESIGN.md section 22.
+ * ---------------------------------------------------------------------------------- */
+/* Layout: x (sum P, 3) the source and y (sum R, 3) the target, float32, packed and point-major; x_first and y_first are offset arrays
+ *   of b + 1 int64 in HOST memory under section 15's conventions (read during the call, free afterwards; non-decreasing from 0).
+ *   A transform is 13 float32 per entry: R (9, row-major), T (3), s (1), in pytorch3d's row-vector convention xt = s (x @ R) + T.
+ *
+ * Apply rule (bdm_similarity_apply; transform (b, 13) and xt (sum P, 3) on the device): per point and output axis c, every operation
+ *   rounded on its own (no FMA contraction),
+ *     d = fl(fl(fl(x0 R0c) + fl(x1 R1c)) + fl(x2 R2c));   xt_c = fl(fl(s d) + T_c).
+ *
+ * Match.  mode 0, "nearest": the source point is transformed by the entry's current transform with the apply rule; its partner is
+ *   the target row with the smallest (d2, j) of section 15 for K = 1 (d2 between the target row and the TRANSFORMED point, the lowest
+ *   index among equal d2, a pair whose d2 overflowed to +inf included).  A source point whose transformed image has a non-finite
+ *   coordinate (every non-finite source point has one) has no partner; a target row with a non-finite coordinate is nobody's partner.
+ *   mode 1, "paired": the partner of source row i is target row i; the two lengths of every entry must be equal; a pair with a
+ *   non-finite member is left out.
+ * Moments.  Over the matched pairs (x, y) of an entry -- x the UNTRANSFORMED source point -- the count W and 17 integer sums in fixed
+ *   point, 18 int64 in this order: W, Sx_a (3), Sy_b (3), S x_a y_b (9, a-major), S |x|^2, S |y|^2.
+ *     amax = the largest |coordinate| over the finite rows of the entry's x and y (an integer atomic maximum of float bits), E its
+ *     binary exponent (-126 for zero and denormals);  bits = min(24, (62 - ceil_log2(max(P, 1))) / 2), integer division;
+ *     e = bits - 1 - E;  q(c) = (long long) rint((double) c * 2^e), so |q| <= 2^bits.
+ *   Every product is an int64 product of two such values and every sum an int64 sum of at most P of them: below 2^62, exact.  Up to
+ *   16384 source points per entry all 24 mantissa bits of the largest coordinate are kept.
+ *   bdm_align_moments runs one match under `transform` ((b, 13) on the device, NULL = the identity; not read in mode 1) and writes
+ *   moments (b, 18) int64, and where not NULL exponent (b) int32 = e and partner (sum P) int32 = the partner's index WITHIN the
+ *   entry's target set, -1 for none.  It is there for tests and diagnostics.
+ * Solve (csrc/align_solve.h, float64, one operation at a time, division and square root correctly rounded).  With the sums scaled
+ *   back by the exact powers of two 2^-e and 2^-2e (the int64 -> float64 conversion rounds to nearest even) and W as a float64:
+ *     mx_a = Sx_a / W, my_b = Sy_b / W;  M_ab = S x_a y_b / W - mx_a my_b;
+ *     Xvar = S|x|^2 / W - ((mx_0^2 + mx_1^2) + mx_2^2), Yvar alike.
+ *   Rotation: Horn's symmetric, trace-free 4 x 4 matrix
+ *     N = [[Mxx+Myy+Mzz, Myz-Mzy, Mzx-Mxz, Mxy-Myx], [., Mxx-Myy-Mzz, Mxy+Myx, Mzx+Mxz], [., ., -Mxx+Myy-Mzz, Myz+Mzy],
+ *          [., ., ., -Mxx-Myy+Mzz]]
+ *   is diagonalised by 10 cyclic Jacobi sweeps over (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) with normals_eig.h's rotation formulas
+ *   (a pair whose entry is already 0 is skipped).  q = (w, x, y, z) is the eigenvector column of the largest diagonal entry, the
+ *   lowest column among equals (M = 0 gives the identity), divided by its length; Rc is the rotation matrix of q and R = Rc^T.  This
+ *   is the Kabsch / SVD solution with the determinant correction (allow_reflection = False): always a proper rotation, rank-deficient
+ *   M included.  Reflections are not offered.
+ *     tr = S_ab R_ab M_ab (a-major, sequential);  s = tr / max(Xvar, eps) with estimate_scale, else 1;
+ *     T = my - s (mx @ R);  mse = max(0, (s s) Xvar - (2 s) tr + Yvar).
+ *   mse is pytorch3d's "rmse": the mean squared residual of the pairs under the new transform, no square root taken.  It is ANALYTIC,
+ *   formed from the moments and not by a second pass over the points; on clouds that fit exactly it is rounding noise around 1e-16 of
+ *   the variance before the clamp.  R, T, s are rounded to float32; mse is kept in float64 for the stopping rule and rounded to float32
+ *   for the caller.
+ * bdm_corresponding_points_alignment: one paired match, one solve -> transform (b, 13) and, where not NULL, mse (b).  An entry
+ *   without a matched pair gets the identity and mse = NaN.
+ *
+ * Iteration.  bdm_icp_init writes the per-entry state into the workspace: transform = start ((b, 13) on the device, NULL = the
+ *   identity), iteration 0, not done, and amax.  bdm_icp_rounds performs `rounds` >= 1 times { match in mode 0 under the current
+ *   transform, solve, stopping rule } on the entries that are not done, then writes *active (one int32 on the device) = the number of
+ *   entries not done; the caller repeats the call until it reads 0, which happens after at most max_iterations rounds in all.
+ *   Every iteration aligns the START cloud x to the current partners, as pytorch3d does: the transform is total, not composed.
+ *   Stopping rule for an entry after its iteration t (counted from 1), prev = the mse of iteration t - 1, all in float64:
+ *     W == 0: done, not converged, mse = NaN, the transform and the iteration count of before (so: the start transform and 0
+ *       iterations when nothing ever matched);
+ *     mse == 0: done, converged;
+ *     t >= 2 and (prev - mse) / prev <= relative_rmse_thr: done, converged;
+ *     t == max_iterations: done, not converged.
+ *   An entry that is done is not touched again (its workgroups leave before their first barrier), so the number of rounds per call
+ *   does not enter the result.  history, where not NULL, is (b, max_iterations, 13) float32: iteration t of entry i writes row
+ *   (i, t - 1); the rows past an entry's last iteration are left untouched.  bdm_icp_finish writes xt (sum P, 3) by the apply rule
+ *   under the entry's transform, transform (b, 13), mse (b) float32, converged (b) int32 and iterations (b) int32.  The three calls
+ *   take the same b, offsets and workspace, which has to stay untouched between them; max_iterations, estimate_scale,
+ *   relative_rmse_thr and eps have to be the same in every bdm_icp_rounds call of a run.
+ *   Two deliberate differences from pytorch3d: (1) pytorch3d stops the whole batch when ALL entries pass the test, so an entry's result
+ *   depends on its batch-mates; here every entry stops on its own, and entry i of a batch has the bits of that entry alone.
+ *   (2) pytorch3d's relative test forms 0 / 0 on identical clouds and never converges; here mse == 0 is converged.
+ *
+ * Limits (all): 0 <= b <= 65535, sum P and sum R < 2^31, every entry at most 2^20 source and 2^20 target points, offsets
+ *   non-decreasing from 0, mode in {0, 1}, rounds >= 1, 1 <= max_iterations <= 10000 (with a history, 13 b max_iterations < 2^31),
+ *   eps finite and >= 0, relative_rmse_thr not NaN, no NULL among x, y, the offsets, the workspace and the outputs not marked
+ *   optional (an empty side still passes a valid pointer, which is not read), the workspace 16-byte aligned, no output and no part of
+ *   the workspace overlapping an input or another output (judged on byte ranges).  b == 0 or sum P == 0 returns 0 without a launch;
+ *   anything else outside the limits returns 1, launches nothing and leaves the outputs untouched.
+ * workspace: bdm_similarity_apply_workspace_bytes(b) bytes for the apply (the offsets); bdm_align_workspace_bytes(b) bytes for every
+ *   other call (0 outside the limits), contents irrelevant before bdm_icp_init, bdm_align_moments and
+ *   bdm_corresponding_points_alignment: the two offset arrays and a 240-byte state per entry (moments, transform, mse, amax, counters).
+ * Determinism: 64-bit integer atomic adds (the moments) and one 32-bit integer atomic maximum (amax) on global memory, ordinary vector
+ *   atomics; no floating-point atomics, no workgroup waits on another, every loop is bounded by a launch argument or an entry length.
+ *   The sums are exact, so they do not depend on the launch geometry, on how an entry is split over workgroups or on its batch slot:
+ *   entry i of a batch has the bits of that entry alone, and so has a repeated call. */
+size_t bdm_similarity_apply_workspace_bytes(int b);
+int bdm_similarity_apply(int b, const float *x, const long long *x_first, const float *transform, float *xt, void *workspace,
+                         void *stream);
+size_t bdm_align_workspace_bytes(int b);
+int bdm_align_moments(int b, int mode, const float *x, const float *y, const long long *x_first, const long long *y_first,
+                      const float *transform, long long *moments, int *exponent, int *partner, void *workspace, void *stream);
+int bdm_corresponding_points_alignment(int b, int estimate_scale, double eps, const float *x, const float *y, const long long *x_first,
+                                       const long long *y_first, float *transform, float *mse, void *workspace, void *stream);
+int bdm_icp_init(int b, const float *x, const float *y, const long long *x_first, const long long *y_first, const float *start,
+                 void *workspace, void *stream);
+int bdm_icp_rounds(int b, int rounds, int max_iterations, int estimate_scale, double relative_rmse_thr, double eps, const float *x,
+                   const float *y, const long long *x_first, const long long *y_first, float *history, int *active, void *workspace,
+                   void *stream);
+int bdm_icp_finish(int b, const float *x, const long long *x_first, const long long *y_first, float *xt, float *transform, float *mse,
+                   int *converged, int *iterations, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
