@@ -1047,6 +1047,51 @@ __global__ __launch_bounds__(256, 2) void sconv_dilh_kernel(
 
 #endif   // BDM_EXPERIMENTAL
 
+// The instance of a launch: sconv_dil_kernel<MT, NT, NW, R, H2IN> on full tiles -- a workgroup of NW waves owns a tile of <= NT * NW * 16
+// list entries x bm = 16 MT output channels (ncb channel blocks), with xcap compact input rows and lds_bytes of dynamic LDS.  Depends
+// on (cout, r, compact) only.  The half-tile form (EXPERIMENTAL=1) shares the geometry and the LDS formula below.
+struct DilVariant { int mt, nt, nw, bm, ncb, tile, xcap, tiles_max; size_t lds_bytes; };
+static bool sconv_dil_variant(int cout, int r, int compact, int half_tile, DilVariant *v) {
+  *v = DilVariant{0, 0, 0, 0, 0, 0, 0, 0, 0};
+  if ((r != 8 && r != 16 && r != 32) || cout < 1) return false;
+  const int mi = cout > 32 ? 2 : 1;                     // 64 or 32 output channels per workgroup
+  sconv_dil_geometry(r, half_tile, &v->tile, &v->xcap, &v->tiles_max);
+  v->mt = 2 * mi;
+  v->nw = half_tile ? 4 : 8;
+  v->nt = v->tile / (16 * v->nw);
+  v->bm = 32 * mi;
+  v->ncb = cdiv(cout, v->bm);
+  const int nblk = v->tile / 16, nb = (v->bm / 16) * 8;
+  size_t smem = half_tile ? 16 * (2 * ((size_t)v->xcap + 128))                          // the row ranges (weights come from global memory)
+                          : 16 * ((size_t)OS_PAIRS * 4 * v->bm + 2 * ((size_t)v->xcap + 128));
+  const size_t smem_out = sizeof(float) * ((size_t)(nblk + 1) * nb + (compact ? 0 : (size_t)v->bm * v->tile));
+  v->lds_bytes = smem_out > smem ? smem_out : smem;
+  return true;
+}
+
+// which instantiation a shape takes (host only): the very sconv_dil_variant the launch below calls, so a test can pin the instance,
+// the tile geometry and the LDS budget it means to reach.  The default library's full-tile form (tile = 0).
+extern "C" int bdm_sparse_conv_dil_variant(int b, int cin, int cout, int r, int h2in, int compact, int *mt, int *nt, int *nw, int *bm,
+                                           int *ncb, int *tile, int *xcap, int *tiles_max, int *lds_bytes) {
+  (void)b; (void)cin; (void)h2in;
+  DilVariant v;
+  const bool ok = sconv_dil_variant(cout, r, h2in ? 1 : compact, 0, &v);
+  if (mt) *mt = v.mt;
+  if (nt) *nt = v.nt;
+  if (nw) *nw = v.nw;
+  if (bm) *bm = v.bm;
+  if (ncb) *ncb = v.ncb;
+  if (tile) *tile = v.tile;
+  if (xcap) *xcap = v.xcap;
+  if (tiles_max) *tiles_max = v.tiles_max;
+  if (lds_bytes) *lds_bytes = (int)v.lds_bytes;
+  if (!ok) {
+    set_error("sparse_conv_dil: resolution %d unsupported (8, 16, 32) or cout %d < 1", r, cout);
+    return BDM_ERR_UNSUPPORTED;
+  }
+  return BDM_OK;
+}
+
 static int sconv_dil_launch(bool h2in, int b, int cin, int cout, int r, int n_max, int n_dil_max, const void *xr, const float *amax,
                             const void *xconst, float x_inv_scale, const int *in_index, const int *dil_list, const int *dil_index,
                             const int *tile_start, const void *packed_w, const float *inv_scale, const float *bias, float *y,
@@ -1062,14 +1107,10 @@ static int sconv_dil_launch(bool h2in, int b, int cin, int cout, int r, int n_ma
   BDM_REQUIRE(half_tile_ok(r, half_tile), "sparse_conv_dil: tile %d unsupported (0 = full tiles; 64 / 128 / 256: EXPERIMENTAL=1 builds)", half_tile);
   if (b == 0) return BDM_OK;
   const int c8 = (cin + 7) / 8;
-  const int mi = cout > 32 ? 2 : 1;                     // 64 or 32 output channels per workgroup
-  int tile, xcap, tiles;
-  sconv_dil_geometry(r, half_tile, &tile, &xcap, &tiles);
-  const int bm = 32 * mi, nblk = tile / 16, nb = (bm / 16) * 8, ncb = cdiv(cout, bm);
-  size_t smem = half_tile ? 16 * (2 * ((size_t)xcap + 128))                             // the row ranges (weights come from global memory)
-                          : 16 * ((size_t)OS_PAIRS * 4 * bm + 2 * ((size_t)xcap + 128));
-  const size_t smem_out = sizeof(float) * ((size_t)(nblk + 1) * nb + (compact ? 0 : (size_t)bm * tile));
-  if (smem_out > smem) smem = smem_out;
+  DilVariant dv;
+  (void)sconv_dil_variant(cout, r, compact, half_tile, &dv);   // (r and cout were checked above)
+  const int mi = dv.mt / 2, bm = dv.bm, ncb = dv.ncb, xcap = dv.xcap, tiles = dv.tiles_max;
+  const size_t smem = dv.lds_bytes;
   BDM_REQUIRE(!half_tile || smem + 1024 <= 81920, "sparse_conv_dil: the half-tile form needs two workgroups per CU (%zu bytes of LDS)", smem);
   // one persistent workgroup per CU (or per item, when there are fewer)
   static int cus[16] = {0};
@@ -1092,6 +1133,7 @@ static int sconv_dil_launch(bool h2in, int b, int cin, int cout, int r, int n_ma
   }
 #define DIL_LAUNCH_(MT, NT, NW, R, H)                                                                                      \
   do {                                                                                                                     \
+    BDM_REQUIRE(dv.mt == MT && dv.nt == NT && dv.nw == NW, "sparse_conv_dil: the launch and its variant query disagree");  \
     BDM_ALLOW_LDS((sconv_dil_kernel<MT, NT, NW, R, H>), smem);                                                             \
     hipLaunchKernelGGL((sconv_dil_kernel<MT, NT, NW, R, H>), grid, dim3(NW * 64), smem, s, c8, cout, n_max, n_dil_max,     \
                        xcap, (const float4 *)xr, amax, (const float4 *)xconst, x_inv_scale, in_index, dil_list, dil_index, \

@@ -577,6 +577,15 @@ int bdm_sparse_conv_dil(int b, int cin, int cout, int r, int n_max, int n_dil_ma
                         const int *occ_index, const int *dil_list, const int *dil_index, const int *tile_start,
                         const void *packed_w, const float *inv_scale, const float *bias, float *y, int compact, int tile,
                         int *work_counter, void *stream);
+/* Host only: the kernel instance sconv_dil_kernel<mt, nt, nw, r, h2in> and the launch geometry that bdm_sparse_conv_dil / _dil_gn
+ * (h2in = 0) and bdm_sparse_conv_dil_h2_gn (h2in = 1, always compact) use for this shape on full tiles (tile = 0) -- what the launch
+ * path itself decides, not a restatement: a workgroup of nw waves owns bm = 16 mt output channels (ncb channel blocks) x a tile of
+ * <= tile = 16 nt nw list entries whose input range holds <= xcap compact rows; tiles_max records per shape
+ * (= bdm_voxel_dilate_slices(r, 0)); lds_bytes of dynamic LDS.  Returns 0, or BDM_ERR_UNSUPPORTED (3) for a resolution other than
+ * 8, 16, 32 or cout < 1 (the outputs are then 0).  The out pointers are HOST pointers and may be NULL; no GPU call.  Depends on
+ * (cout, r, compact) only. */
+int bdm_sparse_conv_dil_variant(int b, int cin, int cout, int r, int h2in, int compact, int *mt, int *nt, int *nw, int *bm, int *ncb,
+                                int *tile, int *xcap, int *tiles_max, int *lds_bytes);
 int bdm_sparse_conv_dil_gn(int b, int cin, int cout, int r, int n_max, int n_dil_max, const void *xr, const float *amax,
                            const int *occ_index, const int *dil_list, const int *dil_index, const int *tile_start,
                            const void *packed_w, const float *inv_scale, const float *bias, float *y, int compact, int groups,
