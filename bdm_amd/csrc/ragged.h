@@ -1,5 +1,5 @@
 // ragged.h -- what the operators on packed, ragged batches share on the host side (mesh_render.hip, mesh_metrics.hip, knn.hip,
-// mesh_clean.hip): the checks on the host "first row" offset arrays, their upload, the overlap checks of the
+// mesh_clean.hip, mesh_fill.hip): the checks on the host "first row" offset arrays, their upload, the overlap checks of the
 // pointer arguments, the workspace paddings, and the workgroup scan two of them use.  The limits on batch sizes and sums differ per
 // operator and stay at the call sites.
 #pragma once

@@ -6,10 +6,12 @@ behaviour ("parity unpinned", as for the normals).
 
     python -m bdm_amd.mesh_clean --mesh_dir D/pred_mesh --out_dir D/pred_mesh_clean [--min-fraction 0.1] [--min-faces 1]
                                  [--keep-largest] [--taubin-iters 10] [--lambd 0.53] [--mu -0.34] [--weights inverse_length]
-                                 [--batch-size 16]
+                                 [--batch-size 16] [--fill-holes 0]
 
 walks the mesh .ply files of mesh_dir in sorted order, removes the small components of every mesh, smooths what is left, writes it
-under out_dir at the same relative path (vertex colours are carried along) and prints one JSON line.
+under out_dir at the same relative path (vertex colours are carried along) and prints one JSON line.  --fill-holes N > 0 closes the
+boundary loops of at most N edges between the two steps (bdm_amd.mesh_fill.fill_holes: islands, then holes, then smoothing) and adds
+the summed fill counts to the JSON line; 0, the default, leaves files and JSON as they are without the option.
 
 Departures from pytorch3d: a vertex without neighbours keeps its position (pytorch3d forms 0 / 0), `weights="uniform"` is an
 extension, no gradients."""
@@ -28,6 +30,9 @@ from .ragged import mesh_lists, pack_meshes
 MAX_B, MAX_ITER = 65535, 10000   # limits of bdm_hip.h section 16
 WEIGHTS = {"inverse_length": 0, "uniform": 1}
 ROUNDS_PER_CALL = 8   # label rounds between two reads of the `changed` flag
+# what a clean_fn that fills holes adds to the info of a mesh (mesh_fill.INFO_KEYS; that module imports this one's neighbours, not this one)
+FILL_KEYS = ("boundary_edges", "loops", "filled_loops", "too_large_loops", "pinched_loops", "nonfinite_loops", "blocked_edges", "new_vertices",
+             "new_faces")
 
 
 def _check_sizes(verts_list, faces_list):
@@ -223,7 +228,7 @@ def process_tree(mesh_dir, out_dir, clean_fn, batch_size=16):
     if batch_size < 1:
         raise ValueError("batch_size must be positive")
     items = [(path.relative_to(mesh_dir), path) for path in sorted(mesh_dir.rglob("*.ply"))]
-    sums = [0] * 7
+    sums, fill_sums = [0] * 7, {}
     for lo in range(0, len(items), batch_size):
         chunk = items[lo:lo + batch_size]
         loaded = [load_mesh_ply(path, with_colors=True) for _, path in chunk]
@@ -233,17 +238,35 @@ def process_tree(mesh_dir, out_dir, clean_fn, batch_size=16):
             save_mesh_ply(v.numpy(), f.numpy(), out_dir / rel, colors=None if c is None else c.numpy())
             for k, add in enumerate((1, v_in.shape[0], f_in.shape[0], v.shape[0], f.shape[0], i["components"], i["removed_components"])):
                 sums[k] += int(add)
-    return compose_result(*sums)
+            for k in FILL_KEYS:
+                if k in i:   # clean_fn filled holes as well
+                    fill_sums[k] = fill_sums.get(k, 0) + int(i[k])
+    result = compose_result(*sums)
+    result.update(fill_sums)
+    return result
 
 
 def clean_batch(verts_list, faces_list, colors_list, device, min_fraction=0.1, min_faces=1, keep_largest=False, taubin_iters=10, lambd=0.53,
-                mu=-0.34, weights="inverse_length"):
-    """process_tree's clean_fn on the HIP path: islands first, smoothing second (taubin_iters == 0 skips it)."""
+                mu=-0.34, weights="inverse_length", fill_holes=0):
+    """process_tree's clean_fn on the HIP path: islands first, then (fill_holes > 0) the holes of at most fill_holes edges, smoothing
+    last (taubin_iters == 0 skips it)."""
     verts, faces = [v.to(device) for v in verts_list], [f.to(device) for f in faces_list]
     V = [v.shape[0] for v in verts]
     # files without colours ride along with a zero-width colour tensor, so that one call compacts all of them
     cols = [torch.zeros(n, 0, device=device) if c is None else c.to(device) for c, n in zip(colors_list, V)]
     verts, faces, cols, info = remove_small_components((verts, faces), min_fraction, min_faces, keep_largest, colors_list=cols, return_info=True)
+    if fill_holes:
+        from . import mesh_fill
+        # a zero-width colour tensor needs no mean; a batch mixes files with and without colours only through mesh_fill.fill_batch's padding
+        widths = {c.shape[1] for c in cols}
+        if len(widths) > 1:
+            width = max(widths)
+            padded = [c if c.shape[1] == width else c.new_zeros(c.shape[0], width) for c in cols]
+            verts, faces, filled, fill_info = mesh_fill.fill_holes((verts, faces), int(fill_holes), colors_list=padded, return_info=True)
+            cols = [f if c.shape[1] == width else f[:, :0] for f, c in zip(filled, cols)]
+        else:
+            verts, faces, cols, fill_info = mesh_fill.fill_holes((verts, faces), int(fill_holes), colors_list=cols, return_info=True)
+        info = [{**i, **fi} for i, fi in zip(info, fill_info)]
     if taubin_iters:
         verts = taubin_smoothing((verts, faces), lambd, mu, taubin_iters, weights=weights).verts_list()
     return ([v.cpu() for v in verts], [f.cpu() for f in faces], [None if c0 is None else c.cpu() for c, c0 in zip(cols, colors_list)], info)
@@ -262,9 +285,13 @@ def parse_args(argv):
     ap.add_argument("--mu", type=float, default=-0.34)
     ap.add_argument("--weights", choices=sorted(WEIGHTS), default="inverse_length")
     ap.add_argument("--batch-size", type=int, default=16)
+    ap.add_argument("--fill-holes", type=int, default=0, metavar="N",
+                    help="after the islands, close the boundary loops of at most N edges (bdm_amd.mesh_fill); 0 = off")
     args = ap.parse_args(argv)
     if args.batch_size < 1:
         ap.error("--batch-size must be positive")
+    if args.fill_holes != 0 and not 3 <= args.fill_holes <= 65535:
+        ap.error("--fill-holes must be 0 (off) or lie in 3..65535")
     try:
         _check_selection(args.min_fraction, args.min_faces)
         _check_taubin(args.lambd, args.mu, args.taubin_iters, args.weights)
@@ -281,7 +308,7 @@ def main(argv=None):
 
     def clean_fn(verts_list, faces_list, colors_list):
         return clean_batch(verts_list, faces_list, colors_list, device, args.min_fraction, args.min_faces, args.keep_largest, args.taubin_iters,
-                           args.lambd, args.mu, args.weights)
+                           args.lambd, args.mu, args.weights, args.fill_holes)
 
     result = process_tree(args.mesh_dir, args.out_dir, clean_fn, args.batch_size)
     print(json.dumps(result))

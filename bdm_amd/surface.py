@@ -10,7 +10,7 @@ writes every cloud again under the same relative path as a triangle mesh and pri
 meshed as they are; the others get estimate_pointcloud_normals(..., disambiguate_directions="visibility") first.
 
 The method has no hole filling: where the grid is finer than the sampling, nodes stay undefined and the quads next to them are
-left out; `skipped_quads` and `open_edge_fraction` report it."""
+left out; `skipped_quads` and `open_edge_fraction` report it.  bdm_amd.mesh_fill.fill_holes closes the small holes afterwards."""
 import argparse
 import json
 import math

@@ -1441,6 +1441,73 @@ int bdm_icp_rounds(int b, int rounds, int max_iterations, int estimate_scale, do
 int bdm_icp_finish(int b, const float *x, const long long *x_first, const long long *y_first, float *xt, float *transform, float *mse,
                    int *converged, int *iterations, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * 19. Hole filling (csrc/mesh_fill.hip): the boundary loops of a packed batch of triangle meshes and a centroid fan over every small
+ *     simple one.  The rule is this project's own text.  DESIGN.md section 23.
+ * ---------------------------------------------------------------------------------- */
+/* Meshes: verts, faces, vert_first, face_first exactly as bdm_mesh_adjacency takes them; "connected face" as in section 16.  Every
+ *   other face takes no part and is passed through untouched.  Everything below is per mesh, indices within the mesh.
+ * 1. Half-edges: connected face f = (v0, v1, v2) has the half-edges 3 f + k, k = 0, 1, 2, running v_k -> v_{k+1}.  For an ordered pair
+ *    (a, x): out = the number of half-edges a -> x, in = the number x -> a.  (out, in) = (1, 1): the edge is INTERIOR;
+ *    (1, 0): a -> x is a BOUNDARY half-edge; every other combination is IRREGULAR (a fin, or two faces wound the same way).
+ * 2. Successor by rotation: for the boundary half-edge h = p -> a in face (p, a, x) look at a -> x.  Boundary: it is succ(h).
+ *    Interior: cross to the one face (x, a, y) that holds x -> a and go on with a -> y.  Irregular: h is BLOCKED.  This pairs the
+ *    boundary edges correctly where two holes touch at a vertex; succ is injective on what is not blocked, so the boundary half-edges
+ *    are disjoint cycles plus paths that end blocked, and every half-edge of such a path is blocked: blocked(h) = blocked(succ(h)).
+ * 3. Loops: a loop is a cycle of succ; its label is its smallest half-edge index, its size its number of half-edges (>= 3).  Labels
+ *    and blocked flags come from ceil(log2(3 max F)) + 1 rounds of pointer doubling (max F the largest face count of the batch; the
+ *    count is fixed by the host, nothing is read back); a round reads one array and writes the other.  A loop is PINCHED when one
+ *    vertex is the source of two of its half-edges and NON-FINITE when a source vertex has a non-finite coordinate.
+ * 4. Filling: a loop is filled iff size <= max_hole_edges and it is neither pinched nor non-finite.  A filled loop gets one new vertex;
+ *    the new vertices follow the mesh's old ones in ascending loop label.  Every half-edge a -> b of a filled loop gets one new face
+ *    (b, a, c), c the loop's vertex; the new faces follow the mesh's old ones in ascending half-edge index.  Old vertices and faces,
+ *    the faces that are not connected included, keep their place, order and bits.
+ * 5. The new vertex is the mean of the loop's source vertices in integer fixed point: E = the exponent of the largest finite
+ *    |coordinate| of the mesh (exponent field - 127, a field of 0 counting as 1), e = 39 - E, q(c) = rint(c 2^e) as a 64-bit integer
+ *    (rint to nearest even; |q| < 2^40), S = the integer sum of the q, mean = float32((float64(S) 2^-e) / float64(size)): the int64 ->
+ *    float64 conversion rounds to nearest even, the product with the power of two is exact, one correctly rounded float64 division,
+ *    one rounding to float32.  DESIGN.md section 23 derives |mean - exact mean| <= 2^(E-40) (1 + 2^-23) + (2^-24 + 2^-51) |exact mean|.
+ * 6. Attributes: attrs (sum V, c) float32 rows ride along (colours).  A new row is the same fixed-point mean per channel, its scale
+ *    from the largest finite |attribute| of the mesh (all channels together); a channel with a non-finite source value gives NaN.
+ *
+ * bdm_mesh_boundary_loops writes, for the H = 3 sum F half-edges of the batch (half-edge 3 f + k of mesh m at 3 face_first[m] + 3 f + k):
+ *     halfedge_loop (H) int32: the label of the half-edge's loop, -1 for a half-edge that is not on the boundary (or whose face is
+ *       not connected), -2 for a blocked one;
+ *     loop_size, loop_flags (H each) int32: at the slot of a loop's label its size and its flags, 1 filled | 2 too large (size >
+ *       max_hole_edges) | 4 pinched | 8 non-finite (a loop that is not filled may carry several); 0 at every other slot;
+ *     mesh_counts (b, 9) int32: boundary_edges (blocked ones included), loops, filled_loops, too_large_loops, pinched_loops,
+ *       nonfinite_loops, blocked_edges, new_vertices, new_faces; exact integer sums; a loop with several flags is counted under each.
+ *   It leaves the loops in the workspace for bdm_mesh_fill_holes.
+ * bdm_mesh_fill_holes, after a bdm_mesh_boundary_loops call with the same b, verts, faces, offsets and workspace (untouched in between),
+ *   writes the filled batch: verts_out (sum V', 3), attrs_out (sum V', c), faces_out (sum F', 3), packed by out_vert_first and
+ *   out_face_first (b + 1 int64 in HOST memory), which the caller forms from mesh_counts: V' = V + new_vertices, F' = F + new_faces per
+ *   mesh.  That read of mesh_counts is the only synchronisation of a fill.  Offsets that cannot be a filled mesh (V' < V, V' - V > F,
+ *   F' < F, F' - F > 3 F, F' - F < 3 (V' - V)) are refused; a row that the given sizes do not hold is never written.
+ * bdm_mesh_fill_variant(b, face_first): 0 when a call with these offsets launches nothing on the boundary list (b == 0, no faces, or
+ *   outside the limits), else 256 + the number of doubling rounds.
+ *
+ * Limits: 0 <= b <= 65535, 6 sum F < 2^31, sum V + sum F < 2^31 (a new vertex index stays an int32), offsets non-decreasing from 0,
+ *   3 <= max_hole_edges <= 65535, 0 <= c <= 16, no NULL pointer (with c == 0 attrs and attrs_out still point somewhere; they are not
+ *   read or written), the workspace 16-byte aligned, no output and no part of the workspace overlapping an input or another output
+ *   (judged on byte ranges).  b == 0 returns 0 and launches nothing; anything else outside the limits returns 1, launches nothing and
+ *   leaves the outputs untouched.  bdm_mesh_fill_workspace_bytes returns 0 outside the limits.
+ * workspace: bdm_mesh_fill_workspace_bytes(b, sum_v, sum_f) bytes, contents irrelevant before bdm_mesh_boundary_loops: the offsets, two
+ *   counters per vertex, six 8-byte corner records per face (neighbour, direction, half-edge; sorted per vertex), and per half-edge the
+ *   compaction scan and the arrays of the compacted boundary list, which is all the walk, the doubling rounds, the loop statistics and
+ *   the fill touch.
+ * Determinism: integer atomics only (slot claims, counts, flag bits, one maximum per mesh), no floating-point atomics, no workgroup
+ *   waits on another, every loop is bounded by a launch argument, a segment length or a loop size.  The coordinate sums are integers,
+ *   formed by one thread per loop.  Mesh j of a batch has the bits of that mesh alone, and so has a repeated call.  A vertex of very
+ *   high valence or a very long filled loop is slow (one thread handles it), never wrong. */
+size_t bdm_mesh_fill_workspace_bytes(int b, long long sum_v, long long sum_f);
+int bdm_mesh_fill_variant(int b, const long long *face_first);
+int bdm_mesh_boundary_loops(int b, int max_hole_edges, const float *verts, const int *faces, const long long *vert_first,
+                            const long long *face_first, int *halfedge_loop, int *loop_size, int *loop_flags, int *mesh_counts,
+                            void *workspace, void *stream);
+int bdm_mesh_fill_holes(int b, int c, const float *verts, const float *attrs, const int *faces, const long long *vert_first,
+                        const long long *face_first, const long long *out_vert_first, const long long *out_face_first, float *verts_out,
+                        float *attrs_out, int *faces_out, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
