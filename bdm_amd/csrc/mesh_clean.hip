@@ -10,13 +10,9 @@
 //
 // Kernels.
 //   (ragged.h)             send_offsets: the two host offset arrays travel as launch arguments into the workspace.
-//   mc_fill_kernel         an int array set to one value (counters, rows past the component count).
-//   mc_scan_kernel<false>  one workgroup per MC_CHUNK entries: their sum.  mc_scan_top_kernel: one workgroup, the exclusive scan of
-//   mc_scan_kernel<true>   those sums in place.  Then every workgroup scans its entries again, plus its offset: an exclusive scan in place.
-//   mc_incidence_kernel<false>  one thread per face: a connected face adds 2 to the counter of each of its vertices.
-//   mc_incidence_kernel<true>   the same walk: claims two slots per vertex (atomicAdd on a cursor) and writes the two other vertices.
-//   mc_sort_kernel         one thread per vertex: sorts its segment in place (insertion sort, heap sort above MC_INSERTION_MAX), drops
-//                          the repeats, counts what is left.
+//   (mesh_incidence.h)     fill_ints_kernel, scan_kernel<false / true>, scan_top_kernel, and incidence_kernel<false / true, McNeighbours>:
+//                          the records of a corner are the face's two other vertices.
+//   mc_sort_kernel         one thread per vertex: sorts its segment in place (sort_segment), drops the repeats, counts what is left.
 //   mc_compact_kernel      one thread per vertex: its list moves to its place in nbr.
 //   mc_label_init_kernel, mc_label_round_kernel (Jacobi: reads one label array, writes the other), mc_label_copy_kernel, mc_flag_kernel.
 //   mc_root_kernel         1 where label == index; scanned, it ranks the components.  mc_vert_comp_kernel, mc_face_comp_kernel.
@@ -24,7 +20,7 @@
 //                          neighbouring vertices, one 16-byte load per neighbour; LAST writes 12-byte rows to the output.
 #include "../../include/bdm_hip.h"
 #include "common.h"
-#include "ragged.h"
+#include "mesh_incidence.h"
 
 #include <limits.h>
 #include <math.h>
@@ -33,103 +29,16 @@
 
 using namespace bdm;
 
-#define MC_THREADS 256
-#define MC_CHUNK (4 * MC_THREADS)         // entries per workgroup of the scan
-#define MC_MAX_B 65535                    // gridDim.y
-#define MC_INSERTION_MAX 32               // longer segments are heap-sorted
+#define MC_THREADS MESH_THREADS
 #define MC_MAX_ITER 10000
 
 namespace {
 
-__global__ __launch_bounds__(MC_THREADS) void mc_fill_kernel(int *__restrict__ a, long long n, int value) {
-  const long long i = (long long)blockIdx.x * MC_THREADS + threadIdx.x;
-  if (i < n) a[i] = value;
-}
-
-// ---- exclusive scan of n int32 entries in place, in three launches ------------------------------------------------------------------
-template <bool WRITE>
-__global__ __launch_bounds__(MC_THREADS) void mc_scan_kernel(int *__restrict__ a, long long n, int *__restrict__ bsum) {
-  __shared__ int buf[MC_THREADS];
-  const long long base = (long long)blockIdx.x * MC_CHUNK + 4 * (long long)threadIdx.x;   // the grid covers n: no workgroup leaves early
-  int v[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = base + e < n ? a[base + e] : 0;
-  const int s = (v[0] + v[1]) + (v[2] + v[3]);
-  const int incl = block_scan<int, MC_THREADS>(s, buf);
-  if (WRITE) {
-    int run = bsum[blockIdx.x] + incl - s;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if (base + e < n) a[base + e] = run;
-      run += v[e];
-    }
-  } else if (threadIdx.x == MC_THREADS - 1) {
-    bsum[blockIdx.x] = incl;
-  }
-}
-
-__global__ __launch_bounds__(MC_THREADS) void mc_scan_top_kernel(int *__restrict__ bsum, int nb) {
-  __shared__ int buf[MC_THREADS];
-  int carry = 0;
-  for (int c0 = 0; c0 < nb; c0 += MC_THREADS) {   // uniform trip count
-    const int i = c0 + threadIdx.x;
-    const int v = i < nb ? bsum[i] : 0;
-    const int incl = block_scan<int, MC_THREADS>(v, buf);
-    if (i < nb) bsum[i] = carry + incl - v;
-    buf[threadIdx.x] = incl;
-    __syncthreads();
-    carry += buf[MC_THREADS - 1];
-    __syncthreads();
-  }
-}
-
 // ---- adjacency ------------------------------------------------------------------------------------------------------------------------
-// the three indices of face `row` if it is a connected face of a mesh of nv vertices
-__device__ __forceinline__ bool mc_connected(const int *__restrict__ faces, long long row, long long nv, int &i0, int &i1, int &i2) {
-  const int *fp = faces + (size_t)row * 3;
-  i0 = fp[0], i1 = fp[1], i2 = fp[2];
-  if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= nv || i1 >= nv || i2 >= nv) return false;
-  return i0 != i1 && i1 != i2 && i0 != i2;
-}
-
-// WRITE = false: first[g] += 2 per connected face around packed vertex g.  WRITE = true: first is the scanned array; two slots of g's
-// segment are claimed on cursor[g] and take the face's two other vertices.
-template <bool WRITE>
-__global__ __launch_bounds__(MC_THREADS) void mc_incidence_kernel(const int *__restrict__ faces, const long long *__restrict__ vert_first,
-                                                                  const long long *__restrict__ face_first, int *__restrict__ first,
-                                                                  int *__restrict__ cursor, int *__restrict__ raw) {
-  const int m = blockIdx.y;
-  const long long fbase = face_first[m], nf = face_first[m + 1] - fbase;
-  const long long i = (long long)blockIdx.x * MC_THREADS + threadIdx.x;
-  if (i >= nf) return;
-  const long long vbase = vert_first[m];
-  int idx[3];
-  if (!mc_connected(faces, fbase + i, vert_first[m + 1] - vbase, idx[0], idx[1], idx[2])) return;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const long long g = vbase + idx[c];
-    if (WRITE) {
-      const int slot = first[g] + atomicAdd(cursor + g, 2);   // < first[g + 1]: the count pass added 2 for this face
-      raw[slot] = idx[(c + 1) % 3];
-      raw[slot + 1] = idx[(c + 2) % 3];
-    } else {
-      atomicAdd(first + g, 2);
-    }
-  }
-}
-
-__device__ __forceinline__ void mc_sift_down(int *__restrict__ a, int root, int end) {   // max-heap on a[0 .. end)
-  const int v = a[root];
-  for (;;) {   // at most log2(end) steps: the child index doubles
-    int child = 2 * root + 1;
-    if (child >= end) break;
-    if (child + 1 < end && a[child + 1] > a[child]) ++child;
-    if (a[child] <= v) break;
-    a[root] = a[child];
-    root = child;
-  }
-  a[root] = v;
-}
+struct McNeighbours {   // Rec of incidence_kernel: a vertex records the two other vertices of every connected face around it
+  typedef int type;
+  static __device__ __forceinline__ void corner(const int (&idx)[3], int, int c, int &r0, int &r1) { r0 = idx[(c + 1) % 3], r1 = idx[(c + 2) % 3]; }
+};
 
 // one thread per packed vertex: its segment raw[first[g] .. first[g + 1]) sorted ascending in place, repeats dropped; degree[g] = what is left
 __global__ __launch_bounds__(MC_THREADS) void mc_sort_kernel(long long sum_v, const int *__restrict__ first, int *__restrict__ raw,
@@ -142,22 +51,7 @@ __global__ __launch_bounds__(MC_THREADS) void mc_sort_kernel(long long sum_v, co
   }
   int *a = raw + first[g];
   const int len = first[g + 1] - first[g];
-  if (len <= MC_INSERTION_MAX) {
-    for (int i = 1; i < len; ++i) {
-      const int v = a[i];
-      int j = i;
-      for (; j > 0 && a[j - 1] > v; --j) a[j] = a[j - 1];
-      a[j] = v;
-    }
-  } else {
-    for (int root = len / 2 - 1; root >= 0; --root) mc_sift_down(a, root, len);
-    for (int end = len - 1; end > 0; --end) {
-      const int top = a[0];
-      a[0] = a[end];
-      a[end] = top;
-      mc_sift_down(a, 0, end);
-    }
-  }
+  sort_segment(a, len);
   int kept = 0;
   for (int i = 0; i < len; ++i) {
     const int v = a[i];
@@ -246,9 +140,9 @@ __global__ __launch_bounds__(MC_THREADS) void mc_face_comp_kernel(const int *__r
   const long long i = (long long)blockIdx.x * MC_THREADS + threadIdx.x;
   if (i >= nf) return;
   const long long vbase = vert_first[m];
-  int i0, i1, i2, c = -1;
-  if (mc_connected(faces, fbase + i, vert_first[m + 1] - vbase, i0, i1, i2)) {
-    c = vert_comp[vbase + i0];
+  int idx[3], c = -1;
+  if (connected_face(faces, fbase + i, vert_first[m + 1] - vbase, idx)) {
+    c = vert_comp[vbase + idx[0]];
     atomicAdd(comp_faces + vbase + c, 1);
   }
   face_comp[fbase + i] = c;
@@ -316,28 +210,25 @@ __global__ __launch_bounds__(MC_THREADS) void mc_taubin_kernel(float f, float om
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
-long long mc_scan_blocks(long long n) { return cdivll(n, MC_CHUNK); }
-
 bool mc_sizes_ok(int b, long long sum_v, long long sum_f) {
-  return b >= 0 && b <= MC_MAX_B && sum_v >= 0 && sum_v < INT_MAX && sum_f >= 0 && 6 * sum_f <= INT_MAX;
+  return b >= 0 && b <= MESH_MAX_B && sum_v >= 0 && sum_v < INT_MAX && sum_f >= 0 && 6 * sum_f <= INT_MAX;
 }
 
-// workspace of bdm_mesh_adjacency: offsets | first (sum V + 1) | cursor (sum V) | partial sums | raw (6 sum F)
+// workspace of bdm_mesh_adjacency: offsets | first (sum V + 1) | cursor (sum V + 1) | partial sums | raw (6 sum F)
 struct McAdjWs {
   long long *vert_first, *face_first;
   int *first, *cursor, *bsum, *raw;
   size_t bytes;
 };
 McAdjWs mc_adj_ws(void *ws, int b, long long sum_v, long long sum_f) {
-  char *p = (char *)ws;
+  Carve c{(char *)ws, 0};
   McAdjWs w;
-  w.vert_first = (long long *)p, w.face_first = w.vert_first + (b + 1);
-  size_t o = offsets_bytes(b);
-  w.first = (int *)(p + o), o += align16(4 * (size_t)(sum_v + 1));
-  w.cursor = (int *)(p + o), o += align16(4 * (size_t)(sum_v + 1));
-  w.bsum = (int *)(p + o), o += align16(4 * (size_t)mc_scan_blocks(sum_v + 1));
-  w.raw = (int *)(p + o), o += align16(4 * 6 * (size_t)sum_f);
-  w.bytes = o;
+  w.vert_first = c.take_offsets(b), w.face_first = w.vert_first + (b + 1);
+  w.first = c.take<int>((size_t)(sum_v + 1));
+  w.cursor = c.take<int>((size_t)(sum_v + 1));
+  w.bsum = c.take<int>((size_t)scan_blocks(sum_v + 1));
+  w.raw = c.take<int>(6 * (size_t)sum_f);
+  w.bytes = c.o;
   return w;
 }
 
@@ -348,53 +239,30 @@ struct McCompWs {
   size_t bytes;
 };
 McCompWs mc_comp_ws(void *ws, int b, long long sum_v) {
-  char *p = (char *)ws;
+  Carve c{(char *)ws, 0};
   McCompWs w;
-  w.vert_first = (long long *)p, w.face_first = w.vert_first + (b + 1);
-  size_t o = offsets_bytes(b);
-  w.label = (int *)(p + o), o += align16(4 * (size_t)sum_v);
-  w.label2 = (int *)(p + o), o += align16(4 * (size_t)sum_v);
-  w.rank = (int *)(p + o), o += align16(4 * (size_t)(sum_v + 1));
-  w.bsum = (int *)(p + o), o += align16(4 * (size_t)mc_scan_blocks(sum_v + 1));
-  w.bytes = o;
+  w.vert_first = c.take_offsets(b), w.face_first = w.vert_first + (b + 1);
+  w.label = c.take<int>((size_t)sum_v);
+  w.label2 = c.take<int>((size_t)sum_v);
+  w.rank = c.take<int>((size_t)(sum_v + 1));
+  w.bsum = c.take<int>((size_t)scan_blocks(sum_v + 1));
+  w.bytes = c.o;
   return w;
 }
 
 size_t mc_taubin_bytes(int b, long long sum_v) { return offsets_bytes(b) + 2 * 16 * (size_t)sum_v; }
 
-// the checks on the offset arrays every entry point shares -> 0, or 1 with the error set; face_first may be NULL (not used by the call)
-int mc_check_offsets(const char *what, int b, const long long *vert_first, const long long *face_first, long long &max_v, long long &max_f) {
-  max_f = 0;
-  if (check_first(what, "mesh", b, vert_first, &max_v) != BDM_OK) return BDM_ERR_ARG;
-  if (face_first && check_first(what, "mesh", b, face_first, &max_f) != BDM_OK) return BDM_ERR_ARG;
-  BDM_REQUIRE(vert_first[b] < INT_MAX, "%s: %lld vertices reach 2^31", what, vert_first[b]);
-  BDM_REQUIRE(!face_first || 6 * face_first[b] <= INT_MAX, "%s: %lld faces: six entries per face reach 2^31", what, face_first[b]);
-  return BDM_OK;
-}
-
-void mc_fill(int *a, long long n, int value, hipStream_t s) {
-  if (n > 0) hipLaunchKernelGGL(mc_fill_kernel, dim3((unsigned)cdivll(n, MC_THREADS)), dim3(MC_THREADS), 0, s, a, n, value);
-}
-
-// exclusive scan of a[0 .. n) in place (n >= 1); bsum: mc_scan_blocks(n) ints
-void mc_scan(int *a, long long n, int *bsum, hipStream_t s) {
-  const unsigned nb = (unsigned)mc_scan_blocks(n);
-  hipLaunchKernelGGL(mc_scan_kernel<false>, dim3(nb), dim3(MC_THREADS), 0, s, a, n, bsum);
-  hipLaunchKernelGGL(mc_scan_top_kernel, dim3(1), dim3(MC_THREADS), 0, s, bsum, (int)nb);
-  hipLaunchKernelGGL(mc_scan_kernel<true>, dim3(nb), dim3(MC_THREADS), 0, s, a, n, bsum);
-}
-
-// the prologue every entry point shares: limits on b, the offsets, the workspace pointer.  -> BDM_OK with nothing_to_do set when the call returns 0 at once
+// the prologue every entry point shares: the batch checks, the limits on the sums, the workspace pointer; face_first may be NULL when
+// the call uses no faces.  -> BDM_OK with nothing_to_do set when the call returns 0 at once
 int mc_prologue(const char *what, int b, const long long *vert_first, const long long *face_first, bool needs_faces, const void *workspace,
                 long long &max_v, long long &max_f, bool &nothing_to_do) {
   nothing_to_do = true;
-  BDM_REQUIRE(b >= 0 && b <= MC_MAX_B, "%s: batch size %d outside 0 .. %d", what, b, MC_MAX_B);
+  if (check_mesh_batch(what, b, vert_first, face_first, needs_faces, &max_v, &max_f) != BDM_OK) return BDM_ERR_ARG;
   if (b == 0) return BDM_OK;
-  BDM_REQUIRE(vert_first && (face_first || !needs_faces), "%s: an offset array is NULL", what);
-  if (mc_check_offsets(what, b, vert_first, face_first, max_v, max_f) != BDM_OK) return BDM_ERR_ARG;
-  if (vert_first[b] == 0) return BDM_OK;
-  BDM_REQUIRE(workspace, "%s: the workspace is NULL", what);
-  BDM_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: the workspace is not 16-byte aligned", what);
+  BDM_REQUIRE(vert_first[b] < INT_MAX, "%s: %lld vertices reach 2^31", what, vert_first[b]);
+  BDM_REQUIRE(!face_first || 6 * face_first[b] <= INT_MAX, "%s: %lld faces: six entries per face reach 2^31", what, face_first[b]);
+  if (vert_first[b] == 0) return BDM_OK;   // before the workspace is looked at
+  if (check_workspace(what, workspace) != BDM_OK) return BDM_ERR_ARG;
   nothing_to_do = false;
   return BDM_OK;
 }
@@ -420,18 +288,10 @@ extern "C" int bdm_mesh_adjacency(int b, const int *faces, const long long *vert
   if (check_overlap("mesh_adjacency", in, 1, out, 3) != BDM_OK) return BDM_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   send_offsets(b, vert_first, face_first, w.vert_first, w.face_first, st);
-  mc_fill(w.first, sum_v + 1, 0, st);
-  mc_fill(w.cursor, sum_v + 1, 0, st);
+  build_incidence<McNeighbours>(b, sum_v, max_f, faces, w.vert_first, w.face_first, w.first, w.cursor, w.bsum, w.raw, st);
   const unsigned flat_v = (unsigned)cdivll(sum_v + 1, MC_THREADS);
-  if (max_f > 0)
-    hipLaunchKernelGGL(mc_incidence_kernel<false>, dim3((unsigned)cdivll(max_f, MC_THREADS), (unsigned)b), dim3(MC_THREADS), 0, st, faces,
-                       w.vert_first, w.face_first, w.first, w.cursor, w.raw);
-  mc_scan(w.first, sum_v + 1, w.bsum, st);
-  if (max_f > 0)
-    hipLaunchKernelGGL(mc_incidence_kernel<true>, dim3((unsigned)cdivll(max_f, MC_THREADS), (unsigned)b), dim3(MC_THREADS), 0, st, faces,
-                       w.vert_first, w.face_first, w.first, w.cursor, w.raw);
   hipLaunchKernelGGL(mc_sort_kernel, dim3(flat_v), dim3(MC_THREADS), 0, st, sum_v, w.first, w.raw, nbr_first);
-  mc_scan(nbr_first, sum_v + 1, w.bsum, st);
+  exclusive_scan_ints(nbr_first, sum_v + 1, nullptr, w.bsum, st);
   hipLaunchKernelGGL(mc_compact_kernel, dim3(flat_v), dim3(MC_THREADS), 0, st, sum_v, w.first, w.raw, nbr_first, nbr);
   return launch_status("mesh_adjacency");
 }
@@ -497,9 +357,9 @@ extern "C" int bdm_mesh_components_finish(int b, const int *faces, const long lo
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid_v((unsigned)cdivll(max_v, MC_THREADS), (unsigned)b);
   hipLaunchKernelGGL(mc_root_kernel, grid_v, dim3(MC_THREADS), 0, st, w.vert_first, sum_v, w.label, w.rank);
-  mc_scan(w.rank, sum_v + 1, w.bsum, st);
-  mc_fill(comp_verts, sum_v, 0, st);
-  mc_fill(comp_faces, sum_v, 0, st);
+  exclusive_scan_ints(w.rank, sum_v + 1, nullptr, w.bsum, st);
+  fill_ints(comp_verts, sum_v, 0, st);
+  fill_ints(comp_faces, sum_v, 0, st);
   hipLaunchKernelGGL(mc_vert_comp_kernel, grid_v, dim3(MC_THREADS), 0, st, w.vert_first, w.label, w.rank, vert_comp, comp_count, comp_verts);
   if (max_f > 0)
     hipLaunchKernelGGL(mc_face_comp_kernel, dim3((unsigned)cdivll(max_f, MC_THREADS), (unsigned)b), dim3(MC_THREADS), 0, st, faces, w.vert_first,

@@ -11,13 +11,10 @@
 //
 // Kernels.
 //   (ragged.h)            send_offsets: the host offset arrays travel as launch arguments into the workspace.
-//   mf_fill_kernel        an int array set to one value.
-//   mf_scan_kernel<false>, mf_scan_top_kernel, mf_scan_kernel<true>: exclusive scan in place; the entry count may live on the device
-//                         (the compacted list), and workgroups past it leave at once.
-//   mf_corner_kernel<false>  one thread per face: a connected face adds 2 to the counter of each of its vertices.
-//   mf_corner_kernel<true>   the same walk: claims two slots per vertex and writes the two records of the corner, 64-bit keys
-//                            neighbour << 32 | direction << 31 | half-edge (direction 0: vertex -> neighbour, 1: neighbour -> vertex).
-//   mf_sort_kernel        one thread per vertex: sorts its segment of keys (insertion sort, heap sort above MF_INSERTION_MAX).
+//   (mesh_incidence.h)    fill_ints_kernel; scan_kernel<false / true>, scan_top_kernel: the entry count may live on the device (the
+//                         compacted list); incidence_kernel<false / true, MfKeys>: the records of a corner are two 64-bit keys
+//                         neighbour << 32 | direction << 31 | half-edge (direction 0: vertex -> neighbour, 1: neighbour -> vertex).
+//   mf_sort_kernel        one thread per vertex: sorts its segment of keys (sort_segment).
 //   mf_classify_kernel    one thread per half-edge: boundary or not; presets the three per-half-edge outputs.
 //   mf_compact_kernel     one thread per half-edge: a boundary half-edge moves to its scanned place (order kept).
 //   Everything below runs on the compacted list, grid-stride, its length read from the device:
@@ -31,7 +28,7 @@
 //   mf_emit_kernel        one thread per boundary half-edge of a filled loop: its face.
 #include "../../include/bdm_hip.h"
 #include "common.h"
-#include "ragged.h"
+#include "mesh_incidence.h"
 #include "align_solve.h"   // align_pow2, align_ceil_log2
 
 #include <limits.h>
@@ -41,10 +38,7 @@
 
 using namespace bdm;
 
-#define MF_THREADS 256
-#define MF_CHUNK (4 * MF_THREADS)         // entries per workgroup of the scan
-#define MF_MAX_B 65535                    // gridDim.y
-#define MF_INSERTION_MAX 32               // longer segments are heap-sorted
+#define MF_THREADS MESH_THREADS
 #define MF_MAX_EDGES 65535
 #define MF_MAX_C 16
 #define MF_COUNTS 9                       // per-mesh counters, in the order of bdm_hip.h section 19
@@ -64,120 +58,18 @@ __device__ __forceinline__ int mf_key_nbr(mf_key k) { return (int)(k >> 32); }
 __device__ __forceinline__ int mf_key_dir(mf_key k) { return (int)((k >> 31) & 1); }
 __device__ __forceinline__ int mf_key_half(mf_key k) { return (int)(k & 0x7fffffffll); }
 
-__global__ __launch_bounds__(MF_THREADS) void mf_fill_kernel(int *__restrict__ a, long long n, int value) {
-  const long long i = (long long)blockIdx.x * MF_THREADS + threadIdx.x;
-  if (i < n) a[i] = value;
-}
-
-// ---- exclusive scan of n int32 entries in place; n = n_host, or *n_dev + 1 when n_dev is given (n_host then bounds the grid) --------
-template <bool WRITE>
-__global__ __launch_bounds__(MF_THREADS) void mf_scan_kernel(int *__restrict__ a, long long n_host, const int *__restrict__ n_dev,
-                                                             int *__restrict__ bsum) {
-  __shared__ int buf[MF_THREADS];
-  const long long n = n_dev ? (long long)*n_dev + 1 : n_host;
-  const long long base = (long long)blockIdx.x * MF_CHUNK + 4 * (long long)threadIdx.x;
-  if ((long long)blockIdx.x * MF_CHUNK >= n) return;   // the whole workgroup leaves: no barrier is left waiting
-  int v[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = base + e < n ? a[base + e] : 0;
-  const int s = (v[0] + v[1]) + (v[2] + v[3]);
-  const int incl = block_scan<int, MF_THREADS>(s, buf);
-  if (WRITE) {
-    int run = bsum[blockIdx.x] + incl - s;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if (base + e < n) a[base + e] = run;
-      run += v[e];
-    }
-  } else if (threadIdx.x == MF_THREADS - 1) {
-    bsum[blockIdx.x] = incl;
+struct MfKeys {   // Rec of incidence_kernel: corner c of face i records its outgoing and its incoming half-edge
+  typedef mf_key type;
+  static __device__ __forceinline__ void corner(const int (&idx)[3], int i, int c, mf_key &r0, mf_key &r1) {
+    r0 = mf_make_key(idx[(c + 1) % 3], 0, 3 * i + c);                 // this vertex -> the next one
+    r1 = mf_make_key(idx[(c + 2) % 3], 1, 3 * i + (c + 2) % 3);       // the previous one -> this vertex
   }
-}
-
-__global__ __launch_bounds__(MF_THREADS) void mf_scan_top_kernel(int *__restrict__ bsum, long long n_host, const int *__restrict__ n_dev) {
-  __shared__ int buf[MF_THREADS];
-  const long long n = n_dev ? (long long)*n_dev + 1 : n_host;
-  const int nb = (int)((n + MF_CHUNK - 1) / MF_CHUNK);
-  int carry = 0;
-  for (int c0 = 0; c0 < nb; c0 += MF_THREADS) {   // uniform trip count
-    const int i = c0 + threadIdx.x;
-    const int v = i < nb ? bsum[i] : 0;
-    const int incl = block_scan<int, MF_THREADS>(v, buf);
-    if (i < nb) bsum[i] = carry + incl - v;
-    buf[threadIdx.x] = incl;
-    __syncthreads();
-    carry += buf[MF_THREADS - 1];
-    __syncthreads();
-  }
-}
-
-// ---- corner table ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool mf_connected(const int *__restrict__ faces, long long row, long long nv, int (&idx)[3]) {
-  const int *fp = faces + (size_t)row * 3;
-  idx[0] = fp[0], idx[1] = fp[1], idx[2] = fp[2];
-  if (idx[0] < 0 || idx[1] < 0 || idx[2] < 0 || idx[0] >= nv || idx[1] >= nv || idx[2] >= nv) return false;
-  return idx[0] != idx[1] && idx[1] != idx[2] && idx[0] != idx[2];
-}
-
-template <bool WRITE>
-__global__ __launch_bounds__(MF_THREADS) void mf_corner_kernel(const int *__restrict__ faces, const long long *__restrict__ vert_first,
-                                                               const long long *__restrict__ face_first, int *__restrict__ first,
-                                                               int *__restrict__ cursor, mf_key *__restrict__ rec) {
-  const int m = blockIdx.y;
-  const long long fbase = face_first[m], nf = face_first[m + 1] - fbase;
-  const long long i = (long long)blockIdx.x * MF_THREADS + threadIdx.x;
-  if (i >= nf) return;
-  const long long vbase = vert_first[m];
-  int idx[3];
-  if (!mf_connected(faces, fbase + i, vert_first[m + 1] - vbase, idx)) return;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const long long g = vbase + idx[c];
-    if (WRITE) {
-      const int slot = first[g] + atomicAdd(cursor + g, 2);   // < first[g + 1]: the count pass added 2 for this face
-      rec[slot] = mf_make_key(idx[(c + 1) % 3], 0, 3 * (int)i + c);                 // this vertex -> the next one
-      rec[slot + 1] = mf_make_key(idx[(c + 2) % 3], 1, 3 * (int)i + (c + 2) % 3);   // the previous one -> this vertex
-    } else {
-      atomicAdd(first + g, 2);
-    }
-  }
-}
-
-__device__ __forceinline__ void mf_sift_down(mf_key *__restrict__ a, int root, int end) {   // max-heap on a[0 .. end)
-  const mf_key v = a[root];
-  for (;;) {   // at most log2(end) steps: the child index doubles
-    int child = 2 * root + 1;
-    if (child >= end) break;
-    if (child + 1 < end && a[child + 1] > a[child]) ++child;
-    if (a[child] <= v) break;
-    a[root] = a[child];
-    root = child;
-  }
-  a[root] = v;
-}
+};
 
 // one thread per packed vertex: its segment of keys sorted ascending in place (the keys are all different: the half-edge is part of them)
 __global__ __launch_bounds__(MF_THREADS) void mf_sort_kernel(long long sum_v, const int *__restrict__ first, mf_key *__restrict__ rec) {
   const long long g = (long long)blockIdx.x * MF_THREADS + threadIdx.x;
-  if (g >= sum_v) return;
-  mf_key *a = rec + first[g];
-  const int len = first[g + 1] - first[g];
-  if (len <= MF_INSERTION_MAX) {
-    for (int i = 1; i < len; ++i) {
-      const mf_key v = a[i];
-      int j = i;
-      for (; j > 0 && a[j - 1] > v; --j) a[j] = a[j - 1];
-      a[j] = v;
-    }
-  } else {
-    for (int root = len / 2 - 1; root >= 0; --root) mf_sift_down(a, root, len);
-    for (int end = len - 1; end > 0; --end) {
-      const mf_key top = a[0];
-      a[0] = a[end];
-      a[end] = top;
-      mf_sift_down(a, 0, end);
-    }
-  }
+  if (g < sum_v) sort_segment(rec + first[g], first[g + 1] - first[g]);
 }
 
 // the half-edges between a and x in a's sorted segment: how many run a -> x (out) and x -> a (in), and the last x -> a seen
@@ -212,7 +104,7 @@ __global__ __launch_bounds__(MF_THREADS) void mf_classify_kernel(const int *__re
   const long long vbase = vert_first[m], hg = 3 * fbase + h;
   const int f = (int)(h / 3), k = (int)(h - 3 * (long long)f);
   int idx[3], boundary = 0;
-  if (mf_connected(faces, fbase + f, vert_first[m + 1] - vbase, idx)) {
+  if (connected_face(faces, fbase + f, vert_first[m + 1] - vbase, idx)) {
     const int a = idx[k], x = idx[(k + 1) % 3];
     const int s0 = first[vbase + a];
     int out, in, in_half;
@@ -506,10 +398,8 @@ __global__ __launch_bounds__(MF_THREADS) void mf_emit_kernel(const int *__restri
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
-long long mf_scan_blocks(long long n) { return cdivll(n, MF_CHUNK); }
-
 bool mf_sizes_ok(int b, long long sum_v, long long sum_f) {
-  return b >= 0 && b <= MF_MAX_B && sum_v >= 0 && sum_f >= 0 && 6 * sum_f <= INT_MAX && sum_v + sum_f < INT_MAX;
+  return b >= 0 && b <= MESH_MAX_B && sum_v >= 0 && sum_f >= 0 && 6 * sum_f <= INT_MAX && sum_v + sum_f < INT_MAX;
 }
 
 // offsets | output offsets | first (sum V + 1) | cursor (sum V + 1) | partial sums | records (6 sum F keys) | pos (H + 1) | bh, bm, succ,
@@ -523,39 +413,26 @@ struct MfWs {
   size_t bytes;
 };
 MfWs mf_ws(void *ws, int b, long long sum_v, long long sum_f) {
-  char *p = (char *)ws;
+  Carve c{(char *)ws, 0};
   MfWs w;
   const size_t H = 3 * (size_t)sum_f;
-  size_t o = 0;
-  w.vert_first = (long long *)p, w.face_first = w.vert_first + (b + 1), o += offsets_bytes(b);
-  w.out_vert_first = (long long *)(p + o), w.out_face_first = w.out_vert_first + (b + 1), o += offsets_bytes(b);
-  w.first = (int *)(p + o), o += align16(4 * (size_t)(sum_v + 1));
-  w.cursor = (int *)(p + o), o += align16(4 * (size_t)(sum_v + 1));
+  w.vert_first = c.take_offsets(b), w.face_first = w.vert_first + (b + 1);
+  w.out_vert_first = c.take_offsets(b), w.out_face_first = w.out_vert_first + (b + 1);
+  w.first = c.take<int>((size_t)(sum_v + 1));
+  w.cursor = c.take<int>((size_t)(sum_v + 1));
   const long long longest = sum_v + 1 > (long long)H + 1 ? sum_v + 1 : (long long)H + 1;
-  w.bsum = (int *)(p + o), o += align16(4 * (size_t)mf_scan_blocks(longest));
-  w.rec = (mf_key *)(p + o), o += align16(8 * 6 * (size_t)sum_f);
-  w.pos = (int *)(p + o), o += align16(4 * (H + 1));
+  w.bsum = c.take<int>((size_t)scan_blocks(longest));
+  w.rec = c.take<mf_key>(6 * (size_t)sum_f);
+  w.pos = c.take<int>(H + 1);
   int **per_h[6] = {&w.bh, &w.bm, &w.succ, &w.lab, &w.wflag, &w.wsize};
-  for (int i = 0; i < 6; ++i) *per_h[i] = (int *)(p + o), o += align16(4 * H);
-  w.rankv = (int *)(p + o), o += align16(4 * (H + 1));
-  w.rankf = (int *)(p + o), o += align16(4 * (H + 1));
-  w.state_a = (uint2 *)(p + o), o += align16(8 * H);
-  w.state_b = (uint2 *)(p + o), o += align16(8 * H);
-  w.amax = (unsigned *)(p + o), o += align16(4 * 2 * (size_t)b);
-  w.bytes = o;
+  for (int i = 0; i < 6; ++i) *per_h[i] = c.take<int>(H);
+  w.rankv = c.take<int>(H + 1);
+  w.rankf = c.take<int>(H + 1);
+  w.state_a = c.take<uint2>(H);
+  w.state_b = c.take<uint2>(H);
+  w.amax = c.take<unsigned>(2 * (size_t)b);
+  w.bytes = c.o;
   return w;
-}
-
-void mf_fill(int *a, long long n, int value, hipStream_t s) {
-  if (n > 0) hipLaunchKernelGGL(mf_fill_kernel, dim3((unsigned)cdivll(n, MF_THREADS)), dim3(MF_THREADS), 0, s, a, n, value);
-}
-
-// exclusive scan in place of a[0 .. n), n = n_host (>= 1), or *n_dev + 1 <= n_host
-void mf_scan(int *a, long long n_host, const int *n_dev, int *bsum, hipStream_t s) {
-  const unsigned nb = (unsigned)mf_scan_blocks(n_host);
-  hipLaunchKernelGGL(mf_scan_kernel<false>, dim3(nb), dim3(MF_THREADS), 0, s, a, n_host, n_dev, bsum);
-  hipLaunchKernelGGL(mf_scan_top_kernel, dim3(1), dim3(MF_THREADS), 0, s, bsum, n_host, n_dev);
-  hipLaunchKernelGGL(mf_scan_kernel<true>, dim3(nb), dim3(MF_THREADS), 0, s, a, n_host, n_dev, bsum);
 }
 
 int mf_rounds(long long max_f) { return max_f > 0 ? align_ceil_log2(3 * max_f) + 1 : 0; }
@@ -563,17 +440,12 @@ int mf_rounds(long long max_f) { return max_f > 0 ? align_ceil_log2(3 * max_f) +
 // the checks both entry points share -> BDM_OK with the largest per-mesh counts
 int mf_check(const char *what, int b, const long long *vert_first, const long long *face_first, const void *workspace, long long &max_v,
              long long &max_f) {
-  BDM_REQUIRE(b >= 0 && b <= MF_MAX_B, "%s: batch size %d outside 0 .. %d", what, b, MF_MAX_B);
+  if (check_mesh_batch(what, b, vert_first, face_first, true, &max_v, &max_f) != BDM_OK) return BDM_ERR_ARG;
   if (b == 0) return BDM_OK;
-  BDM_REQUIRE(vert_first && face_first, "%s: an offset array is NULL", what);
-  if (check_first(what, "mesh", b, vert_first, &max_v) != BDM_OK) return BDM_ERR_ARG;
-  if (check_first(what, "mesh", b, face_first, &max_f) != BDM_OK) return BDM_ERR_ARG;
   BDM_REQUIRE(6 * face_first[b] <= INT_MAX, "%s: %lld faces: six records per face reach 2^31", what, face_first[b]);
   BDM_REQUIRE(vert_first[b] + face_first[b] < INT_MAX, "%s: %lld vertices and %lld faces: a new vertex index could reach 2^31", what,
               vert_first[b], face_first[b]);
-  BDM_REQUIRE(workspace, "%s: the workspace is NULL", what);
-  BDM_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: the workspace is not 16-byte aligned", what);
-  return BDM_OK;
+  return check_workspace(what, workspace);
 }
 
 unsigned mf_stride_grid(long long sum_f) {
@@ -589,7 +461,7 @@ extern "C" size_t bdm_mesh_fill_workspace_bytes(int b, long long sum_v, long lon
 }
 
 extern "C" int bdm_mesh_fill_variant(int b, const long long *face_first) {
-  if (b <= 0 || b > MF_MAX_B || !face_first) return 0;
+  if (b <= 0 || b > MESH_MAX_B || !face_first) return 0;
   long long max_f = 0;
   for (int m = 0; m < b; ++m) {
     const long long nf = face_first[m + 1] - face_first[m];
@@ -616,20 +488,16 @@ extern "C" int bdm_mesh_boundary_loops(int b, int max_hole_edges, const float *v
   if (check_overlap("mesh_boundary_loops", in, 2, out, 5) != BDM_OK) return BDM_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   send_offsets(b, vert_first, face_first, w.vert_first, w.face_first, st);
-  mf_fill(mesh_counts, (long long)MF_COUNTS * b, 0, st);
-  mf_fill(w.pos, H + 1, 0, st);   // a batch without faces still leaves an empty compacted list behind for bdm_mesh_fill_holes
+  fill_ints(mesh_counts, (long long)MF_COUNTS * b, 0, st);
+  fill_ints(w.pos, H + 1, 0, st);   // a batch without faces still leaves an empty compacted list behind for bdm_mesh_fill_holes
   if (max_f == 0) return launch_status("mesh_boundary_loops");
-  mf_fill(w.first, sum_v + 1, 0, st);
-  mf_fill(w.cursor, sum_v + 1, 0, st);
-  const dim3 grid_f((unsigned)cdivll(max_f, MF_THREADS), (unsigned)b), grid_h((unsigned)cdivll(3 * max_f, MF_THREADS), (unsigned)b);
+  const dim3 grid_h((unsigned)cdivll(3 * max_f, MF_THREADS), (unsigned)b);
   const dim3 block(MF_THREADS);
-  hipLaunchKernelGGL(mf_corner_kernel<false>, grid_f, block, 0, st, faces, w.vert_first, w.face_first, w.first, w.cursor, w.rec);
-  mf_scan(w.first, sum_v + 1, nullptr, w.bsum, st);
-  hipLaunchKernelGGL(mf_corner_kernel<true>, grid_f, block, 0, st, faces, w.vert_first, w.face_first, w.first, w.cursor, w.rec);
+  build_incidence<MfKeys>(b, sum_v, max_f, faces, w.vert_first, w.face_first, w.first, w.cursor, w.bsum, w.rec, st);
   if (sum_v > 0) hipLaunchKernelGGL(mf_sort_kernel, dim3((unsigned)cdivll(sum_v, MF_THREADS)), block, 0, st, sum_v, w.first, w.rec);
   hipLaunchKernelGGL(mf_classify_kernel, grid_h, block, 0, st, faces, w.vert_first, w.face_first, H, w.first, w.rec, w.pos, halfedge_loop,
                      loop_size, loop_flags);
-  mf_scan(w.pos, H + 1, nullptr, w.bsum, st);
+  exclusive_scan_ints(w.pos, H + 1, nullptr, w.bsum, st);
   hipLaunchKernelGGL(mf_compact_kernel, grid_h, block, 0, st, w.face_first, w.pos, w.bh, w.bm);
   const int *nb = w.pos + H;   // the length of the compacted list, on the device
   const dim3 grid_c(mf_stride_grid(sum_f));
@@ -646,8 +514,8 @@ extern "C" int bdm_mesh_boundary_loops(int b, int max_hole_edges, const float *v
   hipLaunchKernelGGL(mf_decide_kernel, grid_c, block, 0, st, max_hole_edges, nb, w.bh, w.bm, w.lab, loop_size, loop_flags, w.wflag, w.wsize,
                      w.rankv, mesh_counts);
   hipLaunchKernelGGL(mf_face_flag_kernel, grid_c, block, 0, st, nb, w.bm, w.lab, w.wflag, w.rankf, mesh_counts);
-  mf_scan(w.rankv, H + 1, nb, w.bsum, st);
-  mf_scan(w.rankf, H + 1, nb, w.bsum, st);
+  exclusive_scan_ints(w.rankv, H + 1, nb, w.bsum, st);
+  exclusive_scan_ints(w.rankf, H + 1, nb, w.bsum, st);
   return launch_status("mesh_boundary_loops");
 }
 
@@ -688,7 +556,7 @@ extern "C" int bdm_mesh_fill_holes(int b, int c, const float *verts, const float
   hipLaunchKernelGGL(mf_copy_kernel, dim3((unsigned)cdivll(3 * max_f, MF_THREADS), (unsigned)b), block, 0, st, 3, (const unsigned *)faces,
                      w.face_first, w.out_face_first, (unsigned *)faces_out);
   if (out_v == sum_v || max_v == 0) return launch_status("mesh_fill_holes");   // nothing is filled
-  mf_fill((int *)w.amax, 2 * (long long)b, 0, st);
+  fill_ints((int *)w.amax, 2 * (long long)b, 0, st);
   hipLaunchKernelGGL(mf_amax_kernel, dim3((unsigned)cdivll(max_v, MF_THREADS), (unsigned)b), block, 0, st, c, verts, attrs, w.vert_first, w.amax);
   const int *nb = w.pos + H;
   const dim3 grid_c(mf_stride_grid(sum_f));

@@ -1,7 +1,8 @@
 // ragged.h -- what the operators on packed, ragged batches share on the host side (mesh_render.hip, mesh_metrics.hip, knn.hip,
-// mesh_clean.hip, mesh_fill.hip): the checks on the host "first row" offset arrays, their upload, the overlap checks of the
-// pointer arguments, the workspace paddings, and the workgroup scan two of them use.  The limits on batch sizes and sums differ per
-// operator and stay at the call sites.
+// face_point.hip, align.hip, and through mesh_incidence.h mesh_clean.hip and mesh_fill.hip): the checks on
+// the host "first row" offset arrays, their upload, the overlap checks of the pointer arguments, the workspace paddings and the
+// carver that lays a workspace out, and the workgroup scan of mesh_metrics.hip and mesh_incidence.h.  The limits on batch sizes and
+// sums differ per operator and stay at the call sites.
 #pragma once
 #include "common.h"
 
@@ -32,6 +33,20 @@ int check_overlap(const char *what, const Range *in, int n_in, const Range *out,
 static inline size_t align16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
 // the two offset arrays of a batch of b, side by side, padded to 16 bytes
 static inline size_t offsets_bytes(int b) { return align16(2 * sizeof(long long) * (size_t)(b + 1)); }
+// Hands out the pieces of a workspace one after the other, each padded to 16 bytes; o is the size so far.  p may be NULL when only
+// the size is wanted (the pointers are then not to be used).
+struct Carve {
+  char *p;
+  size_t o;
+  template <class T>
+  T *take(size_t count) {
+    T *piece = (T *)(p + o);
+    o += align16(sizeof(T) * count);
+    return piece;
+  }
+  // the two offset arrays of a batch of b (offsets_bytes): the second one starts b + 1 entries after the first
+  long long *take_offsets(int b) { return take<long long>(2 * (size_t)(b + 1)); }
+};
 
 #if defined(__HIPCC__)
 // inclusive scan of one value per thread over a workgroup of THREADS (Hillis-Steele in LDS) -> this thread's prefix; buf: THREADS

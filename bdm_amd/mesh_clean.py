@@ -25,14 +25,12 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .mesh_fill import INFO_KEYS as FILL_KEYS   # what a clean_fn that fills holes adds to the info of a mesh (mesh_fill imports nothing of this module)
 from .ragged import mesh_lists, pack_meshes
 
 MAX_B, MAX_ITER = 65535, 10000   # limits of bdm_hip.h section 16
 WEIGHTS = {"inverse_length": 0, "uniform": 1}
 ROUNDS_PER_CALL = 8   # label rounds between two reads of the `changed` flag
-# what a clean_fn that fills holes adds to the info of a mesh (mesh_fill.INFO_KEYS; that module imports this one's neighbours, not this one)
-FILL_KEYS = ("boundary_edges", "loops", "filled_loops", "too_large_loops", "pinched_loops", "nonfinite_loops", "blocked_edges", "new_vertices",
-             "new_faces")
 
 
 def _check_sizes(verts_list, faces_list):

@@ -217,6 +217,37 @@ def nonfinite_meshes():
     return {"nan_on_rim": (v, faces, 32), "inf_off_rim": (w, faces, 32)}
 
 
+def fan(valence, seed):
+    """A closed fan: hub 0 and a rim of `valence` vertices, the rim its one boundary loop.  The hub has 2 * valence records."""
+    rim = torch.arange(1, valence + 1)
+    return _coords(valence + 1, seed), torch.stack([torch.zeros_like(rim), rim, rim.roll(-1)], 1)
+
+
+def fan_meshes():
+    """name -> (verts, faces, max_hole_edges): hubs of 32 records (the longest segment the kernel sorts by insertion), of 34 (the
+    shortest it heap-sorts) and of 140.  At a cap of 64 the rims of the first two are filled and the third is too large."""
+    return {f"fan_{n}": (*fan(n, 40 + n), 64) for n in (16, 17, 70)}
+
+
+def separate_triangles(n, unused, seed):
+    """n triangles without a common vertex under a shuffled numbering, and `unused` vertices that no face names."""
+    perm = torch.randperm(3 * n + unused, generator=torch.Generator().manual_seed(seed))
+    return _coords(3 * n + unused, seed + 1), perm[torch.arange(3 * n).view(n, 3)]
+
+
+def separate_triangles_filled(faces, V):
+    """What fill() gives on separate_triangles at any cap >= 3, in closed form, for sizes at which its loop over the half-edges is
+    too slow: triangle f is one loop of the half-edges 3f, 3f + 1, 3f + 2, labelled 3f and filled; its new vertex is V + f and its
+    new faces, in half-edge order, are (v_{k+1}, v_k, V + f).  -> the integer entries of fill()'s dict; the new vertex rows are
+    fixed_mean over the three vertices of the triangle (tests/test_mesh_fill_host.py holds this against fill())."""
+    faces = torch.as_tensor(faces).long().reshape(-1, 3)
+    n = faces.shape[0]
+    label = 3 * torch.arange(n)
+    new_f = torch.stack([faces[:, [1, 2, 0]], faces, (V + torch.arange(n))[:, None].expand(n, 3)], dim=2).reshape(3 * n, 3)
+    return {"faces": torch.cat([faces, new_f]), "halfedge_loop": label[:, None].expand(n, 3).contiguous(), "labels": label.tolist(),
+            "loop_sizes": torch.full((n,), 3), "loop_flags": torch.full((n,), FILLED), "info": dict(zip(INFO_KEYS, (3 * n, n, n, 0, 0, 0, 0, n, 3 * n)))}
+
+
 @functools.lru_cache(maxsize=None)
 def surface_mesh(name):
     """The surface_ref meshes of the issue's second table -> (verts, faces)."""
@@ -249,6 +280,7 @@ def batch():
     """Every mesh of the tables as one ragged batch: a tuple of (name, verts, faces, max_hole_edges); the surface meshes at cap 64."""
     rows = [(k, *v) for k, v in {**hand_meshes(), **nonfinite_meshes()}.items()]
     rows += [(k, *surface_mesh(k), 64) for k in SURFACE_MESHES]
+    rows += [(k, *v) for k, v in fan_meshes().items()]
     return tuple(rows)
 
 

@@ -260,6 +260,18 @@ def test_33_meshes_cross_the_launch_boundary_of_the_offsets_upload(hip):
         _assert_floats(_taubin(p, first, nbr, 1, mode), want, f"33 meshes, mode {mode}")
 
 
+def test_scan_of_more_than_256_partial_sums_carries_into_its_second_trip(hip):
+    """The scan's middle launch is one workgroup of 256 threads that walks the partial sums (one per 1024 entries) 256 at a time and
+    carries the total along.  87 400 separate triangles and 10 unused vertices are 262 210 vertices: the sum V + 1 = 262 211 entries of
+    both scans of bdm_mesh_adjacency (the entry count comes from the host) have 257 partial sums, one more than a trip takes."""
+    v, f = R.separate_triangles(87400, 10, 50)
+    p = Packed([(v, f)])
+    assert -(-(p.sum_v + 1) // 1024) == 257
+    first, nbr = _adjacency(p)
+    _assert_adjacency(p, first, nbr, [dict(zip(("first", "nbr"), R.adjacency(f, v.shape[0])))], "262 210 vertices")
+    assert int(first[-1]) == 6 * 87400
+
+
 # ---- errors ---------------------------------------------------------------------------------------------------------------------------
 def test_every_documented_limit_returns_1_and_leaves_the_outputs_untouched(hip):
     from bdm_amd import _lib as L

@@ -45,6 +45,8 @@ class Packed:
         self.b, self.sum_v, self.sum_f, self.C = len(meshes), sum(self.nv), sum(self.nf), C
         self.verts = torch.cat([v for v, _, _ in meshes] + [torch.zeros(1, 3)]).float().cuda().contiguous()   # one unread row: never NULL
         self.attrs = torch.cat([a for _, _, a in meshes] + [torch.zeros(1, C)]).float().cuda().contiguous()
+        if C == 0:
+            self.attrs = torch.zeros(1, device="cuda")   # no channel: one unread word, never NULL
         self.faces = torch.cat([f for _, f, _ in meshes] + [torch.zeros(1, 3, dtype=torch.int64)]).int().cuda().contiguous()
         self.vert_first = torch.tensor([0] + self.nv, dtype=torch.int64).cumsum(0)
         self.face_first = torch.tensor([0] + self.nf, dtype=torch.int64).cumsum(0)
@@ -192,6 +194,31 @@ def test_33_meshes_cross_the_launch_boundary_of_the_offsets_upload(hip):
     assert p.b == 33
     for m, (g_, mesh) in enumerate(zip(_split(p, _run(p, 32)), meshes)):
         _assert_mesh(g_, R.fill(mesh[0], mesh[1], 32, attrs=mesh[2]), 1, f"mesh {m} of 33")
+
+
+def test_scans_of_more_than_256_partial_sums_carry_with_a_host_and_a_device_count(hip):
+    """87 400 separate triangles (and 10 unused vertices) have H = 262 200 half-edges, all on the boundary: the scan of the H + 1 flags
+    (count from the host) and the scans of rankv and rankf over the compacted list (its length H read from the device) each have 257
+    partial sums, one more than the middle launch takes per trip.  No attribute channel.  Expected values: R.separate_triangles_filled,
+    held against R.fill at 64 triangles by tests/test_mesh_fill_host.py; the new vertices, on a sample of the loops, by R.fixed_mean."""
+    n = 87400
+    v, f = R.separate_triangles(n, 10, 50)
+    V = v.shape[0]
+    p = Packed([(v, f, torch.zeros(V, 0))], 0)
+    assert -(-(3 * n + 1) // 1024) == 257
+    g = _split(p, _run(p, 32))[0]
+    want = R.separate_triangles_filled(f, V)
+    assert g["counts"] == list(want["info"].values()) == [3 * n, n, n, 0, 0, 0, 0, n, 3 * n]
+    assert torch.equal(g["loop"].long(), want["halfedge_loop"].flatten()), "labels"
+    slots = torch.zeros(3 * n, dtype=torch.int64)
+    slots[want["labels"]] = 1
+    assert torch.equal(g["size"].long(), 3 * slots) and torch.equal(g["flags"].long(), R.FILLED * slots), "loop sizes or flags"
+    assert torch.equal(g["faces"].long(), want["faces"]), "faces"
+    assert g["verts"].shape == (V + n, 3) and R.same_floats(g["verts"][:V], v), "old vertices"
+    e, vn = R.scale_exp(v.numpy()), v.numpy()
+    for loop in sorted({0, 1, n // 2, n - 1, *range(0, n, 997)}):
+        mean = torch.tensor([float(R.fixed_mean(vn[f[loop].tolist(), d], e)) for d in range(3)])
+        assert R.same_floats(g["verts"][V + loop], mean), f"the new vertex of loop {loop}"
 
 
 def test_every_documented_limit_returns_1_and_leaves_the_outputs_untouched(hip):

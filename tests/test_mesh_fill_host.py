@@ -87,6 +87,30 @@ def test_attributes_ride_along_and_a_non_finite_channel_gives_nan():
             assert int(MF._round_uint8(torch.tensor([float(fm)]))) == R.uint8_mean(col), col
 
 
+def test_fans_put_hub_segments_on_both_sides_of_the_sort_threshold():
+    """A vertex has two records per connected face around it; the kernel sorts up to 32 by insertion and more by heap sort."""
+    want = {"fan_16": (32, R.FILLED), "fan_17": (34, R.FILLED), "fan_70": (140, R.TOO_LARGE)}
+    for name, (v, f, cap) in R.fan_meshes().items():
+        records = 2 * torch.bincount(f.flatten(), minlength=v.shape[0])
+        assert cap == 64 and int(records[0]) == want[name][0] and int(records[1:].max()) == 4, name
+        r = R.fill(v, f, cap)
+        assert r["labels"] == [1] and r["loop_sizes"].tolist() == [f.shape[0]] and r["loop_flags"].tolist() == [want[name][1]], name
+        filled = want[name][1] == R.FILLED
+        assert r["faces"].shape[0] == f.shape[0] * (2 if filled else 1) and r["verts"].shape[0] == v.shape[0] + filled, name
+        assert R.fill(v, f, 3)["loop_flags"].tolist() == [R.TOO_LARGE] and R.fill(v, f, 3)["info"]["new_faces"] == 0, name
+
+
+def test_closed_form_of_separate_triangles_is_what_fill_gives():
+    """tests/test_hip_mesh_fill.py uses the closed form at a size where fill()'s loop over the half-edges takes seconds."""
+    v, f = R.separate_triangles(64, 10, 77)
+    r, c = R.fill(v, f, 32), R.separate_triangles_filled(f, v.shape[0])
+    assert v.shape[0] == 202 and sorted(c) == ["faces", "halfedge_loop", "info", "labels", "loop_flags", "loop_sizes"]
+    assert all(torch.equal(r[k], c[k]) for k in ("faces", "halfedge_loop", "loop_sizes", "loop_flags")) and r["labels"] == c["labels"] and r["info"] == c["info"]
+    e = R.scale_exp(v.numpy())
+    means = np.stack([[R.fixed_mean(v.numpy()[tri, d], e) for d in range(3)] for tri in f.tolist()])
+    assert R.same_floats(r["verts"][:202], v) and R.same_floats(r["verts"][202:], torch.from_numpy(means))
+
+
 # ---- the post-conditions on meshes of the mesher ----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name, loops, filled", [("sphere600", 48, 44), ("torus1500", 1, 1), ("lattice32", 1, 0)])
 def test_post_conditions_on_surface_meshes(name, loops, filled):

@@ -1,5 +1,6 @@
 """bdm_amd/ragged.py without a GPU: the first-row arrays, the int32 rule for face indices, and the refusal of host tensors before
-anything is allocated."""
+anything is allocated; and the sizes of the mesh workspaces that csrc/ragged.h's carver lays out, asked of the library (DESIGN.md
+section 17.1)."""
 import pytest
 import torch
 
@@ -39,3 +40,31 @@ def test_packers_refuse_host_tensors_before_allocating(monkeypatch):
         ragged.pack_rows(verts, 3, "cuda")
     with pytest.raises(BdmHipError, match="CPU tensor"):
         ragged.pack_rows([verts[0][:0]], 3, "cuda")   # an empty side is no excuse
+
+
+# (b, sum V, sum F): zero sums, b of 1, 33 and 65535, sums either side of multiples of 1024 (the scan's partial sums), the largest
+# accepted sums, and from (-1, 10, 10) on sizes that an operator refuses
+WORKSPACE_ROWS = [(0, 0, 0), (1, 0, 0), (1, 1, 0), (1, 0, 1), (1, 3, 1), (1, 1022, 340), (1, 1023, 341), (1, 1024, 342), (1, 1025, 2047), (1, 2047, 2048),
+                  (1, 2048, 2049), (33, 0, 0), (33, 4914, 6576), (33, 262210, 87400), (65535, 0, 0), (65535, 65535, 65535), (65535, 1048575, 2097151),
+                  (65535, 1048576, 2097152), (1, 2 ** 31 - 2, 0), (1, 0, 357913941), (3, 1789569705, 357913941), (3, 1789569706, 357913941),
+                  (-1, 10, 10), (65536, 10, 10), (1, -1, 1), (1, 1, -1), (1, 2 ** 31 - 1, 0), (1, 2 ** 31, 1), (1, 10, 357913942)]
+# The values the library returned before the workspaces were laid out by ragged.h's carver (commit 2a90d23 built and asked): the
+# layouts are part of no interface, but a layout that moved would show here first.  components and taubin take (b, sum V) only.
+WORKSPACE_BYTES = {
+    "adjacency": [64, 80, 80, 112, 112, 16400, 16432, 16480, 57408, 65584, 65648, 592, 197728, 4196880, 1048624, 3145968, 59772912, 59772976,
+                  17188257824, 8589934672, 22913482832, 22913482832, 0, 0, 0, 0, 0, 0, 0],
+    "components": [48, 64, 96, 64, 96, 12336, 12336, 12352, 12384, 24624, 24640, 576, 59568, 3148128, 1048608, 1835264, 13635584, 13635616,
+                   25778192416, 64, 21481827072, 21481827072, 0, 0, 0, 96, 0, 0, 192],
+    "taubin": [16, 32, 64, 32, 128, 32736, 32768, 32800, 32832, 65536, 65568, 544, 157792, 8391264, 1048576, 3145696, 34602976, 34603008,
+               68719476704, 32, 57266230624, 57266230656, 0, 0, 0, 64, 0, 0, 352],
+    "fill": [128, 176, 176, 384, 384, 77696, 77904, 78160, 426048, 434336, 434576, 1456, 1382320, 19929744, 2621536, 16515760, 438853552,
+             438853728, 17188257920, 73018638432, 87337992352, 0, 0, 0, 0, 0, 0, 0, 0],
+}
+
+
+@pytest.mark.parametrize("name", list(WORKSPACE_BYTES))
+def test_mesh_workspace_sizes_are_what_they_were(name):
+    from bdm_amd import _lib as L
+    fn = getattr(L.lib(), f"bdm_mesh_{name}_workspace_bytes")
+    nargs = 3 if name in ("adjacency", "fill") else 2
+    assert [fn(*row[:nargs]) for row in WORKSPACE_ROWS] == WORKSPACE_BYTES[name]
