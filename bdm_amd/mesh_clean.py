@@ -6,12 +6,16 @@ behaviour ("parity unpinned", as for the normals).
 
     python -m bdm_amd.mesh_clean --mesh_dir D/pred_mesh --out_dir D/pred_mesh_clean [--min-fraction 0.1] [--min-faces 1]
                                  [--keep-largest] [--taubin-iters 10] [--lambd 0.53] [--mu -0.34] [--weights inverse_length]
-                                 [--batch-size 16] [--fill-holes 0]
+                                 [--batch-size 16] [--fill-holes 0] [--decimate-resolution 0]
 
 walks the mesh .ply files of mesh_dir in sorted order, removes the small components of every mesh, smooths what is left, writes it
 under out_dir at the same relative path (vertex colours are carried along) and prints one JSON line.  --fill-holes N > 0 closes the
 boundary loops of at most N edges between the two steps (bdm_amd.mesh_fill.fill_holes: islands, then holes, then smoothing) and adds
 the summed fill counts to the JSON line; 0, the default, leaves files and JSON as they are without the option.
+--decimate-resolution R > 0 thins every mesh by vertex clustering at R cells along its largest extent
+(bdm_amd.mesh_decimate.simplify_vertex_clustering, contraction "average") after islands and holes and before the smoothing, which
+relaxes the clustered triangles, and adds its counts to the JSON line as decimate_<count> (sums; the maximum for largest_cluster); 0,
+the default, leaves files and JSON as they are without the option.
 
 Departures from pytorch3d: a vertex without neighbours keeps its position (pytorch3d forms 0 / 0), `weights="uniform"` is an
 extension, no gradients."""
@@ -26,6 +30,7 @@ import torch
 from . import _lib as L
 from . import ops
 from .mesh_fill import INFO_KEYS as FILL_KEYS   # what a clean_fn that fills holes adds to the info of a mesh (mesh_fill imports nothing of this module)
+from .mesh_decimate import INFO_KEYS as DECIMATE_KEYS   # likewise for one that decimates, under "decimate_" + key
 from .ragged import mesh_lists, pack_meshes
 
 MAX_B, MAX_ITER = 65535, 10000   # limits of bdm_hip.h section 16
@@ -226,7 +231,7 @@ def process_tree(mesh_dir, out_dir, clean_fn, batch_size=16):
     if batch_size < 1:
         raise ValueError("batch_size must be positive")
     items = [(path.relative_to(mesh_dir), path) for path in sorted(mesh_dir.rglob("*.ply"))]
-    sums, fill_sums = [0] * 7, {}
+    sums, fill_sums, decimate_sums = [0] * 7, {}, {}
     for lo in range(0, len(items), batch_size):
         chunk = items[lo:lo + batch_size]
         loaded = [load_mesh_ply(path, with_colors=True) for _, path in chunk]
@@ -239,15 +244,20 @@ def process_tree(mesh_dir, out_dir, clean_fn, batch_size=16):
             for k in FILL_KEYS:
                 if k in i:   # clean_fn filled holes as well
                     fill_sums[k] = fill_sums.get(k, 0) + int(i[k])
+            for k in DECIMATE_KEYS:
+                if "decimate_" + k in i:   # clean_fn decimated as well
+                    combine = max if k == "largest_cluster" else int.__add__
+                    decimate_sums["decimate_" + k] = combine(decimate_sums.get("decimate_" + k, 0), int(i["decimate_" + k]))
     result = compose_result(*sums)
     result.update(fill_sums)
+    result.update(decimate_sums)
     return result
 
 
 def clean_batch(verts_list, faces_list, colors_list, device, min_fraction=0.1, min_faces=1, keep_largest=False, taubin_iters=10, lambd=0.53,
-                mu=-0.34, weights="inverse_length", fill_holes=0):
-    """process_tree's clean_fn on the HIP path: islands first, then (fill_holes > 0) the holes of at most fill_holes edges, smoothing
-    last (taubin_iters == 0 skips it)."""
+                mu=-0.34, weights="inverse_length", fill_holes=0, decimate_resolution=0):
+    """process_tree's clean_fn on the HIP path: islands first, then (fill_holes > 0) the holes of at most fill_holes edges, then
+    (decimate_resolution > 0) vertex clustering at that resolution, smoothing last (taubin_iters == 0 skips it)."""
     verts, faces = [v.to(device) for v in verts_list], [f.to(device) for f in faces_list]
     V = [v.shape[0] for v in verts]
     # files without colours ride along with a zero-width colour tensor, so that one call compacts all of them
@@ -265,6 +275,15 @@ def clean_batch(verts_list, faces_list, colors_list, device, min_fraction=0.1, m
         else:
             verts, faces, cols, fill_info = mesh_fill.fill_holes((verts, faces), int(fill_holes), colors_list=cols, return_info=True)
         info = [{**i, **fi} for i, fi in zip(info, fill_info)]
+    if decimate_resolution:
+        from . import mesh_decimate
+        widths = {c.shape[1] for c in cols}
+        width = max(widths, default=0)
+        padded = [c if c.shape[1] == width else c.new_zeros(c.shape[0], width) for c in cols] if len(widths) > 1 else cols
+        verts, faces, thinned, dec_info = mesh_decimate.simplify_vertex_clustering((verts, faces), resolution=int(decimate_resolution),
+                                                                                   colors_list=padded, return_info=True)
+        cols = [t if c.shape[1] == width else t[:, :0] for t, c in zip(thinned, cols)]
+        info = [{**i, **{"decimate_" + k: v for k, v in di.items()}} for i, di in zip(info, dec_info)]
     if taubin_iters:
         verts = taubin_smoothing((verts, faces), lambd, mu, taubin_iters, weights=weights).verts_list()
     return ([v.cpu() for v in verts], [f.cpu() for f in faces], [None if c0 is None else c.cpu() for c, c0 in zip(cols, colors_list)], info)
@@ -285,9 +304,14 @@ def parse_args(argv):
     ap.add_argument("--batch-size", type=int, default=16)
     ap.add_argument("--fill-holes", type=int, default=0, metavar="N",
                     help="after the islands, close the boundary loops of at most N edges (bdm_amd.mesh_fill); 0 = off")
+    ap.add_argument("--decimate-resolution", type=int, default=0, metavar="R",
+                    help="after islands and holes, thin the mesh by vertex clustering at R cells along its largest extent "
+                         "(bdm_amd.mesh_decimate); 0 = off")
     args = ap.parse_args(argv)
     if args.batch_size < 1:
         ap.error("--batch-size must be positive")
+    if not 0 <= args.decimate_resolution <= 1024:
+        ap.error("--decimate-resolution must be 0 (off) or lie in 1..1024")
     if args.fill_holes != 0 and not 3 <= args.fill_holes <= 65535:
         ap.error("--fill-holes must be 0 (off) or lie in 3..65535")
     try:
@@ -306,7 +330,7 @@ def main(argv=None):
 
     def clean_fn(verts_list, faces_list, colors_list):
         return clean_batch(verts_list, faces_list, colors_list, device, args.min_fraction, args.min_faces, args.keep_largest, args.taubin_iters,
-                           args.lambd, args.mu, args.weights, args.fill_holes)
+                           args.lambd, args.mu, args.weights, args.fill_holes, args.decimate_resolution)
 
     result = process_tree(args.mesh_dir, args.out_dir, clean_fn, args.batch_size)
     print(json.dumps(result))

@@ -1508,6 +1508,70 @@ int bdm_mesh_fill_holes(int b, int c, const float *verts, const float *attrs, co
                         const long long *face_first, const long long *out_vert_first, const long long *out_face_first, float *verts_out,
                         float *attrs_out, int *faces_out, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * 20. Decimation by vertex clustering (csrc/mesh_decimate.hip): Open3D's simplify_vertex_clustering by name and meaning.  The rule
+ *     is this project's own text.  DESIGN.md section 24.
+ * ---------------------------------------------------------------------------------- */
+/* Meshes: verts, faces, vert_first, face_first exactly as bdm_mesh_adjacency takes them; "connected face" as in sections 16 and 19:
+ *   three indices in range and pairwise different.  Everything below is per mesh, indices within the mesh.
+ * 1. Bounds: a vertex is finite when its three coordinates are finite.  lo[a], hi[a] = the minimum and maximum of coordinate a over
+ *    the finite vertices, compared as floats (the sign of a zero does not matter below).
+ * 2. Cell size h (float32): the caller gives one positive finite voxel_size per mesh, or one resolution R, 1 <= R <= 1024.  With R,
+ *    h = max_a(hi[a] - lo[a]) / float32(R): float32 subtractions, a maximum, one correctly rounded float32 division, computed on the
+ *    device (nothing is read back for it); if that h is zero or not finite (a mesh without finite vertices included), h = 1.
+ * 3. Cell of a finite vertex: k_a = min(int(floorf((c_a - lo[a]) / h)), 2^21 - 1), float32 subtraction and correctly rounded float32
+ *    division, no contraction; a quotient that is not below 2^21 (an infinite one included) gives 2^21 - 1.  The key is
+ *    kx | ky << 21 | kz << 42.  The grid is anchored at lo: not at the origin, and not half a cell below lo as Open3D's is.
+ * 4. Clusters: finite vertices with equal keys form one cluster; a non-finite vertex is a cluster of its own.  A cluster's leader is
+ *    its smallest member index.  The new vertices are the clusters in ascending leader; vert_map[v] = the new index of v's cluster.
+ * 5. Position: a cluster of one member copies that member's row bit for bit (a non-finite row too).  A larger cluster: contraction 1
+ *    ("first") copies the leader's row bit for bit; contraction 0 ("average") takes section 19 rule 5's fixed-point mean over the
+ *    members: E from the mesh's largest finite |coordinate|, e = 39 - E, q(c) = rint(c 2^e), S = the 64-bit integer sum,
+ *    float32((float64(S) 2^-e) / float64(size)).  A mesh has fewer than 2^21 vertices and |q| < 2^40, so |S| < 2^61; section 19's
+ *    bound on the mean holds unchanged.
+ * 6. Attributes: attrs (sum V, c) float32 rows, c <= 16, ride along as in section 19 rule 6: copied for a cluster of one and for the
+ *    leader under "first"; under "average" the same mean per channel, its scale from the mesh's largest finite |attribute|, and NaN for
+ *    a channel with a non-finite member.  (The float32 mean of up to 65 535 uint8 values, rounded to nearest even and clamped, equals
+ *    the correctly rounded integer mean: DESIGN.md section 23.  Larger clusters are averaged all the same, without that guarantee.)
+ * 7. Faces, in this order: a face that is not connected is dropped, face_map = -3.  A connected face (a, b, c) becomes (vert_map[a],
+ *    vert_map[b], vert_map[c]); if two of those are equal it has collapsed and is dropped, face_map = -1.  Among the remaining faces with
+ *    the same vertex SET (orientation ignored) the one of the lowest old index is kept, the others are duplicates, face_map = -2.  Kept
+ *    faces follow each other in ascending old index and keep their corner order; face_map[i] = the new index of a kept face.
+ * 8. mesh_counts (b, 8) int32, exact: new_vertices, new_faces, collapsed_faces, duplicate_faces, bad_faces, nonfinite_vertices,
+ *    largest_cluster, merged_vertices (the members of clusters of more than one).
+ * Not promised: clustering can leave non-manifold edges and change the genus; nothing repairs that.
+ *
+ * bdm_mesh_cluster writes vert_map (sum V), face_map (sum F) and mesh_counts and leaves its plan (leaders, ranks, the members of every
+ *   cluster, the kept faces) in the workspace.  voxel_size: b float32 in HOST memory, or NULL; with NULL `resolution` counts, with
+ *   voxel sizes resolution must be 0.  contraction: 0 average, 1 first (the plan does not depend on it).
+ * bdm_mesh_decimate, after a bdm_mesh_cluster call with the same b, verts, faces, offsets and workspace (untouched in between), writes
+ *   verts_out (sum V', 3), attrs_out (sum V', c), faces_out (sum F', 3), packed by out_vert_first and out_face_first (b + 1 int64 in
+ *   HOST memory), which the caller forms from mesh_counts: V' = new_vertices, F' = new_faces.  That read of mesh_counts is the only
+ *   synchronisation.  Offsets that cannot be a decimated mesh (V' > V, V' = 0 with V > 0, F' > F, F' > 0 with V' < 3) are refused; a
+ *   row that the given sizes do not hold is never written.
+ *
+ * Limits: 0 <= b <= 65535, every mesh fewer than 2^21 vertices, sum V < 2^31, 3 sum F < 2^31, offsets non-decreasing from 0,
+ *   0 <= c <= 16, no NULL pointer other than voxel_size (with c == 0 attrs and attrs_out still point somewhere; they are not read or
+ *   written), the workspace 16-byte aligned, no output and no part of the workspace overlapping an input or another output (judged
+ *   on byte ranges).  b == 0 returns 0 and launches nothing; anything else outside the limits returns 1, launches nothing and leaves
+ *   the outputs untouched.  bdm_mesh_decimate_workspace_bytes returns 0 outside the limits.
+ * workspace: bdm_mesh_decimate_workspace_bytes(b, sum_v, sum_f) bytes, contents irrelevant before bdm_mesh_cluster: the offsets, per
+ *   mesh bounds, maxima and h, one open-addressing table of 2 max(sum V, sum F) + b slots (12 bytes each; mesh m owns 2 V_m + 1 of
+ *   them for its cells and afterwards 2 F_m + 1 for its face sets), six ints per vertex and two per face.
+ * Determinism: integer atomics only (slot claims by 64-bit compare-and-swap, minima for leaders and kept faces, counts, cursors,
+ *   per-workgroup minima / maxima of order-preserving float bits), no floating-point atomics, no workgroup waits on another, every
+ *   probe loop is bounded by its region's size, every grid by host counts.  Where a key lands in the table depends on arrival order
+ *   and nothing but key -> minimum leaves it; the order of a cluster's member segment depends on it too and only integer sums read it.
+ *   Mesh j of a batch has the bits of that mesh alone, and so has a repeated call.  One thread averages one cluster: a very large
+ *   cluster is slow, never wrong. */
+size_t bdm_mesh_decimate_workspace_bytes(int b, long long sum_v, long long sum_f);
+int bdm_mesh_cluster(int b, int resolution, const float *voxel_size, int contraction, const float *verts, const int *faces,
+                     const long long *vert_first, const long long *face_first, int *vert_map, int *face_map, int *mesh_counts,
+                     void *workspace, void *stream);
+int bdm_mesh_decimate(int b, int resolution, const float *voxel_size, int contraction, int c, const float *verts, const float *attrs,
+                      const int *faces, const long long *vert_first, const long long *face_first, const long long *out_vert_first,
+                      const long long *out_face_first, float *verts_out, float *attrs_out, int *faces_out, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
