@@ -195,3 +195,61 @@ def save_image_png(image_chw, path):
     arr = (arr * 255.0).astype(np.uint8).transpose(1, 2, 0)  # truncation, as Tensor.byte() does
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     Image.fromarray(arr[:, :, 0] if arr.shape[2] == 1 else arr).save(path)
+
+
+def save_binvox(voxels, path, translate=(0.0, 0.0, 0.0), scale=1.0):
+    """A (D, D, D) occupancy grid indexed [x][y][z] as a binvox file (the ShapeNetVox32 form): the header lines `#binvox 1`, `dim D D D`,
+    `translate tx ty tz`, `scale s`, `data`, then (value, count) byte pairs over the linear index x D^2 + z D + y, a run of more than
+    255 cells split.  The centre of cell i lies at translate + (i + 0.5) scale / D."""
+    vox = np.asarray(voxels).astype(bool)
+    if vox.ndim != 3 or len(set(vox.shape)) != 1 or vox.shape[0] < 1:
+        raise ValueError(f"a binvox grid is cubic, got shape {vox.shape}")
+    D = vox.shape[0]
+    flat = np.ascontiguousarray(vox.transpose(0, 2, 1)).reshape(-1).astype(np.uint8)
+    cuts = np.flatnonzero(np.diff(flat)) + 1                      # where the value changes
+    starts, ends = np.concatenate([[0], cuts]), np.concatenate([cuts, [flat.size]])
+    pieces = -(-(ends - starts) // 255)                           # runs of at most 255
+    value = np.repeat(flat[starts], pieces)
+    count = np.full(value.size, 255, dtype=np.int64)
+    last = np.cumsum(pieces) - 1
+    count[last] = (ends - starts) - 255 * (pieces - 1)
+    t = [float(x) for x in np.asarray(translate, dtype=np.float64).reshape(3)]
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as out:
+        out.write(f"#binvox 1\ndim {D} {D} {D}\ntranslate {t[0]!r} {t[1]!r} {t[2]!r}\nscale {float(scale)!r}\ndata\n".encode("ascii"))
+        out.write(np.stack([value, count.astype(np.uint8)], axis=1).tobytes())
+
+
+def load_binvox(path):
+    """(voxels bool (D, D, D) indexed [x][y][z], translate (3,) float64, scale float) from a binvox file in save_binvox's form.  A grid
+    that is not cubic, a header that is not the five lines in that order, an odd number of data bytes, a value other than 0 / 1, a
+    zero count or runs that do not add up to D^3 cells raise ValueError."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    lines, at = [], 0
+    for _ in range(5):
+        end = raw.find(b"\n", at)
+        if end < 0:
+            raise ValueError(f"{path}: the binvox header ends early")
+        lines.append(raw[at:end].decode("ascii", "replace").strip())
+        at = end + 1
+    try:
+        if lines[0].split() != ["#binvox", "1"] or lines[4] != "data":
+            raise ValueError("not `#binvox 1` ... `data`")
+        dim, tr, sc = lines[1].split(), lines[2].split(), lines[3].split()
+        if dim[0] != "dim" or tr[0] != "translate" or sc[0] != "scale" or len(dim) != 4 or len(tr) != 4 or len(sc) != 2:
+            raise ValueError("expected dim, translate and scale")
+        dims, translate, scale = [int(x) for x in dim[1:]], np.array([float(x) for x in tr[1:]], dtype=np.float64), float(sc[1])
+    except (ValueError, IndexError) as e:
+        raise ValueError(f"{path}: malformed binvox header: {e}") from None
+    if len(set(dims)) != 1 or dims[0] < 1:
+        raise ValueError(f"{path}: only cubic grids are read, got dim {dims}")
+    D = dims[0]
+    body = np.frombuffer(raw, dtype=np.uint8, offset=at)
+    if body.size % 2:
+        raise ValueError(f"{path}: an odd number of data bytes")
+    value, count = body[0::2], body[1::2].astype(np.int64)
+    if (value > 1).any() or (count == 0).any() or int(count.sum()) != D ** 3:
+        raise ValueError(f"{path}: the runs do not describe {D}^3 cells of 0 / 1")
+    vox = np.repeat(value.astype(bool), count).reshape(D, D, D).transpose(0, 2, 1)   # stored [x][z][y]
+    return np.ascontiguousarray(vox), translate, scale

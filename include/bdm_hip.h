@@ -1572,6 +1572,50 @@ int bdm_mesh_decimate(int b, int resolution, const float *voxel_size, int contra
                       const int *faces, const long long *vert_first, const long long *face_first, const long long *out_vert_first,
                       const long long *out_face_first, float *verts_out, float *attrs_out, int *faces_out, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * 21. Solid voxelisation (csrc/mesh_voxel.hip): the occupancy grid of a packed batch of triangle meshes by parity counting along
+ *     grid-aligned rays.  The rule is this project's own text, restated by tests/mesh_voxel_ref.py.  DESIGN.md section 25.
+ * ---------------------------------------------------------------------------------- */
+/* Meshes: verts, faces, vert_first, face_first exactly as bdm_mesh_adjacency takes them.  Everything below is per mesh.
+ * 1. Grid: R = resolution cells per axis, origin o = origin[3 m .. 3 m + 2], cell size h = cell[m] (float32; HOST arrays).  In snapped
+ *    coordinates (256 per cell, as section 13's 256 per pixel) the centre of cell i along an axis sits at 256 i + 128.
+ * 2. Snapping: q_a = rintf(((v_a - o_a) / h) * 256) in float32, operation by operation: no contraction, the division correctly
+ *    rounded, ties to even.  A vertex is usable when its three coordinates are finite and every |q_a| <= 2^19 (compared as floats).
+ * 3. Faces: a face with an index out of range, a repeated index or an unusable vertex is DROPPED and counted; every other is USED.
+ * 4. The perturbed point: every predicate is evaluated at the cell centre moved by (eps, eps^2, eps^3) in (x, y, z), eps positive
+ *    and infinitesimal; the ties of the three rays then describe one and the same point, which is never on the surface.  In integers:
+ *    Ray along axis w, (u, v) = the two other axes in increasing order: (y, z), (x, z), (x, y).  A = the doubled area of the face
+ *    projected to (u, v); A == 0: the face contributes nothing along w; A < 0: two corners are swapped.  The column centre is covered
+ *    when each of the three int64 edge functions is > 0, or == 0 on an edge whose vector (du, dv) has dv < 0 || (dv == 0 && du > 0).
+ *    (Not section 13's rule, whose image y points down.)  With n = (b - a) x (c - a) and g(k) = n . (p_k - a), p_k the centre of cell k
+ *    of the column, cell k lies BELOW the face when sign~(g(k)) sign(n_w) < 0; sign~(g) = sign(g), or for g == 0 the sign of the first
+ *    non-zero of (n_x, n_y, n_z).  Below is monotone in k; with c cells below, the face flips the parity of cells 0 .. c - 1.
+ * 5. A cell is inside along an axis when its flips are odd.  mode 0 ("vote"): occupied when at least two axes say inside; mode 1, 2,
+ *    3: the x, y, z axis alone.  A closed mesh gives the same grid along all three axes; an open one does not, and the vote repairs
+ *    the cells that one ray alone gets wrong, not a hole that two rays see.
+ * 6. Integers: |q| <= 2^19 and R <= 512 keep every difference within 2^20, edge functions and normal components within 2^41 and g
+ *    within 3 * 2^61: int64 holds them exactly.
+ *
+ * bdm_mesh_voxelize writes occupancy (b, R, R, R) uint8, 0 / 1, indexed [m][ix][iy][iz]; axes (the same shape, or NULL): bit 0, 1, 2 =
+ *   inside along x, y, z; counts (b, 8) int32, exact: faces used, faces dropped, cells inside along x, y, z, cells occupied (by mode),
+ *   cells on which the three axes are not all equal ("disagree"), 0.
+ *
+ * Limits: 0 <= b <= 65535, 1 <= R <= 512, b R^3 < 2^31, sum V < 2^31, 3 sum F < 2^31, offsets non-decreasing from 0, mode 0 .. 3, every
+ *   cell size positive and finite, every origin finite, no NULL pointer other than axes, the workspace 16-byte aligned, no output and
+ *   no part of the workspace overlapping an input or another output (judged on byte ranges).  b == 0 returns 0 and launches nothing;
+ *   anything else outside the limits returns 1, launches nothing and leaves the outputs untouched.
+ *   bdm_mesh_voxelize_workspace_bytes returns 0 outside the limits.
+ * workspace: bdm_mesh_voxelize_workspace_bytes(b, sum_v, sum_f, R) bytes, contents irrelevant before the call: the offsets, the frames,
+ *   16 bytes per vertex and ceil(R / 32) 32-bit words per column, axis and mesh (3 b R^2 columns).
+ * Determinism: integer atomics only (XOR of one bit per face and covered column, adds for the counts), no floating-point atomics, no
+ *   workgroup waits on another, every loop is bounded by R, by a box or by a launch argument.  The offsets and the frames travel as
+ *   launch arguments: nothing is copied or synchronised, and the call is safe under stream capture.  Mesh j of a batch has the bits of
+ *   that mesh alone, and so has a repeated call. */
+size_t bdm_mesh_voxelize_workspace_bytes(int b, long long sum_v, long long sum_f, int resolution);
+int bdm_mesh_voxelize(int b, int resolution, int mode, const float *origin, const float *cell, const float *verts, const int *faces,
+                      const long long *vert_first, const long long *face_first, unsigned char *occupancy, unsigned char *axes, int *counts,
+                      void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
