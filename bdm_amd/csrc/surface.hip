@@ -14,41 +14,15 @@
 // Count, scan and write are separate launches; nothing waits on another workgroup, every loop is bounded by a launch argument.
 // Sums are integers, so the order of the atomics cannot change a bit.
 //
+// The workspace layout, the frame (surf_launch_frame) and the mark stage (surf_launch_mark: surf_cell_kernel ... surf_rank_kernel) are
+// shared with bdm_surface_poisson_grid (surface_poisson.hip) through surface_stage.h.
+//
 // The file is compiled with -ffp-contract=off and correctly rounded division (Makefile): the arithmetic defines integers.
 #include "common.h"
 #include "bdm_hip.h"
+#include "surface_stage.h"
 
 namespace bdm {
-
-constexpr int SRF_THREADS = 256;             // workgroup of the per-node kernels: one count per workgroup
-constexpr int SRF_WAVES = SRF_THREADS / 64;
-constexpr int SRF_WIDE = 1024;               // workgroup of the per-cloud kernels (box, scan)
-constexpr int SRF_PAR = 8;                   // words per cloud: cx, cy, cz, inv, live, 3 unused
-constexpr int SRF_N_MAX = 65536, SRF_R_MIN = 16, SRF_R_MAX = 256, SRF_S_MIN = 2, SRF_S_MAX = 4;
-constexpr unsigned SRF_GRID_Y = 32768;       // clouds beyond it are reached by the stride loop over blockIdx.y
-
-struct SurfWs {
-  int *sw, *su, *cell;      // [b][r3] each
-  int *cell_bc, *edge_bc;   // [b][nb], [b][3][nb]: counts per workgroup, then their exclusive scan
-  float *par;               // [b][SRF_PAR]
-  unsigned char *eflag;     // [b][3][r3]
-  int r3, nb;
-};
-
-static inline size_t surf_ws_ints(int b, int r3, int nb) { return (size_t)b * (3 * (size_t)r3 + 4 * (size_t)nb + SRF_PAR); }
-
-static inline SurfWs surf_ws(void *ws, int b, int r) {
-  SurfWs w;
-  w.r3 = r * r * r, w.nb = cdiv(w.r3, SRF_THREADS);
-  w.sw = (int *)ws;
-  w.su = w.sw + (size_t)b * w.r3;
-  w.cell = w.su + (size_t)b * w.r3;
-  w.cell_bc = w.cell + (size_t)b * w.r3;
-  w.edge_bc = w.cell_bc + (size_t)b * w.nb;
-  w.par = (float *)(w.edge_bc + (size_t)b * 3 * w.nb);
-  w.eflag = (unsigned char *)(w.par + (size_t)b * SRF_PAR);
-  return w;
-}
 
 // rank of a set flag among the set flags of the workgroup (ascending thread index) and their number; all threads call it
 __device__ __forceinline__ int surf_block_rank(bool flag, int &total, int *waves) {
@@ -336,17 +310,32 @@ __global__ __launch_bounds__(SRF_THREADS) void surf_face_kernel(int b, int r, in
   }
 }
 
-static bool surf_sizes_ok(int b, int n, int r, int s) {
+bool surf_sizes_ok(int b, int n, int r, int s) {
   return b >= 0 && n >= 1 && n <= SRF_N_MAX && r >= SRF_R_MIN && r <= SRF_R_MAX && s >= SRF_S_MIN && s <= SRF_S_MAX &&
          (long long)b * r * r * r < (1ll << 31);
 }
 
-static int surf_check_sizes(const char *what, int b, int n, int r, int s) {
+int surf_check_sizes(const char *what, int b, int n, int r, int s) {
   BDM_REQUIRE(b >= 0 && n >= 1 && n <= SRF_N_MAX, "%s: bad sizes b=%d n=%d (n in 1..%d)", what, b, n, SRF_N_MAX);
   BDM_REQUIRE(r >= SRF_R_MIN && r <= SRF_R_MAX, "%s: r=%d outside %d..%d", what, r, SRF_R_MIN, SRF_R_MAX);
   BDM_REQUIRE(s >= SRF_S_MIN && s <= SRF_S_MAX, "%s: s=%d outside %d..%d", what, s, SRF_S_MIN, SRF_S_MAX);
   BDM_REQUIRE((long long)b * r * r * r < (1ll << 31), "%s: b r^3 = %lld exceeds int", what, (long long)b * r * r * r);
   return BDM_OK;
+}
+
+void surf_launch_frame(int b, int n, int r, int margin, const float *points, const float *normals, const SurfWs &w, int *counts,
+                       hipStream_t st) {
+  // the kernel's frame leaves s + 1 voxels free on every side: margin = s + 1 is section 12's, a wider one is asked for as a larger s
+  hipLaunchKernelGGL(surf_box_kernel, dim3((unsigned)b), dim3(SRF_WIDE), 0, st, n, r, margin - 1, points, normals, w.par, counts);
+}
+
+void surf_launch_mark(int b, int r, int thr, const SurfWs &w, int *counts, hipStream_t st) {
+  const unsigned gy = (unsigned)b < SRF_GRID_Y ? (unsigned)b : SRF_GRID_Y;
+  hipLaunchKernelGGL(surf_cell_kernel, dim3((unsigned)w.nb, gy), dim3(SRF_THREADS), 0, st, b, r, thr, w.nb, w.sw, w.su, w.cell, w.cell_bc);
+  hipLaunchKernelGGL(surf_edge_kernel, dim3((unsigned)(3 * w.nb), gy), dim3(SRF_THREADS), 0, st, b, r, thr, w.nb, w.sw, w.su, w.cell,
+                     w.eflag, w.edge_bc, counts);
+  hipLaunchKernelGGL(surf_scan_kernel, dim3((unsigned)b), dim3(SRF_WIDE), 0, st, w.nb, w.cell_bc, w.edge_bc, counts);
+  hipLaunchKernelGGL(surf_rank_kernel, dim3((unsigned)w.nb, gy), dim3(SRF_THREADS), 0, st, b, r, w.nb, w.cell_bc, w.cell);
 }
 
 }  // namespace bdm
@@ -355,8 +344,7 @@ using namespace bdm;
 
 extern "C" size_t bdm_surface_workspace_bytes(int b, int n, int r, int s) {
   if (!surf_sizes_ok(b, n, r, s)) return 0;
-  const int r3 = r * r * r;
-  return surf_ws_ints(b, r3, cdiv(r3, SRF_THREADS)) * sizeof(int) + 3 * (size_t)b * r3;
+  return surf_ws_bytes(b, r);
 }
 
 extern "C" int bdm_surface_grid(int b, int n, int r, int s, float min_weight, const float *points, const float *normals, int *counts,
@@ -372,15 +360,11 @@ extern "C" int bdm_surface_grid(int b, int n, int r, int s, float min_weight, co
   const int weight = (int)rintf(min_weight * 4096.0f), thr = weight > 1 ? weight : 1;
   hipStream_t st = (hipStream_t)stream;
   const unsigned gy = (unsigned)b < SRF_GRID_Y ? (unsigned)b : SRF_GRID_Y;
-  hipLaunchKernelGGL(surf_box_kernel, dim3((unsigned)b), dim3(SRF_WIDE), 0, st, n, r, s, points, normals, w.par, counts);
+  surf_launch_frame(b, n, r, s + 1, points, normals, w, counts, st);
   if (hipMemsetAsync(w.sw, 0, 2 * (size_t)b * w.r3 * sizeof(int), st) != hipSuccess) return launch_status("surface_grid (memset)");
   hipLaunchKernelGGL(surf_scatter_kernel, dim3((unsigned)cdiv(n * 4 * s * s, SRF_THREADS), gy), dim3(SRF_THREADS), 0, st, b, n, r, s,
                      points, normals, w.par, w.sw, w.su);
-  hipLaunchKernelGGL(surf_cell_kernel, dim3((unsigned)w.nb, gy), dim3(SRF_THREADS), 0, st, b, r, thr, w.nb, w.sw, w.su, w.cell, w.cell_bc);
-  hipLaunchKernelGGL(surf_edge_kernel, dim3((unsigned)(3 * w.nb), gy), dim3(SRF_THREADS), 0, st, b, r, thr, w.nb, w.sw, w.su, w.cell,
-                     w.eflag, w.edge_bc, counts);
-  hipLaunchKernelGGL(surf_scan_kernel, dim3((unsigned)b), dim3(SRF_WIDE), 0, st, w.nb, w.cell_bc, w.edge_bc, counts);
-  hipLaunchKernelGGL(surf_rank_kernel, dim3((unsigned)w.nb, gy), dim3(SRF_THREADS), 0, st, b, r, w.nb, w.cell_bc, w.cell);
+  surf_launch_mark(b, r, thr, w, counts, st);
   return launch_status("surface_grid");
 }
 

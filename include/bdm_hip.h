@@ -1616,6 +1616,78 @@ int bdm_mesh_voxelize(int b, int resolution, int mode, const float *origin, cons
                       const long long *vert_first, const long long *face_first, unsigned char *occupancy, unsigned char *axes, int *counts,
                       void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * 22. Closed triangle meshes from oriented clouds (csrc/surface_poisson.hip): Poisson surface reconstruction (Kazhdan et al. 2006) on
+ *     the uniform grid of section 12.  The normals are splatted into a vector field V, Laplace(phi) = div V is solved by a fixed
+ *     schedule of multigrid V-cycles, and the level set of phi through its mean at the samples is handed to the surface nets of
+ *     section 12.  phi is defined on every node, so no quad is skipped and every edge of the mesh has an even number of faces.
+ *     The rule is this project's own text, restated by tests/surface_poisson_ref.py.  DESIGN.md section 26.
+ * ---------------------------------------------------------------------------------- */
+/* points, normals, r, s, the node order and the float32 convention (every operation rounded on its own, in the order written, no
+ * contraction, division correctly rounded, rint to even) are section 12's.
+ * 1. Frame: steps 1 and 2 of section 12 with a margin of s + 3 voxels: inv = float(r - 1 - 2 (s + 3)) / (2 * half).  The same validity
+ *    test, the same empty-cloud rule, counts[3] = the number of valid points.  The SAMPLES are the valid points whose q lies in [0, r - 1]^3.
+ * 2. Splat: for every sample and every node g = floor(q) + o, o in {-s + 1, ..., s}^3, inside the grid: d, d2, t, w, w3 as in step 3 of
+ *    section 12 (no contribution if t <= 0); W = rint(w3 * 4096); V_a = rint((w3 * n_a) * 4096) clamped to [-4096, 4096] (a normal
+ *    longer than 1 counts as 1 per component), 0 if the product is NaN, a = x, y, z.  W, Vx, Vy, Vz are exact int32 sums per node: a
+ *    sample reaches a node at most once, so n <= 65536 keeps every |sum| <= 65536 * 4096 = 2^28.
+ * 3. Right-hand side: D(g) = Vx(g + ex) - Vx(g - ex) + Vy(g + ey) - Vy(g - ey) + Vz(g + ez) - Vz(g - ez), zero outside the grid, an exact
+ *    int32 (|D| <= 6 * 2^28 < 2^31), converted to float32 once (to nearest even).
+ * 4. Solve: levels l = 0, 1, ... of side m_0 = r, m_{l+1} = m_l / 2, halved while m_l is even and above 4 (16 -> 8 -> 4, 24 -> 12 -> 6 -> 3,
+ *    40 -> 20 -> 10 -> 5, 56 -> 28 -> 14 -> 7).  Accepted r: the multiples of 8 in 16 .. 256 whose coarsest side is at most 8, that is
+ *    16, 24, 32, 40, 48, 56, 64, 80, 96, 112, 128, 160, 192, 224, 256.  h2_l = 4^l.  On every level the unknowns sit at the cell
+ *    centres and phi = 0 holds on the outer cell faces: a neighbour outside the level is minus the node's own value.
+ *    lap(phi)(g) = (((xm + xp) + (ym + yp)) + (zm + zp)) - 6 * phi(g), xm, xp the neighbours at g -+ ex and so on.
+ *    sweep:    phi'(g) = phi(g) + ((lap(phi)(g) - h2_l * f(g)) * c7), c7 = the float32 nearest 1 / 7 (damped Jacobi, omega = 6 / 7),
+ *              every node from the old phi.
+ *    residual: res(g) = f(g) - lap(phi)(g) * (1 / h2_l).
+ *    restrict: f_{l+1}(G) = (the sum of res over the children 2 G + (a, b, c), started from (0, 0, 0) and added in lexicographic
+ *              order of (a, b, c)) * 0.125.
+ *    prolong:  along z, then y, then x: child 2 K + a takes 0.75 * e(K) + 0.25 * e(K - 1 + 2 a); a coarse index outside the level
+ *              is clamped and the value negated, once per axis that is outside.  phi_l(g) += that value.
+ *    V-cycle on level l: if l is the coarsest: phi_l = 0, then 32 sweeps.  Otherwise (phi_l = 0 first when l > 0; level 0 continues from
+ *    the cycle before, and from 0 in the first) 2 sweeps, restrict the residual, the V-cycle on level l + 1, prolong, 2 sweeps.
+ *    phi = level 0 after `cycles` V-cycles.  The schedule depends on (r, cycles) alone: no stopping test, nothing read back.
+ * 5. Level: M = max |phi| over the nodes (exact: the bits of |phi| order as integers).  If M == 0 or there is no sample: iso = scale = 0.
+ *    Otherwise scale = 2^22 / M, qs = scale * 256.  Per sample: base = min(floor(q), r - 2) per axis, t = q - float(base),
+ *    lerp(a, b, t) = a + t * (b - a); the 8 nodes around it are reduced along z, then y, then x to v; I = rint(v * qs) (|I| <= 2^30 + 1).
+ *    iso = (float(sum of I, an exact int64) / float(number of samples)) / qs.
+ * 6. Hand-over: if scale == 0: SW = SU = 0 everywhere (no vertex, no face).  Otherwise SW = 4096 and
+ *    SU = rint((phi - iso) * scale) clamped to [-2^23, 2^23] on every node; then a node of the outermost layer (a coordinate 0 or
+ *    r - 1) with SU < 1 gets SU = 1 and is counted in border_raised.  Then two separation passes: in a pass, judged on the grid before it,
+ *    a negative node becomes 1 when it lies on a grid face (four nodes g, g + eu, g + ev, g + eu + ev in one coordinate plane, all inside
+ *    the grid) on which it and the node across the face are negative and the two others are not.  Surface nets would put four faces on
+ *    the mesh edge between the two cells on either side of such a face; a pass can in principle leave new such faces next to the raised
+ *    nodes, which is what the second pass is for (none was seen after the first).  Steps 5 and 6 of section 12 follow with thr = 1, unchanged:
+ *    negative is inside, triangle normals point to the non-negative side.  Every sign-change edge has its negative end off the border,
+ *    so it is a candidate and its four cells hold both signs: skipped == 0 and every mesh edge has an even number of faces.
+ * 7. Density: per vertex, (the int32 sum of W over the 8 corners of its cell, as float32) * (1 / 32768).
+ *
+ * bdm_surface_poisson_grid runs steps 1 - 6 up to and including the mark stage of bdm_surface_grid; counts as in section 12;
+ *   info (b, 3) int32 = {border_raised, the bits of iso, the bits of scale}.  bdm_surface_extract then runs on the same workspace as it
+ *   is.  The workspace holds the section-12 layout at its start (bdm_surface_workspace_bytes(b, n, r, s) bytes) and behind it, each
+ *   (b, r, r, r): W, Vx, Vy, Vz int32, D float32, phi float32; then the accumulators and the coarser levels.
+ * bdm_surface_poisson_density, after the grid call with the same b, r and workspace: density[vert_offsets[c] + v] for every vertex v
+ *   of cloud c (the offsets as bdm_surface_extract takes them); nothing else is written.
+ * Limits: those of section 12 for b, n, r, s; r accepted (step 4); 1 <= cycles <= 32; no NULL pointer; no output or the workspace equal
+ *   to an input or to another output.  b == 0 launches nothing and returns 0; outside the limits a call returns 1, launches nothing
+ *   and leaves the outputs untouched.  bdm_surface_poisson_workspace_bytes returns 0 outside the limits.
+ * Determinism: integer atomics only (sums of the splat, the 64-bit sum of the samples, the maximum of the bits, border_raised), no
+ *   floating-point atomic or reduction, no workgroup waits on another, every loop is bounded by a launch argument, safe under stream
+ *   capture.  Every cycle overwrites what it reads of the workspace: its contents before the call are irrelevant.  Cloud j of a batch
+ *   has the same bits as the same cloud run alone, and so does a repeated call. */
+size_t bdm_surface_poisson_workspace_bytes(int b, int n, int r, int s);
+int bdm_surface_poisson_grid(int b, int n, int r, int s, int cycles, const float *points, const float *normals, int *counts, int *info,
+                             void *workspace, void *stream);
+int bdm_surface_poisson_density(int b, int r, const long long *vert_offsets, float *density, void *workspace, void *stream);
+/* For tools/surface_poisson_bench.py: the launches of bdm_surface_poisson_grid in parts.  stages: bit 0 = frame, memset, splat and
+ * divergence; bit 1 = the solve, which continues from the phi in the workspace (the memset of bit 0 zeroes it); bit 2 = level, hand-over
+ * and mark.  per_level = 1 runs every level of the solve in global memory, one launch per level and operator and one per sweep of the
+ * coarsest level, in place of the LDS tail: the same arithmetic, so the same bits.  stages = 7, per_level = 0 is
+ * bdm_surface_poisson_grid.  The limits are the same; stages outside 1 .. 7 or per_level outside 0 .. 1 return 1. */
+int bdm_surface_poisson_grid_staged(int b, int n, int r, int s, int cycles, int stages, int per_level, const float *points,
+                                    const float *normals, int *counts, int *info, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
