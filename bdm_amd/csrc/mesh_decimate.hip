@@ -29,6 +29,7 @@
 #include "../../include/bdm_hip.h"
 #include "common.h"
 #include "mesh_incidence.h"
+#include "mesh_mean.h"
 #include "align_solve.h"   // align_pow2
 
 #include <limits.h>
@@ -329,14 +330,9 @@ __global__ __launch_bounds__(MD_THREADS) void md_face_map_kernel(const long long
 }
 
 // ---- output ---------------------------------------------------------------------------------------------------------------------------
-// the exponent e of the fixed point (mesh_fill.hip's): every finite |value| <= amax quantises to rint(value 2^e) below 2^40 in magnitude
-__device__ __forceinline__ int md_scale_exp(unsigned amax_bits) {
-  const int field = (int)((amax_bits >> 23) & 0xffu);
-  return 39 - ((field < 1 ? 1 : field) - 127);
-}
-
-// S 2^-e / n in float64, rounded once to float32
-__device__ __forceinline__ float md_mean(long long s, double inv, double n) { return (float)(((double)s * inv) / n); }
+// the fixed point of the means (mesh_mean.h; mesh_fill.hip's rule)
+__device__ __forceinline__ int md_scale_exp(unsigned amax_bits) { return mean_scale_exp(amax_bits); }
+__device__ __forceinline__ float md_mean(long long s, double inv, double n) { return mean_of_sum(s, inv, n); }
 
 // one thread per vertex; the leader of a cluster writes the cluster's row (never one the caller's sizes do not hold)
 __global__ __launch_bounds__(MD_THREADS) void md_vertex_out_kernel(int c, int average, const float *__restrict__ verts,

@@ -6,7 +6,7 @@ behaviour ("parity unpinned", as for the normals).
 
     python -m bdm_amd.mesh_clean --mesh_dir D/pred_mesh --out_dir D/pred_mesh_clean [--min-fraction 0.1] [--min-faces 1]
                                  [--keep-largest] [--taubin-iters 10] [--lambd 0.53] [--mu -0.34] [--weights inverse_length]
-                                 [--batch-size 16] [--fill-holes 0] [--decimate-resolution 0]
+                                 [--batch-size 16] [--fill-holes 0] [--decimate-resolution 0 | --decimate-fraction 0]
 
 walks the mesh .ply files of mesh_dir in sorted order, removes the small components of every mesh, smooths what is left, writes it
 under out_dir at the same relative path (vertex colours are carried along) and prints one JSON line.  --fill-holes N > 0 closes the
@@ -15,7 +15,10 @@ the summed fill counts to the JSON line; 0, the default, leaves files and JSON a
 --decimate-resolution R > 0 thins every mesh by vertex clustering at R cells along its largest extent
 (bdm_amd.mesh_decimate.simplify_vertex_clustering, contraction "average") after islands and holes and before the smoothing, which
 relaxes the clustered triangles, and adds its counts to the JSON line as decimate_<count> (sums; the maximum for largest_cluster); 0,
-the default, leaves files and JSON as they are without the option.
+the default, leaves files and JSON as they are without the option.  --decimate-fraction f in (0, 1] thins in the same place by
+quadric edge collapses down to the share f of every mesh's faces instead (bdm_amd.mesh_decimate.simplify_quadric_decimation, which
+keeps a closed mesh closed) and adds decimate_rounds (the maximum), decimate_collapses and decimate_locked_vertices (sums); the two
+options exclude each other.
 
 Departures from pytorch3d: a vertex without neighbours keeps its position (pytorch3d forms 0 / 0), `weights="uniform"` is an
 extension, no gradients."""
@@ -31,6 +34,7 @@ from . import _lib as L
 from . import ops
 from .mesh_fill import INFO_KEYS as FILL_KEYS   # what a clean_fn that fills holes adds to the info of a mesh (mesh_fill imports nothing of this module)
 from .mesh_decimate import INFO_KEYS as DECIMATE_KEYS   # likewise for one that decimates, under "decimate_" + key
+QEM_KEYS = ("rounds", "collapses", "locked_vertices")   # and for one that decimates by quadrics (sums; the maximum for rounds)
 from .ragged import mesh_lists, pack_meshes
 
 MAX_B, MAX_ITER = 65535, 10000   # limits of bdm_hip.h section 16
@@ -244,9 +248,9 @@ def process_tree(mesh_dir, out_dir, clean_fn, batch_size=16):
             for k in FILL_KEYS:
                 if k in i:   # clean_fn filled holes as well
                     fill_sums[k] = fill_sums.get(k, 0) + int(i[k])
-            for k in DECIMATE_KEYS:
+            for k in DECIMATE_KEYS + QEM_KEYS:
                 if "decimate_" + k in i:   # clean_fn decimated as well
-                    combine = max if k == "largest_cluster" else int.__add__
+                    combine = max if k in ("largest_cluster", "rounds") else int.__add__
                     decimate_sums["decimate_" + k] = combine(decimate_sums.get("decimate_" + k, 0), int(i["decimate_" + k]))
     result = compose_result(*sums)
     result.update(fill_sums)
@@ -255,9 +259,10 @@ def process_tree(mesh_dir, out_dir, clean_fn, batch_size=16):
 
 
 def clean_batch(verts_list, faces_list, colors_list, device, min_fraction=0.1, min_faces=1, keep_largest=False, taubin_iters=10, lambd=0.53,
-                mu=-0.34, weights="inverse_length", fill_holes=0, decimate_resolution=0):
+                mu=-0.34, weights="inverse_length", fill_holes=0, decimate_resolution=0, decimate_fraction=0.0):
     """process_tree's clean_fn on the HIP path: islands first, then (fill_holes > 0) the holes of at most fill_holes edges, then
-    (decimate_resolution > 0) vertex clustering at that resolution, smoothing last (taubin_iters == 0 skips it)."""
+    (decimate_resolution > 0) vertex clustering at that resolution or (decimate_fraction > 0; not both) quadric edge collapses down to
+    that share of the faces, smoothing last (taubin_iters == 0 skips it)."""
     verts, faces = [v.to(device) for v in verts_list], [f.to(device) for f in faces_list]
     V = [v.shape[0] for v in verts]
     # files without colours ride along with a zero-width colour tensor, so that one call compacts all of them
@@ -284,6 +289,17 @@ def clean_batch(verts_list, faces_list, colors_list, device, min_fraction=0.1, m
                                                                                    colors_list=padded, return_info=True)
         cols = [t if c.shape[1] == width else t[:, :0] for t, c in zip(thinned, cols)]
         info = [{**i, **{"decimate_" + k: v for k, v in di.items()}} for i, di in zip(info, dec_info)]
+    if decimate_fraction:
+        from . import mesh_decimate
+        if decimate_resolution:
+            raise ValueError("decimate_resolution and decimate_fraction exclude each other")
+        widths = {c.shape[1] for c in cols}
+        width = max(widths, default=0)
+        padded = [c if c.shape[1] == width else c.new_zeros(c.shape[0], width) for c in cols] if len(widths) > 1 else cols
+        verts, faces, thinned, dec_info = mesh_decimate.simplify_quadric_decimation((verts, faces), target_fraction=float(decimate_fraction),
+                                                                                    colors_list=padded, return_info=True)
+        cols = [t if c.shape[1] == width else t[:, :0] for t, c in zip(thinned, cols)]
+        info = [{**i, **{"decimate_" + k: di[k] for k in QEM_KEYS}} for i, di in zip(info, dec_info)]
     if taubin_iters:
         verts = taubin_smoothing((verts, faces), lambd, mu, taubin_iters, weights=weights).verts_list()
     return ([v.cpu() for v in verts], [f.cpu() for f in faces], [None if c0 is None else c.cpu() for c, c0 in zip(cols, colors_list)], info)
@@ -307,11 +323,18 @@ def parse_args(argv):
     ap.add_argument("--decimate-resolution", type=int, default=0, metavar="R",
                     help="after islands and holes, thin the mesh by vertex clustering at R cells along its largest extent "
                          "(bdm_amd.mesh_decimate); 0 = off")
+    ap.add_argument("--decimate-fraction", type=float, default=0.0, metavar="f",
+                    help="in the same place, thin the mesh by quadric edge collapses down to the share f of its faces, which keeps a closed "
+                         "mesh closed (bdm_amd.mesh_decimate.simplify_quadric_decimation); 0 = off; not together with --decimate-resolution")
     args = ap.parse_args(argv)
     if args.batch_size < 1:
         ap.error("--batch-size must be positive")
     if not 0 <= args.decimate_resolution <= 1024:
         ap.error("--decimate-resolution must be 0 (off) or lie in 1..1024")
+    if not 0.0 <= args.decimate_fraction <= 1.0:
+        ap.error("--decimate-fraction must be 0 (off) or lie in (0, 1]")
+    if args.decimate_fraction and args.decimate_resolution:
+        ap.error("--decimate-fraction and --decimate-resolution exclude each other")
     if args.fill_holes != 0 and not 3 <= args.fill_holes <= 65535:
         ap.error("--fill-holes must be 0 (off) or lie in 3..65535")
     try:
@@ -330,7 +353,7 @@ def main(argv=None):
 
     def clean_fn(verts_list, faces_list, colors_list):
         return clean_batch(verts_list, faces_list, colors_list, device, args.min_fraction, args.min_faces, args.keep_largest, args.taubin_iters,
-                           args.lambd, args.mu, args.weights, args.fill_holes, args.decimate_resolution)
+                           args.lambd, args.mu, args.weights, args.fill_holes, args.decimate_resolution, args.decimate_fraction)
 
     result = process_tree(args.mesh_dir, args.out_dir, clean_fn, args.batch_size)
     print(json.dumps(result))

@@ -12,7 +12,15 @@ The vertices of a mesh that fall into one cell of a regular grid become one vert
 and of several faces over the same three new vertices the first stays.  The grid of cell size h is anchored at lo, the per-axis
 minimum of the mesh's finite vertices: not at the origin, and not half a cell below lo as Open3D's is, so the cells differ from
 Open3D's by that half cell.  Clustering can leave non-manifold edges and change the genus; surface.mesh_stats reports that and
-nothing here repairs it.  Edge-collapse decimation is not offered."""
+nothing here repairs it.
+
+    python -m bdm_amd.mesh_decimate --mesh_dir D/pred_mesh --out_dir D/pred_mesh_small --method quadric
+                                    (--target-faces N | --target-fraction f) [--max-error x] [--boundary-weight w]
+
+thins by quadric edge collapses instead (simplify_quadric_decimation, Open3D's simplify_quadric_decimation by name and meaning, over
+bdm_mesh_qem_init / _rounds / _finish, csrc/mesh_qem.hip; bdm_hip.h section 23): a closed manifold mesh stays
+closed and manifold, and the faces go where the curvature is.  Its JSON line carries the method, the sizes, the open-edge fractions,
+the rounds (the maximum over the files) and the collapses."""
 import argparse
 import json
 import sys
@@ -156,6 +164,140 @@ def simplify_vertex_clustering(meshes, voxel_size=None, resolution=None, contrac
     return (out_v, out_f) + ((out_c,) if colors_list is not None else ()) + ((info,) if return_info else ())
 
 
+# ---- quadric edge collapse (bdm_hip.h section 23) -------------------------------------------------------------------------------------
+QEM_INFO_KEYS = ("stop", "rounds", "collapses", "faces_in", "faces_out", "vertices_in", "vertices_out", "locked_vertices", "bad_faces",
+                 "max_cost_bits", "selected", "candidates", "rejected_nonmanifold", "rejected_locked", "rejected_cost", "rejected_link",
+                 "rejected_boundary", "rejected_valence", "rejected_flip", "target")
+QEM_STOPS = ("running", "target", "no_edge", "max_rounds")
+QEM_MAX_ROUNDS = 2 ** 20
+QEM_ROUNDS_PER_CALL = 8   # rounds between two reads of the number of meshes still running
+
+
+def _per_mesh(value, B, name):
+    if isinstance(value, (list, tuple)) or torch.is_tensor(value):
+        out = list(value.tolist() if torch.is_tensor(value) else value)
+        if len(out) != B:
+            raise ValueError(f"{len(out)} values of {name} for {B} meshes")
+        return out
+    return [value] * B
+
+
+def _check_targets(target_number_of_triangles, target_fraction, faces_list):
+    """Exactly one of the two, a number or one per mesh -> the per-mesh face targets (Python ints)."""
+    if (target_number_of_triangles is None) == (target_fraction is None):
+        raise ValueError("give exactly one of target_number_of_triangles and target_fraction")
+    B = len(faces_list)
+    if target_fraction is not None:
+        out = []
+        for f, faces in zip(_per_mesh(target_fraction, B, "target_fraction"), faces_list):
+            if isinstance(f, bool) or not isinstance(f, (int, float)) or not 0.0 < float(f) <= 1.0:
+                raise ValueError(f"target_fraction={f!r} is not a number in (0, 1]")
+            out.append(int(float(f) * int(faces.shape[0])))
+        return out
+    out = _per_mesh(target_number_of_triangles, B, "target_number_of_triangles")
+    for n in out:
+        if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n < 2 ** 31 - 1:
+            raise ValueError(f"target_number_of_triangles={n!r} is not an integer in 0..2^31-2")
+    return out
+
+
+def _check_qem(maximum_error, boundary_weight, max_rounds):
+    for name, x in (("maximum_error", maximum_error), ("boundary_weight", boundary_weight)):
+        if isinstance(x, bool) or not isinstance(x, (int, float)) or not float(x) >= 0.0:
+            raise ValueError(f"{name}={x!r} is not a number >= 0")
+    if float(boundary_weight) == float("inf"):
+        raise ValueError("boundary_weight must be finite")
+    if isinstance(max_rounds, bool) or not isinstance(max_rounds, int) or not 1 <= max_rounds <= QEM_MAX_ROUNDS:
+        raise ValueError(f"max_rounds={max_rounds!r} is not an integer in 1..{QEM_MAX_ROUNDS}")
+
+
+def qem_info(row):
+    """One row of mesh_counts -> the info dictionary: QEM_INFO_KEYS, and stop_reason and max_cost decoded."""
+    out = dict(zip(QEM_INFO_KEYS, (int(x) for x in row)))
+    out["stop_reason"] = QEM_STOPS[out["stop"]]
+    out["max_cost"] = float(torch.tensor(out["max_cost_bits"], dtype=torch.int32).view(torch.float32))
+    return out
+
+
+@torch.no_grad()
+def simplify_quadric_decimation(meshes, target_number_of_triangles=None, target_fraction=None, maximum_error=float("inf"), boundary_weight=1.0,
+                                colors_list=None, return_info=False, return_maps=False, max_rounds=256):
+    """Thin every mesh by quadric edge collapses -> (verts_list, faces_list[, colors_list][, info][, (vert_map_list, face_map_list)]).
+    Exactly one of target_number_of_triangles (an integer, or one per mesh) and target_fraction (in (0, 1], or one per mesh: the target
+    is int(fraction * faces)) is given.  Collapses happen in rounds: every edge that is the cheapest of its two-hop neighbourhood and
+    passes the validity checks (link condition, no flipped face, bdm_hip.h section 23) collapses at once, the vertex of the lower
+    index surviving at the quadric's optimum.  Rounds are applied whole, so the final face count lies in (target - the last round's
+    removals, target]; it is not exact.  A mesh stops when it has reached its target, when a round finds no valid edge (or none within
+    maximum_error), or after max_rounds rounds; info[m]["stop_reason"] says which.  A closed, consistently wound manifold stays one,
+    with its Euler characteristic; an open sheet keeps its boundary loops; non-manifold edges, non-finite vertices and faces with a bad
+    index are left locked in place and counted.  Surviving vertices keep their order, surviving faces their order and winding.
+    colors_list ((V_i, C) per mesh, uint8 or floating point, C <= 16) is carried along: a vertex nothing merged into keeps its row,
+    another takes the order-free fixed-point mean of the old vertices mapped to it, as simplify_vertex_clustering does.  The maps:
+    vert_map (V,) int64 old -> new index, face_map (F,) int64 the new index, -1 for a collapsed face, -3 for a bad one.  Everything is
+    bit-reproducible and a mesh's result does not depend on its batch.  Not Open3D's heap order, and no attribute-aware quadrics.
+    Bad arguments raise ValueError before any launch; host tensors are refused."""
+    verts_list, faces_list = mesh_lists(meshes)
+    targets = _check_targets(target_number_of_triangles, target_fraction, faces_list)
+    _check_qem(maximum_error, boundary_weight, max_rounds)
+    C = 0 if colors_list is None else _check_colors(colors_list, verts_list)
+    if not verts_list:
+        return ([], []) + (([],) if colors_list is not None else ()) + (([],) if return_info else ()) + ((([], []),) if return_maps else ())
+    if len(verts_list) > MAX_B:
+        raise ValueError(f"{len(verts_list)} meshes exceed {MAX_B}: split the batch")
+    nv, nf = [int(v.shape[0]) for v in verts_list], [int(f.shape[0]) for f in faces_list]
+    if sum(nv) >= 2 ** 31 - 1 or 6 * sum(nf) >= 2 ** 31 - 1:
+        raise ValueError("the batch reaches 2^31 vertices or incidence records (six per face): split it")
+    verts, faces, vert_first, face_first = pack_meshes(verts_list, faces_list)
+    B, dev, sum_v, sum_f = len(verts_list), verts.device, sum(nv), sum(nf)
+    if C:
+        for c in colors_list:
+            L.ptr(c)
+        attrs = L.f32(torch.cat([c.float() for c in colors_list] + [torch.zeros(1, C, device=dev)]))   # one unread row: never empty
+    else:
+        attrs = torch.zeros(1, 1, dtype=torch.float32, device=dev)
+    lib = L.lib()
+    ws = ops.workspace(lib.bdm_mesh_qem_workspace_bytes(B, sum_v, sum_f), dev, "mesh_qem")
+    counts = torch.zeros(B, len(QEM_INFO_KEYS), dtype=torch.int32, device=dev)
+    active = torch.zeros(1, dtype=torch.int32, device=dev)
+    want = torch.tensor(targets, dtype=torch.int64)
+    vf, ff = vert_first.data_ptr(), face_first.data_ptr()
+    L.check(lib.bdm_mesh_qem_init(B, float(boundary_weight), want.data_ptr(), L.ptr(verts), L.ptr(faces), vf, ff, L.ptr(counts), L.ptr(ws),
+                                  L.stream()), "mesh_qem_init")
+    done = 0
+    while True:
+        L.check(lib.bdm_mesh_qem_rounds(B, QEM_ROUNDS_PER_CALL, max_rounds, float(maximum_error), vf, ff, L.ptr(counts), L.ptr(active), L.ptr(ws),
+                                        L.stream()), "mesh_qem_rounds")
+        done += QEM_ROUNDS_PER_CALL
+        if int(active.item()) == 0 or done >= max_rounds + QEM_ROUNDS_PER_CALL:   # the one small read-back per call
+            break
+    rows = counts.cpu()
+    new_v, new_f = rows[:, 6].tolist(), rows[:, 4].tolist()
+    out_vert_first, out_face_first = first(new_v), first(new_f)
+    verts_out = torch.zeros(max(int(out_vert_first[-1]), 1), 3, dtype=torch.float32, device=dev)
+    attrs_out = torch.zeros(max(int(out_vert_first[-1]), 1), max(C, 1), dtype=torch.float32, device=dev)
+    faces_out = torch.zeros(max(int(out_face_first[-1]), 1), 3, dtype=torch.int32, device=dev)
+    vert_map = torch.zeros(max(sum_v, 1), dtype=torch.int32, device=dev)
+    face_map = torch.zeros(max(sum_f, 1), dtype=torch.int32, device=dev)
+    L.check(lib.bdm_mesh_qem_finish(B, C, L.ptr(attrs), vf, ff, out_vert_first.data_ptr(), out_face_first.data_ptr(), L.ptr(verts_out),
+                                    L.ptr(attrs_out), L.ptr(faces_out), L.ptr(vert_map), L.ptr(face_map), L.ptr(ws), L.stream()), "mesh_qem_finish")
+    out_v, out_f, out_c = [], [], []
+    for m in range(B):
+        v0, f0 = int(out_vert_first[m]), int(out_face_first[m])
+        out_v.append(verts_out[v0:v0 + new_v[m]])
+        out_f.append(faces_out[f0:f0 + new_f[m]].to(faces_list[m].dtype))
+        if C:
+            part = attrs_out[v0:v0 + new_v[m]]
+            out_c.append(_round_uint8(part) if colors_list[m].dtype == torch.uint8 else part.to(colors_list[m].dtype))
+        elif colors_list is not None:
+            out_c.append(colors_list[m].new_zeros(new_v[m], 0))
+    out = (out_v, out_f) + ((out_c,) if colors_list is not None else ())
+    if return_info:
+        out += ([qem_info(row) for row in rows.tolist()],)
+    if return_maps:
+        out += (([x.long() for x in vert_map[:sum_v].split(nv)], [x.long() for x in face_map[:sum_f].split(nf)]),)
+    return out
+
+
 # ---- command line ------------------------------------------------------------------------------------------------------------------
 def decimate_batch(verts_list, faces_list, colors_list, device, voxel_size=None, resolution=None, contraction="average"):
     """Host tensors of ragged sizes (a colour entry None for a file that carries none) -> (verts_list, faces_list, colors_list, info) on
@@ -168,6 +310,26 @@ def decimate_batch(verts_list, faces_list, colors_list, device, voxel_size=None,
         verts, faces, cols, info = simplify_vertex_clustering((verts, faces), voxel_size, resolution, contraction, colors_list=cols, return_info=True)
     else:
         verts, faces, info = simplify_vertex_clustering((verts, faces), voxel_size, resolution, contraction, return_info=True)
+        cols = [None] * len(verts)
+    return ([v.cpu() for v in verts], [f.cpu() for f in faces], [None if c0 is None else c.cpu() for c, c0 in zip(cols, colors_list)], info)
+
+
+QEM_CLI_KEYS = ("rounds", "collapses", "locked_vertices", "bad_faces")   # of the quadric method's JSON line: sums, rounds the maximum
+
+
+def quadric_batch(verts_list, faces_list, colors_list, device, target_faces=None, target_fraction=None, maximum_error=float("inf"),
+                  boundary_weight=1.0):
+    """decimate_batch for simplify_quadric_decimation."""
+    verts, faces = [v.to(device) for v in verts_list], [f.to(device) for f in faces_list]
+    kw = dict(target_number_of_triangles=target_faces, target_fraction=target_fraction, maximum_error=maximum_error, boundary_weight=boundary_weight,
+              return_info=True)
+    have = [c for c in colors_list if c is not None]
+    if have:
+        like = have[0]
+        cols = [like.new_zeros(v.shape[0], like.shape[1]).to(device) if c is None else c.to(device) for c, v in zip(colors_list, verts)]
+        verts, faces, cols, info = simplify_quadric_decimation((verts, faces), colors_list=cols, **kw)
+    else:
+        verts, faces, info = simplify_quadric_decimation((verts, faces), **kw)
         cols = [None] * len(verts)
     return ([v.cpu() for v in verts], [f.cpu() for f in faces], [None if c0 is None else c.cpu() for c, c0 in zip(cols, colors_list)], info)
 
@@ -191,15 +353,16 @@ def _stats(v, f):
     return mesh_stats(v, f[ok])
 
 
-def process_tree(mesh_dir, out_dir, decimate_fn, batch_size=16):
+def process_tree(mesh_dir, out_dir, decimate_fn, batch_size=16, info_keys=INFO_KEYS, max_keys=("largest_cluster",)):
     """Walk mesh_dir for mesh .ply files in sorted path order, up to batch_size files per call of decimate_fn(verts_list, faces_list,
-    colors_list) -> (verts_list, faces_list, colors_list, info; host tensors), and write out_dir/<same relative path>."""
+    colors_list) -> (verts_list, faces_list, colors_list, info; host tensors), and write out_dir/<same relative path>.  info_keys are
+    summed over the files, those in max_keys take the maximum."""
     from .io import load_mesh_ply, save_mesh_ply
     mesh_dir, out_dir = Path(mesh_dir), Path(out_dir)
     if batch_size < 1:
         raise ValueError("batch_size must be positive")
     items = [(path.relative_to(mesh_dir), path) for path in sorted(mesh_dir.rglob("*.ply"))]
-    sums, sizes, edges = {k: 0 for k in INFO_KEYS}, [0, 0, 0, 0], [0, 0, 0, 0]
+    sums, sizes, edges = {k: 0 for k in info_keys}, [0, 0, 0, 0], [0, 0, 0, 0]
     for lo in range(0, len(items), batch_size):
         chunk = items[lo:lo + batch_size]
         loaded = [load_mesh_ply(path, with_colors=True) for _, path in chunk]
@@ -212,26 +375,40 @@ def process_tree(mesh_dir, out_dir, decimate_fn, batch_size=16):
                 edges[k] += add
             for k, add in enumerate((v_in.shape[0], f_in.shape[0], v.shape[0], f.shape[0])):
                 sizes[k] += int(add)
-            for k in INFO_KEYS:
-                sums[k] = max(sums[k], int(i[k])) if k == "largest_cluster" else sums[k] + int(i[k])
+            for k in info_keys:
+                sums[k] = max(sums[k], int(i[k])) if k in max_keys else sums[k] + int(i[k])
     return compose_result(len(items), sums, *sizes, *edges)
 
 
 def parse_args(argv):
     ap = argparse.ArgumentParser(prog="python -m bdm_amd.mesh_decimate",
-                                 description="write a tree of triangle meshes again, thinned by vertex clustering")
+                                 description="write a tree of triangle meshes again, thinned by vertex clustering or by quadric edge collapses")
     ap.add_argument("--mesh_dir", required=True, help="directory tree of triangle-mesh .ply files")
     ap.add_argument("--out_dir", required=True)
-    grid = ap.add_mutually_exclusive_group(required=True)
+    ap.add_argument("--method", choices=("clustering", "quadric"), default="clustering",
+                    help="clustering: --resolution or --voxel-size; quadric (keeps a closed mesh closed): --target-faces or --target-fraction")
+    grid = ap.add_mutually_exclusive_group()
     grid.add_argument("--resolution", type=int, help=f"cells along the mesh's largest extent, 1..{MAX_R}")
     grid.add_argument("--voxel-size", type=float, help="the cell size")
+    grid.add_argument("--target-faces", type=int, help="quadric: the face count to reach, per mesh")
+    grid.add_argument("--target-fraction", type=float, help="quadric: the share of its faces a mesh keeps, in (0, 1]")
     ap.add_argument("--contraction", choices=sorted(CONTRACTIONS), default="average")
+    ap.add_argument("--max-error", type=float, default=float("inf"), help="quadric: no collapse above this quadric error")
+    ap.add_argument("--boundary-weight", type=float, default=1.0, help="quadric: the weight of the planes that hold a boundary in place")
     ap.add_argument("--batch-size", type=int, default=16)
     args = ap.parse_args(argv)
     if args.batch_size < 1:
         ap.error("--batch-size must be positive")
     try:
-        _check_grid(args.voxel_size, args.resolution, 1)
+        if args.method == "quadric":
+            if args.resolution is not None or args.voxel_size is not None:
+                ap.error("--method quadric takes --target-faces or --target-fraction, not a grid")
+            _check_targets(args.target_faces, args.target_fraction, [torch.zeros(0, 3)])
+            _check_qem(args.max_error, args.boundary_weight, 256)
+        else:
+            if args.target_faces is not None or args.target_fraction is not None:
+                ap.error("--target-faces and --target-fraction belong to --method quadric")
+            _check_grid(args.voxel_size, args.resolution, 1)
     except ValueError as e:
         ap.error(str(e))
     return args
@@ -242,8 +419,14 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise L.BdmHipError("bdm_amd.mesh_decimate needs a HIP device (no CPU fallback)")
     device = torch.device("cuda", torch.cuda.current_device())
-    result = process_tree(args.mesh_dir, args.out_dir,
-                          lambda v, f, c: decimate_batch(v, f, c, device, args.voxel_size, args.resolution, args.contraction), args.batch_size)
+    if args.method == "quadric":
+        result = process_tree(args.mesh_dir, args.out_dir,
+                              lambda v, f, c: quadric_batch(v, f, c, device, args.target_faces, args.target_fraction, args.max_error,
+                                                            args.boundary_weight), args.batch_size, QEM_CLI_KEYS, ("rounds",))
+        result = {"files": result.pop("files"), "method": "quadric", **result}
+    else:
+        result = process_tree(args.mesh_dir, args.out_dir,
+                              lambda v, f, c: decimate_batch(v, f, c, device, args.voxel_size, args.resolution, args.contraction), args.batch_size)
     print(json.dumps(result))
     return result
 

@@ -1688,6 +1688,91 @@ int bdm_surface_poisson_density(int b, int r, const long long *vert_offsets, flo
 int bdm_surface_poisson_grid_staged(int b, int n, int r, int s, int cycles, int stages, int per_level, const float *points,
                                     const float *normals, int *counts, int *info, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * 23. Decimation by quadric edge collapse in rounds (csrc/mesh_qem.hip): Open3D's simplify_quadric_decimation by name and meaning
+ *     (Garland and Heckbert 1997); a closed, consistently wound manifold stays one.  Not Open3D's heap order and not an exact face
+ *     count (Open3D is not installed: parity unpinned).  The rule is this project's own text, restated by tests/mesh_qem_ref.py,
+ *     which is the definition wherever this text is silent.  DESIGN.md section 27.
+ * ---------------------------------------------------------------------------------- */
+/* Meshes: verts, faces, vert_first, face_first exactly as bdm_mesh_adjacency takes them; "connected face" as in section 16.  Everything
+ *   below is per mesh, indices within the mesh.  Arithmetic: positions are float32 in and out; everything that decides is float64,
+ *   every operation rounded on its own in the order written (no contraction), division and square root correctly rounded.
+ *   dot(a, b) = (a0 b0 + a1 b1) + a2 b2;  cross(p0, p1, p2) = (p1 - p0) x (p2 - p0), each component u_i v_j - u_j v_i.
+ * State: a position, a live flag, a locked flag and a quadric (10 float64: a2 ab ac ad b2 bc bd c2 cd d2 of a plane (a, b, c, d)) per
+ *   vertex; three indices per face, a dead face holding -1 three times.  Indices are stable through the rounds.
+ * Init.  A face that is not connected is dead from the start (face_map -3, "bad") and locks those of its indices that are in range; a
+ *   vertex with a non-finite coordinate is locked.  Half-edge 3 f + c of live face f runs from its corner c to corner c + 1.  An
+ *   undirected edge {a, b} with `out` half-edges a -> b and `in` half-edges b -> a is INTERIOR for (1, 1), BOUNDARY for (1, 0) or
+ *   (0, 1) and IRREGULAR otherwise; its id is the lowest half-edge index over it, in either direction.
+ *   Plane term of face (p0, p1, p2): n = cross, l2 = dot(n, n); skipped unless 0 < l2 < inf; area = 0.5 sqrt(l2); d = -dot(n, p0);
+ *   the ten products (n_i n_j) s, (n_i d) s, (d d) s with s = area / l2.  Boundary term of a boundary half-edge p -> q of such a face:
+ *   e = q - p, m = e x n, ml2 = dot(m, m), skipped unless 0 < ml2 < inf; d = -dot(m, p); s = (boundary_weight area) / ml2.
+ *   The quadric of a vertex is 0 plus, for its faces in ascending index: the plane term, then the boundary term of the half-edge that
+ *   leaves the vertex in that face, then that of the one that arrives, each term added coefficient by coefficient.
+ * A round, for every edge of live faces (each is evaluated once, at its id h; lo < hi its ends), in this order:
+ *   1. refused "nonmanifold" when the edge is irregular or an irregular edge ends at lo or hi; "locked" when lo or hi is locked.
+ *   2. Q = Q_lo + Q_hi.  With A the 3 x 3 block and r = -(ad, bd, cd): c00 = b2 c2 - bc bc, c01 = ab c2 - bc ac, c02 = ab bc - b2 ac,
+ *      det = (a2 c00 - ab c01) + ac c02, tr = (a2 + b2) + c2.  If |det| > 2^-40 ((tr tr) tr) the optimum is Cramer's
+ *      m0 = r1 c2 - bc r2, m1 = r1 bc - b2 r2, m2 = ab r2 - r1 ac, x = ((r0 c00 - ab m0) + ac m1) / det, y = ((a2 m0 - r0 c01) + ac m2) / det,
+ *      z = ((r0 c02 - a2 m1) - ab m2) / det, accepted when its squared distance to the midpoint (p_lo + p_hi) 0.5 is at most |p_hi - p_lo|^2.
+ *      Otherwise the target is the cheapest of p_lo, p_hi and the midpoint, a later one only when strictly cheaper.
+ *      error(v) = ((A + 2 B) + 2 C) + d2, A = ((a2 x) x + (b2 y) y) + (c2 z) z, B = ((ab x) y + (ac x) z) + (bc y) z, C = (ad x + bd y) + cd z;
+ *      cost = error clamped: e > 0 ? e : 0 (a NaN stays), clamped before any comparison.  Refused "cost" unless cost <= maximum_error and
+ *      float32(cost) is finite.  The position stored by a collapse is the target rounded to float32; step 3 uses that rounded value.
+ *   3. Validity.  "link": lo and hi must have exactly 2 common neighbours (interior edge) or 1 (boundary edge).  "boundary": an
+ *      interior edge between two vertices that each have a boundary edge.  "valence": the third vertex of a face at the edge needs at
+ *      least 4 neighbours, or 3 if it has a boundary edge (it loses one and must keep a fan).  "flip": for every live face around lo
+ *      that does not contain hi, and around hi that does not contain lo, dot(cross with that corner at the target, cross as it is)
+ *      must be > 0 (a zero normal, before or after, refuses).  The first reason that applies is counted.
+ *   4. key = bits(float32(cost)) << 32 | h for a valid edge, 2^64 - 1 otherwise.  m1[v] = the minimum key over the edges at v;
+ *      m2[v] = the minimum of m1 over v and its neighbours; the edge is SELECTED iff key < 2^64 - 1 and key == m2[lo] == m2[hi].
+ *      Selected edges neither share nor neighbour an endpoint, so rule 5 touches disjoint vertices and faces.
+ *   5. Apply: lo takes the rounded target and Q (lo's quadric first in every sum); hi dies, vert_map chains hi -> lo; the faces
+ *      around hi that contain lo die (face_map -1), the others get lo in hi's corner.
+ * Stopping, per mesh, at a round boundary, first match: live faces <= target ("target", 1; tested before the first round too); the
+ *   round selected nothing ("no_edge", 2); the number of rounds reached max_rounds ("max_rounds", 3).  Rounds are applied whole: the
+ *   final face count lies in (target - the last round's removals, target].  A stopped mesh is not touched again, so neither its
+ *   batch-mates nor the number of rounds per call enter its result.
+ * mesh_counts (b, 20) int32: stop, rounds, collapses, faces_in, faces_out (live), vertices_in, vertices_out (live), locked_vertices,
+ *   bad_faces, the bits of the largest applied float32 cost, then of the mesh's last round: selected, edges evaluated, and the edges
+ *   refused as nonmanifold, locked, cost, link, boundary, valence, flip; last the target.
+ *
+ * bdm_mesh_qem_init checks the batch, copies it into the workspace, forms the quadrics and writes mesh_counts.  target_faces: b int64
+ *   in HOST memory.  bdm_mesh_qem_rounds runs up to `rounds` rounds on the meshes that have not stopped, then writes mesh_counts and
+ *   *active (one int32 on the device) = the number of meshes still running; the caller repeats the call until it reads 0, which is the
+ *   only synchronisation.  maximum_error and max_rounds have to be the same in every call of a run.  bdm_mesh_qem_finish writes
+ *   vert_map (sum V; the new index of the survivor a vertex's chain ends in), face_map (sum F; the new index, -1 collapsed, -3 bad),
+ *   and verts_out (sum V', 3), attrs_out (sum V', c), faces_out (sum F', 3) packed by out_vert_first and out_face_first (b + 1 int64
+ *   in HOST memory) that the caller forms from mesh_counts: survivors in ascending old index, live faces in old order and winding.
+ *   Offsets that cannot be a decimated mesh are refused as in section 20; a row the given sizes do not hold is never written.
+ *   attrs (sum V, c) float32: a survivor nothing was merged into copies its row bit for bit; another takes section 19 rule 6's
+ *   fixed-point mean over the old vertices mapped to it (NaN for a channel with a non-finite member).  The three calls take the same
+ *   b, offsets and workspace, which stays untouched in between.
+ * Limits: 0 <= b <= 65535, sum V < 2^31, 6 sum F < 2^31, offsets non-decreasing from 0, boundary_weight finite and >= 0, every target
+ *   in 0 .. 2^31 - 2, 1 <= rounds, max_rounds <= 2^20, maximum_error >= 0 (+inf allowed), 0 <= c <= 16, no NULL pointer (with c == 0
+ *   attrs and attrs_out still point somewhere), the workspace 16-byte aligned, no output and no part of the workspace overlapping an
+ *   input or another output.  b == 0 returns 0 and launches nothing; anything else outside the limits returns 1, launches nothing and
+ *   leaves the outputs untouched.  bdm_mesh_qem_workspace_bytes returns 0 outside the limits.
+ * workspace: bdm_mesh_qem_workspace_bytes(b, sum_v, sum_f) bytes, contents irrelevant before bdm_mesh_qem_init: 148 bytes per vertex
+ *   and 104 per face (positions, quadrics, the two minima; the working faces, six 8-byte incidence records, a key and a flag per
+ *   half-edge) plus the offsets and counters.
+ * Determinism: the minima are gathered over the sorted incidence segments, without atomics; integer atomic adds and maxima only for
+ *   slot claims and counts; no floating-point atomics, no workgroup waits on another, every loop is bounded by a segment length or a
+ *   launch argument.  Mesh j of a batch has the bits of that mesh alone, and so has a repeated call.  One thread handles one vertex
+ *   or edge: a vertex of very high valence is slow, never wrong. */
+size_t bdm_mesh_qem_workspace_bytes(int b, long long sum_v, long long sum_f);
+int bdm_mesh_qem_init(int b, double boundary_weight, const long long *target_faces, const float *verts, const int *faces,
+                      const long long *vert_first, const long long *face_first, int *mesh_counts, void *workspace, void *stream);
+int bdm_mesh_qem_rounds(int b, int rounds, int max_rounds, double maximum_error, const long long *vert_first, const long long *face_first,
+                        int *mesh_counts, int *active, void *workspace, void *stream);
+int bdm_mesh_qem_finish(int b, int c, const float *attrs, const long long *vert_first, const long long *face_first,
+                        const long long *out_vert_first, const long long *out_face_first, float *verts_out, float *attrs_out, int *faces_out,
+                        int *vert_map, int *face_map, void *workspace, void *stream);
+/* For tests and diagnostics: where the state lies in the workspace.  offsets (6 int64 in HOST memory) = the byte offsets of the
+ * positions (sum V, 3) float32, the quadrics (sum V, 10) float64, the vertex live flags (sum V) int32, the working faces (sum F, 3)
+ * int32, the keys (3 sum F) uint64 and the selected flags (3 sum F) int32 of the last round.  Returns 1 outside the limits. */
+int bdm_mesh_qem_layout(int b, long long sum_v, long long sum_f, long long *offsets);
+
 #ifdef __cplusplus
 }
 #endif
