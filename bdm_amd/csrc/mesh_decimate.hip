@@ -14,23 +14,24 @@
 //   (mesh_incidence.h)    fill_ints_kernel; scan_kernel<false / true>, scan_top_kernel; connected_face.
 //   md_table_kernel       the open-addressing table emptied: keys to the marker with bit 63 set, values to INT_MAX.
 //   md_bounds_kernel      per mesh lo / hi of the finite vertices and the largest finite |coordinate|: order-preserving bits, reduced in
-//                         LDS, one integer atomic minimum / maximum per workgroup.  md_amax_kernel: the same for the attributes.
+//                         LDS, one integer atomic minimum / maximum per workgroup (mesh_emit.h's block_fold_atomic).
+//   (mesh_emit.h)         amax_clear_kernel, attr_amax_kernel: the largest finite |attribute| into stat[8 m + 7]; member_flag,
+//                         member_place and build_member_segments: the clusters' member segments; FixedMean: section 19's mean.
 //   md_cell_kernel        one thread per mesh: h.
 //   md_insert_kernel      one thread per vertex: its key claims a slot of the mesh's region (64-bit compare-and-swap on the key), then an
 //                         atomic minimum of the member index on the slot's leader.  Slot placement depends on arrival order; only
 //                         key -> leader leaves the table (md_leader_kernel reads it back per vertex).
-//   md_leader_kernel      leaders flagged for the rank scan, member counts (integer atomic adds at the leader) for the segment scan.
-//   md_member_kernel      vert_map out, members into their cluster's segment (claimed on a cursor), the per-mesh vertex counts.
+//   md_leader_kernel      the leader read back per vertex -> member_flag.
+//   md_member_kernel      member_place, and around it the per-mesh vertex counts.
 //   md_face_insert_kernel one thread per face: not connected / collapsed, or the sorted new triple (3 x 21 bits) claims a slot of the
 //                         same table and takes the minimum of the old face index.
 //   md_face_keep_kernel   kept = (minimum == own index); flags for the scan; per-mesh face counts.  md_face_map_kernel: face_map out.
-//   md_vertex_out_kernel  one thread per cluster (at its leader): copies a row, or walks the segment: 64-bit integer sums, one float64
-//                         divide, one rounding to float32.  md_face_out_kernel: the kept faces.
+//   md_vertex_out_kernel  one thread per cluster (at its leader): copies a row, or walks the segment into two FixedMean.
+//                         md_face_out_kernel: the kept faces.
 #include "../../include/bdm_hip.h"
 #include "common.h"
 #include "mesh_incidence.h"
-#include "mesh_mean.h"
-#include "align_solve.h"   // align_pow2
+#include "mesh_emit.h"
 
 #include <limits.h>
 #include <math.h>
@@ -42,7 +43,6 @@
 using namespace bdm;
 
 #define MD_THREADS MESH_THREADS
-#define MD_MAX_C 16
 #define MD_COUNTS 8                       // per-mesh counters, in the order of bdm_hip.h section 20
 #define MD_MAX_V (1 << 21)                // vertices per mesh, exclusive
 #define MD_MAX_CELL ((1 << 21) - 1)
@@ -105,63 +105,18 @@ __global__ __launch_bounds__(MD_THREADS) void md_stat_kernel(int n, unsigned *__
 // stat[8 m + 0..2] lo, [3..5] hi (ordered bits), [6] the bits of the largest finite |coordinate|
 __global__ __launch_bounds__(MD_THREADS) void md_bounds_kernel(const float *__restrict__ verts, const long long *__restrict__ vert_first,
                                                                unsigned *__restrict__ stat) {
-  __shared__ unsigned buf[7][MD_THREADS];
   const int m = blockIdx.y;
   const long long vbase = vert_first[m], nv = vert_first[m + 1] - vbase;
   const long long i = (long long)blockIdx.x * MD_THREADS + threadIdx.x;
   if ((long long)blockIdx.x * MD_THREADS >= nv) return;   // the whole workgroup
-  unsigned lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0, 0, 0}, amax = 0;
+  unsigned v[7] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0, 0, 0, 0};   // lo, hi, amax
   if (i < nv) {
     const float *p = verts + 3 * (size_t)(vbase + i);
-    const bool fin = md_finite3(p);
-    for (int d = 0; d < 3; ++d) {
-      const float a = fabsf(p[d]);
-      if (a < INFINITY) amax = max(amax, __float_as_uint(a));
-      if (fin) lo[d] = hi[d] = md_ordered(p[d]);
-    }
+    v[6] = amax_fold(p, 3, 0);
+    if (md_finite3(p))
+      for (int d = 0; d < 3; ++d) v[d] = v[3 + d] = md_ordered(p[d]);
   }
-  for (int d = 0; d < 3; ++d) buf[d][threadIdx.x] = lo[d], buf[3 + d][threadIdx.x] = hi[d];
-  buf[6][threadIdx.x] = amax;
-  __syncthreads();
-  for (int off = MD_THREADS / 2; off > 0; off >>= 1) {
-    if (threadIdx.x < off) {
-      for (int d = 0; d < 3; ++d) buf[d][threadIdx.x] = min(buf[d][threadIdx.x], buf[d][threadIdx.x + off]);
-      for (int d = 3; d < 7; ++d) buf[d][threadIdx.x] = max(buf[d][threadIdx.x], buf[d][threadIdx.x + off]);
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x < 3) atomicMin(stat + 8 * m + threadIdx.x, buf[threadIdx.x][0]);
-  else if (threadIdx.x < 7) atomicMax(stat + 8 * m + threadIdx.x, buf[threadIdx.x][0]);
-}
-
-__global__ __launch_bounds__(MD_THREADS) void md_clear_kernel(int b, unsigned *__restrict__ word) {
-  const int m = blockIdx.x * MD_THREADS + threadIdx.x;
-  if (m < b) word[8 * m] = 0u;
-}
-
-// stat[8 m + 7]: the bits of the largest finite |attribute| of mesh m
-__global__ __launch_bounds__(MD_THREADS) void md_amax_kernel(int c, const float *__restrict__ attrs, const long long *__restrict__ vert_first,
-                                                             unsigned *__restrict__ stat) {
-  __shared__ unsigned buf[MD_THREADS];
-  const int m = blockIdx.y;
-  const long long vbase = vert_first[m], nv = vert_first[m + 1] - vbase;
-  const long long i = (long long)blockIdx.x * MD_THREADS + threadIdx.x;
-  if ((long long)blockIdx.x * MD_THREADS >= nv) return;
-  unsigned amax = 0;
-  if (i < nv) {
-    const float *q = attrs + (size_t)c * (size_t)(vbase + i);
-    for (int d = 0; d < c; ++d) {
-      const float a = fabsf(q[d]);
-      if (a < INFINITY) amax = max(amax, __float_as_uint(a));
-    }
-  }
-  buf[threadIdx.x] = amax;
-  __syncthreads();
-  for (int off = MD_THREADS / 2; off > 0; off >>= 1) {
-    if (threadIdx.x < off) buf[threadIdx.x] = max(buf[threadIdx.x], buf[threadIdx.x + off]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) atomicMax(stat + 8 * m + 7, buf[0]);
+  block_fold_atomic<7, 3>(v, stat + 8 * m);
 }
 
 // cell[m] = h.  given[m] holds the bits of a float: the mesh's cell size, or with by_resolution the resolution, the same for every
@@ -209,7 +164,7 @@ __global__ __launch_bounds__(MD_THREADS) void md_insert_kernel(const float *__re
   slot[vbase + i] = md_insert(tkey + region, tval + region, (unsigned)(2 * nv + 1), key, (int)i);
 }
 
-// lead[g]; rank[g] = 1 at a leader (entry sum V: 0); seg[vbase + leader] += 1 (seg zeroed before)
+// member_flag at the leader the table holds for the vertex's key (rank's entry sum V: 0)
 __global__ __launch_bounds__(MD_THREADS) void md_leader_kernel(const long long *__restrict__ vert_first, long long sum_v,
                                                                const int *__restrict__ tval, const int *__restrict__ slot,
                                                                int *__restrict__ lead, int *__restrict__ rank, int *__restrict__ seg) {
@@ -222,9 +177,7 @@ __global__ __launch_bounds__(MD_THREADS) void md_leader_kernel(const long long *
   int l = (int)i;
   if (s >= 0) l = tval[2 * vbase + m + s];
   if (l < 0 || l > i) l = (int)i;   // never: the minimum over the members is at most i
-  lead[vbase + i] = l;
-  rank[vbase + i] = l == i ? 1 : 0;
-  atomicAdd(seg + vbase + l, 1);
+  member_flag(vbase, i, l, lead, rank, seg);
 }
 
 // counts of mesh m: 0 new_vertices, 1 new_faces, 2 collapsed_faces, 3 duplicate_faces, 4 bad_faces, 5 nonfinite_vertices,
@@ -242,10 +195,8 @@ __global__ __launch_bounds__(MD_THREADS) void md_member_kernel(const long long *
   if (threadIdx.x < 3) part[threadIdx.x] = 0;
   __syncthreads();
   if (i < nv) {
-    const long long g = vbase + lead[vbase + i];
+    const long long g = member_place(vbase, i, lead, rank, seg, cursor, member, vert_map);
     const int size = seg[g + 1] - seg[g];
-    member[seg[g] + atomicAdd(cursor + g, 1)] = (int)i;
-    vert_map[vbase + i] = rank[g] - rank[vbase];
     if (slot[vbase + i] < 0) atomicAdd(part + 0, 1);
     if (g == vbase + i) atomicMax(part + 1, size);
     if (size > 1) atomicAdd(part + 2, 1);
@@ -330,10 +281,6 @@ __global__ __launch_bounds__(MD_THREADS) void md_face_map_kernel(const long long
 }
 
 // ---- output ---------------------------------------------------------------------------------------------------------------------------
-// the fixed point of the means (mesh_mean.h; mesh_fill.hip's rule)
-__device__ __forceinline__ int md_scale_exp(unsigned amax_bits) { return mean_scale_exp(amax_bits); }
-__device__ __forceinline__ float md_mean(long long s, double inv, double n) { return mean_of_sum(s, inv, n); }
-
 // one thread per vertex; the leader of a cluster writes the cluster's row (never one the caller's sizes do not hold)
 __global__ __launch_bounds__(MD_THREADS) void md_vertex_out_kernel(int c, int average, const float *__restrict__ verts,
                                                                    const float *__restrict__ attrs, const long long *__restrict__ vert_first,
@@ -356,37 +303,16 @@ __global__ __launch_bounds__(MD_THREADS) void md_vertex_out_kernel(int c, int av
     for (int d = 0; d < c; ++d) oa[d] = q[d];
     return;
   }
-  const int ev = md_scale_exp(stat[8 * m + 6]), ea = md_scale_exp(stat[8 * m + 7]);
-  const double qv = align_pow2(ev), qa = align_pow2(ea);
-  long long sum[3 + MD_MAX_C];
-  bool bad[MD_MAX_C];
-#pragma unroll
-  for (int d = 0; d < 3 + MD_MAX_C; ++d) sum[d] = 0;
-#pragma unroll
-  for (int d = 0; d < MD_MAX_C; ++d) bad[d] = false;
+  FixedMean<3, false> mv(stat[8 * m + 6]);   // a non-finite vertex is a cluster of its own
+  FixedMean<MESH_MAX_C, true> ma(stat[8 * m + 7]);
   const int *mem = member + seg[g];
   for (int t = 0; t < size; ++t) {   // the segment's order depends on arrival; integer sums do not
     const long long a = vbase + mem[t];
-    const float *p = verts + 3 * (size_t)a;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) sum[d] += (long long)rint((double)p[d] * qv);
-    const float *q = attrs + (size_t)c * (size_t)a;
-#pragma unroll
-    for (int d = 0; d < MD_MAX_C; ++d) {
-      if (d >= c) break;
-      const float v = q[d];
-      if (fabsf(v) < INFINITY) sum[3 + d] += (long long)rint((double)v * qa);
-      else bad[d] = true;
-    }
+    mv.add(verts + 3 * (size_t)a, 3);
+    ma.add(attrs + (size_t)c * (size_t)a, c);
   }
-  const double n = (double)size, iv = align_pow2(-ev), ia = align_pow2(-ea);
-#pragma unroll
-  for (int d = 0; d < 3; ++d) o[d] = __float_as_uint(md_mean(sum[d], iv, n));
-#pragma unroll
-  for (int d = 0; d < MD_MAX_C; ++d) {
-    if (d >= c) break;
-    oa[d] = __float_as_uint(bad[d] ? NAN : md_mean(sum[3 + d], ia, n));
-  }
+  mv.write((float *)o, 3, (double)size);
+  ma.write((float *)oa, c, (double)size);
 }
 
 __global__ __launch_bounds__(MD_THREADS) void md_face_out_kernel(const int *__restrict__ faces, const long long *__restrict__ vert_first,
@@ -509,12 +435,13 @@ extern "C" int bdm_mesh_cluster(int b, int resolution, const float *voxel_size, 
     hipLaunchKernelGGL(md_bounds_kernel, grid_v, block, 0, st, verts, w.vert_first, w.stat);
     hipLaunchKernelGGL(md_cell_kernel, dim3((unsigned)cdivll(b, MD_THREADS)), block, 0, st, b, voxel_size ? 0 : 1, w.given, w.stat, w.cell);
     hipLaunchKernelGGL(md_insert_kernel, grid_v, block, 0, st, verts, w.vert_first, w.stat, w.cell, w.tkey, w.tval, w.slot);
-    fill_ints(w.seg, sum_v + 1, 0, st);
-    fill_ints(w.cursor, sum_v, 0, st);
-    hipLaunchKernelGGL(md_leader_kernel, grid_v, block, 0, st, w.vert_first, sum_v, w.tval, w.slot, w.lead, w.rank, w.seg);
-    exclusive_scan_ints(w.rank, sum_v + 1, nullptr, w.bsum, st);
-    exclusive_scan_ints(w.seg, sum_v + 1, nullptr, w.bsum, st);
-    hipLaunchKernelGGL(md_member_kernel, grid_v, block, 0, st, w.vert_first, w.slot, w.lead, w.rank, w.seg, w.cursor, w.member, vert_map, mesh_counts);
+    build_member_segments(
+        sum_v, w.rank, w.seg, w.cursor, w.bsum, st,
+        [&] { hipLaunchKernelGGL(md_leader_kernel, grid_v, block, 0, st, w.vert_first, sum_v, w.tval, w.slot, w.lead, w.rank, w.seg); },
+        [&] {
+          hipLaunchKernelGGL(md_member_kernel, grid_v, block, 0, st, w.vert_first, w.slot, w.lead, w.rank, w.seg, w.cursor, w.member, vert_map,
+                             mesh_counts);
+        });
   }
   if (max_f == 0) return launch_status("mesh_cluster");
   const dim3 grid_f((unsigned)cdivll(max_f, MD_THREADS), (unsigned)b);
@@ -530,22 +457,13 @@ extern "C" int bdm_mesh_decimate(int b, int resolution, const float *voxel_size,
                                  const int *faces, const long long *vert_first, const long long *face_first, const long long *out_vert_first,
                                  const long long *out_face_first, float *verts_out, float *attrs_out, int *faces_out, void *workspace,
                                  void *stream) {
-  BDM_REQUIRE(c >= 0 && c <= MD_MAX_C, "mesh_decimate: %d attribute channels outside 0 .. %d", c, MD_MAX_C);
-  long long max_v = 0, max_f = 0, max_ov = 0, max_of = 0;
-  if (md_check("mesh_decimate", b, resolution, voxel_size, contraction, vert_first, face_first, workspace, max_v, max_f) != BDM_OK)
+  long long max_v = 0, max_f = 0;
+  const auto batch = [&] { return md_check("mesh_decimate", b, resolution, voxel_size, contraction, vert_first, face_first, workspace, max_v, max_f); };
+  if (check_emit("mesh_decimate", "decimated", b, c, vert_first, face_first, out_vert_first, out_face_first,
+                 verts && attrs && faces && verts_out && attrs_out && faces_out, batch, decimated_sizes_ok) != BDM_OK)
     return BDM_ERR_ARG;
   if (b == 0) return BDM_OK;
-  BDM_REQUIRE(out_vert_first && out_face_first, "mesh_decimate: an output offset array is NULL");
-  if (check_first("mesh_decimate", "mesh", b, out_vert_first, &max_ov) != BDM_OK) return BDM_ERR_ARG;
-  if (check_first("mesh_decimate", "mesh", b, out_face_first, &max_of) != BDM_OK) return BDM_ERR_ARG;
   const long long sum_v = vert_first[b], sum_f = face_first[b], out_v = out_vert_first[b], out_f = out_face_first[b];
-  for (int m = 0; m < b; ++m) {
-    const long long nv = vert_first[m + 1] - vert_first[m], nf = face_first[m + 1] - face_first[m];
-    const long long ov = out_vert_first[m + 1] - out_vert_first[m], of = out_face_first[m + 1] - out_face_first[m];
-    BDM_REQUIRE(ov <= nv && (nv == 0 || ov >= 1) && of <= nf && (of == 0 || ov >= 3),
-                "mesh_decimate: mesh %d: %lld -> %lld vertices and %lld -> %lld faces cannot be a decimated mesh", m, nv, ov, nf, of);
-  }
-  BDM_REQUIRE(verts && attrs && faces && verts_out && attrs_out && faces_out, "mesh_decimate: an input or an output is NULL");
   const MdWs w = md_ws(workspace, b, sum_v, sum_f);
   const Range in[3] = {{verts, 12 * (size_t)sum_v}, {attrs, 4 * (size_t)c * (size_t)sum_v}, {faces, 12 * (size_t)sum_f}};
   const Range out[4] = {{verts_out, 12 * (size_t)out_v}, {attrs_out, 4 * (size_t)c * (size_t)out_v}, {faces_out, 12 * (size_t)out_f},
@@ -558,8 +476,8 @@ extern "C" int bdm_mesh_decimate(int b, int resolution, const float *voxel_size,
   const dim3 grid_v((unsigned)cdivll(max_v, MD_THREADS), (unsigned)b);
   const int average = contraction == 0;
   if (average && c > 0) {
-    hipLaunchKernelGGL(md_clear_kernel, dim3((unsigned)cdivll(b, MD_THREADS)), block, 0, st, b, w.stat + 7);
-    hipLaunchKernelGGL(md_amax_kernel, grid_v, block, 0, st, c, attrs, w.vert_first, w.stat);
+    hipLaunchKernelGGL(amax_clear_kernel, dim3((unsigned)cdivll(b, MD_THREADS)), block, 0, st, b, 8, w.stat + 7);
+    hipLaunchKernelGGL(attr_amax_kernel, grid_v, block, 0, st, c, attrs, w.vert_first, 8, w.stat + 7);
   }
   hipLaunchKernelGGL(md_vertex_out_kernel, grid_v, block, 0, st, c, average, verts, attrs, w.vert_first, w.out_vert_first, w.lead, w.rank, w.seg,
                      w.member, w.stat, verts_out, attrs_out);

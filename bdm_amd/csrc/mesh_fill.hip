@@ -22,14 +22,17 @@
 //   mf_double_kernel      one pointer-doubling round, Jacobi: reads one state array, writes the other.
 //   mf_label_kernel       labels out, loop sizes (integer atomic adds), pinched and non-finite flags (flag stores by atomic or).
 //   mf_decide_kernel      one thread per loop root: the loop's flags, the per-mesh counts.  mf_face_flag_kernel: which half-edges get a face.
-//   mf_amax_kernel        per mesh the bits of the largest finite |coordinate| and |attribute| (one integer atomic max per workgroup).
+//   mf_amax_kernel        per mesh the bits of the largest finite |coordinate| and |attribute| in one launch (mesh_emit.h's amax_fold
+//                         and block_fold_atomic: one integer atomic max per lane and workgroup).
 //   mf_copy_kernel        old rows to their place in the outputs.
-//   mf_mean_kernel        one thread per filled loop: walks the loop, 64-bit integer sums, one float64 divide, one rounding to float32.
+//   mf_mean_kernel        one thread per filled loop: walks the loop and feeds mesh_emit.h's FixedMean (64-bit integer sums, one
+//                         float64 divide, one rounding to float32).
 //   mf_emit_kernel        one thread per boundary half-edge of a filled loop: its face.
 #include "../../include/bdm_hip.h"
 #include "common.h"
 #include "mesh_incidence.h"
-#include "align_solve.h"   // align_pow2, align_ceil_log2
+#include "mesh_emit.h"
+#include "align_solve.h"   // align_ceil_log2
 
 #include <limits.h>
 #include <math.h>
@@ -40,7 +43,6 @@ using namespace bdm;
 
 #define MF_THREADS MESH_THREADS
 #define MF_MAX_EDGES 65535
-#define MF_MAX_C 16
 #define MF_COUNTS 9                       // per-mesh counters, in the order of bdm_hip.h section 19
 #define MF_STRIDE_BLOCKS 1024             // grid of the kernels on the compacted list
 #define MF_BLOCKED 0x80000000u
@@ -268,36 +270,15 @@ __global__ __launch_bounds__(MF_THREADS) void mf_face_flag_kernel(const int *__r
 // amax[2 m], amax[2 m + 1]: the bits of the largest finite |coordinate| and |attribute| of mesh m (bits of non-negative floats order as ints)
 __global__ __launch_bounds__(MF_THREADS) void mf_amax_kernel(int c, const float *__restrict__ verts, const float *__restrict__ attrs,
                                                              const long long *__restrict__ vert_first, unsigned *__restrict__ amax) {
-  __shared__ unsigned buf[2][MF_THREADS];
   const int m = blockIdx.y;
   const long long vbase = vert_first[m], nv = vert_first[m + 1] - vbase;
   const long long i = (long long)blockIdx.x * MF_THREADS + threadIdx.x;
-  unsigned mv = 0, ma = 0;
+  unsigned top[2] = {0, 0};
   if (i < nv) {
-    const float *p = verts + 3 * (size_t)(vbase + i);
-    for (int d = 0; d < 3; ++d) {
-      const float v = fabsf(p[d]);
-      if (v < INFINITY) mv = max(mv, __float_as_uint(v));
-    }
-    const float *q = attrs + (size_t)c * (size_t)(vbase + i);
-    for (int d = 0; d < c; ++d) {
-      const float v = fabsf(q[d]);
-      if (v < INFINITY) ma = max(ma, __float_as_uint(v));
-    }
+    top[0] = amax_fold(verts + 3 * (size_t)(vbase + i), 3, 0);
+    top[1] = amax_fold(attrs + (size_t)c * (size_t)(vbase + i), c, 0);
   }
-  buf[0][threadIdx.x] = mv, buf[1][threadIdx.x] = ma;
-  __syncthreads();
-  for (int off = MF_THREADS / 2; off > 0; off >>= 1) {
-    if (threadIdx.x < off) {
-      buf[0][threadIdx.x] = max(buf[0][threadIdx.x], buf[0][threadIdx.x + off]);
-      buf[1][threadIdx.x] = max(buf[1][threadIdx.x], buf[1][threadIdx.x + off]);
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    atomicMax(amax + 2 * m, buf[0][0]);
-    atomicMax(amax + 2 * m + 1, buf[1][0]);
-  }
+  block_fold_atomic<2, 0>(top, amax + 2 * m);
 }
 
 // rows of `width` 4-byte words: mesh m's n rows from in_first[m] to out_first[m] (never more than the output holds)
@@ -309,15 +290,6 @@ __global__ __launch_bounds__(MF_THREADS) void mf_copy_kernel(int width, const un
   if (i >= (n < room ? n : room) * width) return;
   to[obase * width + i] = from[ibase * width + i];
 }
-
-// the exponent e of the fixed point: every finite |value| <= amax quantises to rint(value 2^e) below 2^40 in magnitude
-__device__ __forceinline__ int mf_scale_exp(unsigned amax_bits) {
-  const int field = (int)((amax_bits >> 23) & 0xffu);
-  return 39 - ((field < 1 ? 1 : field) - 127);   // amax < 2^(E + 1), E = its exponent (zero and denormals: -126)
-}
-
-// S 2^-e / n in float64, rounded once to float32
-__device__ __forceinline__ float mf_mean(long long s, double inv, double n) { return (float)(((double)s * inv) / n); }
 
 __global__ __launch_bounds__(MF_THREADS) void mf_mean_kernel(int c, const int *__restrict__ faces, const float *__restrict__ verts,
                                                              const float *__restrict__ attrs, const long long *__restrict__ vert_first,
@@ -336,41 +308,18 @@ __global__ __launch_bounds__(MF_THREADS) void mf_mean_kernel(int c, const int *_
     const long long fbase = face_first[m], vbase = vert_first[m], nv = vert_first[m + 1] - vbase;
     const long long row = nv + (rankv[j] - rankv[pos[3 * fbase]]);   // the new vertex's index within its mesh
     if (row >= out_vert_first[m + 1] - out_vert_first[m]) continue;    // the caller's sizes do not hold it: never written
-    const int ev = mf_scale_exp(amax[2 * m]), ea = mf_scale_exp(amax[2 * m + 1]);
-    const double qv = align_pow2(ev), qa = align_pow2(ea);
-    long long sum[3 + MF_MAX_C];
-    bool bad[MF_MAX_C];
-#pragma unroll
-    for (int d = 0; d < 3 + MF_MAX_C; ++d) sum[d] = 0;
-#pragma unroll
-    for (int d = 0; d < MF_MAX_C; ++d) bad[d] = false;
+    FixedMean<3, false> mv(amax[2 * m]);   // a filled loop has finite sources
+    FixedMean<MESH_MAX_C, true> ma(amax[2 * m + 1]);
     int t = (int)j;
     for (int step = 0; step < size; ++step) {   // the loop's half-edges; integer sums do not depend on where the walk starts
       const long long h = bh[t] - 3 * fbase;
       const int a = faces[3 * (size_t)(fbase + h / 3) + h % 3];
-      const float *p = verts + 3 * (size_t)(vbase + a);
-#pragma unroll
-      for (int d = 0; d < 3; ++d) sum[d] += (long long)rint((double)p[d] * qv);
-      const float *q = attrs + (size_t)c * (size_t)(vbase + a);
-#pragma unroll
-      for (int d = 0; d < MF_MAX_C; ++d) {
-        if (d >= c) break;
-        const float v = q[d];
-        if (fabsf(v) < INFINITY) sum[3 + d] += (long long)rint((double)v * qa);
-        else bad[d] = true;
-      }
+      mv.add(verts + 3 * (size_t)(vbase + a), 3);
+      ma.add(attrs + (size_t)c * (size_t)(vbase + a), c);
       t = succ[t];
     }
-    const double n = (double)size, iv = align_pow2(-ev), ia = align_pow2(-ea);
-    float *o = verts_out + 3 * (size_t)(out_vert_first[m] + row);
-#pragma unroll
-    for (int d = 0; d < 3; ++d) o[d] = mf_mean(sum[d], iv, n);
-    float *oa = attrs_out + (size_t)c * (size_t)(out_vert_first[m] + row);
-#pragma unroll
-    for (int d = 0; d < MF_MAX_C; ++d) {
-      if (d >= c) break;
-      oa[d] = bad[d] ? NAN : mf_mean(sum[3 + d], ia, n);
-    }
+    mv.write(verts_out + 3 * (size_t)(out_vert_first[m] + row), 3, (double)size);
+    ma.write(attrs_out + (size_t)c * (size_t)(out_vert_first[m] + row), c, (double)size);
   }
 }
 
@@ -522,21 +471,16 @@ extern "C" int bdm_mesh_boundary_loops(int b, int max_hole_edges, const float *v
 extern "C" int bdm_mesh_fill_holes(int b, int c, const float *verts, const float *attrs, const int *faces, const long long *vert_first,
                                    const long long *face_first, const long long *out_vert_first, const long long *out_face_first,
                                    float *verts_out, float *attrs_out, int *faces_out, void *workspace, void *stream) {
-  BDM_REQUIRE(c >= 0 && c <= MF_MAX_C, "mesh_fill_holes: %d attribute channels outside 0 .. %d", c, MF_MAX_C);
-  long long max_v = 0, max_f = 0, max_ov = 0, max_of = 0;
-  if (mf_check("mesh_fill_holes", b, vert_first, face_first, workspace, max_v, max_f) != BDM_OK) return BDM_ERR_ARG;
+  long long max_v = 0, max_f = 0;
+  const auto batch = [&] { return mf_check("mesh_fill_holes", b, vert_first, face_first, workspace, max_v, max_f); };
+  const auto filled = [](long long nv, long long ov, long long nf, long long of) {
+    return ov >= nv && ov - nv <= nf && of >= nf && of - nf <= 3 * nf && of - nf >= 3 * (ov - nv);
+  };
+  if (check_emit("mesh_fill_holes", "filled", b, c, vert_first, face_first, out_vert_first, out_face_first,
+                 verts && attrs && faces && verts_out && attrs_out && faces_out, batch, filled) != BDM_OK)
+    return BDM_ERR_ARG;
   if (b == 0) return BDM_OK;
-  BDM_REQUIRE(out_vert_first && out_face_first, "mesh_fill_holes: an output offset array is NULL");
-  if (check_first("mesh_fill_holes", "mesh", b, out_vert_first, &max_ov) != BDM_OK) return BDM_ERR_ARG;
-  if (check_first("mesh_fill_holes", "mesh", b, out_face_first, &max_of) != BDM_OK) return BDM_ERR_ARG;
   const long long sum_v = vert_first[b], sum_f = face_first[b], H = 3 * sum_f, out_v = out_vert_first[b], out_f = out_face_first[b];
-  for (int m = 0; m < b; ++m) {
-    const long long nv = vert_first[m + 1] - vert_first[m], nf = face_first[m + 1] - face_first[m];
-    const long long ov = out_vert_first[m + 1] - out_vert_first[m], of = out_face_first[m + 1] - out_face_first[m];
-    BDM_REQUIRE(ov >= nv && ov - nv <= nf && of >= nf && of - nf <= 3 * nf && of - nf >= 3 * (ov - nv),
-                "mesh_fill_holes: mesh %d: %lld -> %lld vertices and %lld -> %lld faces cannot be a filled mesh", m, nv, ov, nf, of);
-  }
-  BDM_REQUIRE(verts && attrs && faces && verts_out && attrs_out && faces_out, "mesh_fill_holes: an input or an output is NULL");
   const MfWs w = mf_ws(workspace, b, sum_v, sum_f);
   const Range in[3] = {{verts, 12 * (size_t)sum_v}, {attrs, 4 * (size_t)c * (size_t)sum_v}, {faces, 12 * (size_t)sum_f}};
   const Range out[4] = {{verts_out, 12 * (size_t)out_v}, {attrs_out, 4 * (size_t)c * (size_t)out_v}, {faces_out, 12 * (size_t)out_f},

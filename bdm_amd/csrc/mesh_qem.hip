@@ -21,13 +21,14 @@
 //   q_m1_kernel / q_m2_kernel   the minimum key at a vertex; the minimum of those over the vertex and its neighbours.
 //   q_select_kernel       selected = key == m2 at both ends.  q_apply_kernel: rule 5, by the selected edge's thread.
 //   q_begin_kernel / q_end_kernel / q_report_kernel   the per-round counters, the stopping rule, the read-back.
-//   q_root_kernel ... q_face_out_kernel   finish: chains resolved, survivors ranked, members gathered, rows written.
+//   q_root_kernel ... q_face_out_kernel   finish: chains resolved, survivors ranked, members gathered, rows written, over
+//                         mesh_emit.h's member_flag / member_place / build_member_segments, amax_clear_kernel / attr_amax_kernel
+//                         and FixedMean.
 // A one-workgroup form that keeps a small mesh's rounds in LDS is not offered: it was not measured, so it is left out.
 #include "../../include/bdm_hip.h"
 #include "common.h"
 #include "mesh_incidence.h"
-#include "mesh_mean.h"
-#include "align_solve.h"   // align_pow2
+#include "mesh_emit.h"
 
 #include <limits.h>
 #include <math.h>
@@ -39,7 +40,6 @@
 using namespace bdm;
 
 #define Q_THREADS MESH_THREADS
-#define Q_MAX_C 16
 #define Q_COUNTS 20   // per-mesh counters, in the order of bdm_hip.h section 23
 #define Q_MAX_ROUNDS (1 << 20)
 #define Q_INVALID 0xffffffffffffffffull
@@ -520,19 +520,16 @@ __global__ __launch_bounds__(Q_THREADS) void q_report_kernel(int b, const int *_
 }
 
 // ---- finish -------------------------------------------------------------------------------------------------------------------------------
-// root[g] = the survivor g's chain ends in; rank[g] = 1 at a survivor; seg[root] += 1 (rank and seg zeroed before)
-__global__ __launch_bounds__(Q_THREADS) void q_root_kernel(const long long *__restrict__ vert_first, const int *__restrict__ vlive,
-                                                           const int *__restrict__ parent, int *__restrict__ root, int *__restrict__ rank,
-                                                           int *__restrict__ seg) {
+// member_flag at the survivor the vertex's chain ends in (a survivor, and no other vertex, is its own parent)
+__global__ __launch_bounds__(Q_THREADS) void q_root_kernel(const long long *__restrict__ vert_first, const int *__restrict__ parent,
+                                                           int *__restrict__ root, int *__restrict__ rank, int *__restrict__ seg) {
   const int m = blockIdx.y;
   const long long vbase = vert_first[m], nv = vert_first[m + 1] - vbase;
   const long long i = (long long)blockIdx.x * Q_THREADS + threadIdx.x;
   if (i >= nv) return;
   int r = (int)i;
   for (long long step = 0; step < nv && parent[vbase + r] != r; ++step) r = parent[vbase + r];   // a chain descends: it ends
-  root[vbase + i] = r;
-  rank[vbase + i] = vlive[vbase + i];
-  atomicAdd(seg + vbase + r, 1);
+  member_flag(vbase, i, r, root, rank, seg);
 }
 
 __global__ __launch_bounds__(Q_THREADS) void q_face_flag_kernel(const long long *__restrict__ face_first, const int *__restrict__ wfaces,
@@ -543,7 +540,7 @@ __global__ __launch_bounds__(Q_THREADS) void q_face_flag_kernel(const long long 
   if (i < nf) frank[fbase + i] = wfaces[3 * (size_t)(fbase + i)] >= 0 ? 1 : 0;
 }
 
-// rank and seg are scanned: vert_map out, the members of every survivor into its segment (claimed on a cursor)
+// member_place for every vertex
 __global__ __launch_bounds__(Q_THREADS) void q_member_kernel(const long long *__restrict__ vert_first, const int *__restrict__ root,
                                                              const int *__restrict__ rank, const int *__restrict__ seg,
                                                              int *__restrict__ cursor, int *__restrict__ member, int *__restrict__ vert_map) {
@@ -551,39 +548,7 @@ __global__ __launch_bounds__(Q_THREADS) void q_member_kernel(const long long *__
   const long long vbase = vert_first[m], nv = vert_first[m + 1] - vbase;
   const long long i = (long long)blockIdx.x * Q_THREADS + threadIdx.x;
   if (i >= nv) return;
-  const long long g = vbase + root[vbase + i];
-  member[seg[g] + atomicAdd(cursor + g, 1)] = (int)i;
-  vert_map[vbase + i] = rank[g] - rank[vbase];
-}
-
-__global__ __launch_bounds__(Q_THREADS) void q_clear_kernel(int b, unsigned *__restrict__ amax) {
-  const int m = blockIdx.x * Q_THREADS + threadIdx.x;
-  if (m < b) amax[m] = 0u;
-}
-
-// amax[m]: the bits of the largest finite |attribute| of mesh m
-__global__ __launch_bounds__(Q_THREADS) void q_amax_kernel(int c, const float *__restrict__ attrs, const long long *__restrict__ vert_first,
-                                                           unsigned *__restrict__ amax) {
-  __shared__ unsigned buf[Q_THREADS];
-  const int m = blockIdx.y;
-  const long long vbase = vert_first[m], nv = vert_first[m + 1] - vbase;
-  const long long i = (long long)blockIdx.x * Q_THREADS + threadIdx.x;
-  if ((long long)blockIdx.x * Q_THREADS >= nv) return;
-  unsigned top = 0;
-  if (i < nv) {
-    const float *q = attrs + (size_t)c * (size_t)(vbase + i);
-    for (int d = 0; d < c; ++d) {
-      const float a = fabsf(q[d]);
-      if (a < INFINITY) top = max(top, __float_as_uint(a));
-    }
-  }
-  buf[threadIdx.x] = top;
-  __syncthreads();
-  for (int off = Q_THREADS / 2; off > 0; off >>= 1) {
-    if (threadIdx.x < off) buf[threadIdx.x] = max(buf[threadIdx.x], buf[threadIdx.x + off]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) atomicMax(amax + m, buf[0]);
+  member_place(vbase, i, root, rank, seg, cursor, member, vert_map);
 }
 
 // one thread per survivor: its position's bits, and its attribute row: a copy, or the fixed-point mean over its members
@@ -609,18 +574,11 @@ __global__ __launch_bounds__(Q_THREADS) void q_vertex_out_kernel(int c, const fl
     for (int d = 0; d < c; ++d) oa[d] = q[d];
     return;
   }
-  const int ea = mean_scale_exp(amax[m]);
-  const double qa = align_pow2(ea), ia = align_pow2(-ea), n = (double)size;
   const int *mem = member + seg[g];
-  for (int d = 0; d < c; ++d) {   // the segment's order depends on arrival; integer sums do not
-    long long sum = 0;
-    bool bad = false;
-    for (int t = 0; t < size; ++t) {
-      const float v = attrs[(size_t)c * (size_t)(vbase + mem[t]) + d];
-      if (fabsf(v) < INFINITY) sum += (long long)rint((double)v * qa);
-      else bad = true;
-    }
-    oa[d] = __float_as_uint(bad ? NAN : mean_of_sum(sum, ia, n));
+  for (int d = 0; d < c; ++d) {   // channel by channel: one sum in registers; the segment's order depends on arrival, integer sums do not
+    FixedMean<1, true> mean(amax[m]);
+    for (int t = 0; t < size; ++t) mean.add(attrs + (size_t)c * (size_t)(vbase + mem[t]) + d, 1);
+    mean.write((float *)oa + d, 1, (double)size);
   }
 }
 
@@ -798,21 +756,13 @@ extern "C" int bdm_mesh_qem_rounds(int b, int rounds, int max_rounds, double max
 extern "C" int bdm_mesh_qem_finish(int b, int c, const float *attrs, const long long *vert_first, const long long *face_first,
                                    const long long *out_vert_first, const long long *out_face_first, float *verts_out, float *attrs_out,
                                    int *faces_out, int *vert_map, int *face_map, void *workspace, void *stream) {
-  BDM_REQUIRE(c >= 0 && c <= Q_MAX_C, "mesh_qem_finish: %d attribute channels outside 0 .. %d", c, Q_MAX_C);
-  long long max_v = 0, max_f = 0, max_ov = 0, max_of = 0;
-  if (q_check("mesh_qem_finish", b, vert_first, face_first, workspace, max_v, max_f) != BDM_OK) return BDM_ERR_ARG;
+  long long max_v = 0, max_f = 0;
+  const auto batch = [&] { return q_check("mesh_qem_finish", b, vert_first, face_first, workspace, max_v, max_f); };
+  if (check_emit("mesh_qem_finish", "decimated", b, c, vert_first, face_first, out_vert_first, out_face_first,
+                 attrs && verts_out && attrs_out && faces_out && vert_map && face_map, batch, decimated_sizes_ok) != BDM_OK)
+    return BDM_ERR_ARG;
   if (b == 0) return BDM_OK;
-  BDM_REQUIRE(out_vert_first && out_face_first, "mesh_qem_finish: an output offset array is NULL");
-  if (check_first("mesh_qem_finish", "mesh", b, out_vert_first, &max_ov) != BDM_OK) return BDM_ERR_ARG;
-  if (check_first("mesh_qem_finish", "mesh", b, out_face_first, &max_of) != BDM_OK) return BDM_ERR_ARG;
   const long long sum_v = vert_first[b], sum_f = face_first[b], out_v = out_vert_first[b], out_f = out_face_first[b];
-  for (int m = 0; m < b; ++m) {
-    const long long nv = vert_first[m + 1] - vert_first[m], nf = face_first[m + 1] - face_first[m];
-    const long long ov = out_vert_first[m + 1] - out_vert_first[m], of = out_face_first[m + 1] - out_face_first[m];
-    BDM_REQUIRE(ov <= nv && (nv == 0 || ov >= 1) && of <= nf && (of == 0 || ov >= 3),
-                "mesh_qem_finish: mesh %d: %lld -> %lld vertices and %lld -> %lld faces cannot be a decimated mesh", m, nv, ov, nf, of);
-  }
-  BDM_REQUIRE(attrs && verts_out && attrs_out && faces_out && vert_map && face_map, "mesh_qem_finish: an input or an output is NULL");
   const QWs w = q_ws(workspace, b, sum_v, sum_f);
   const Range in[1] = {{attrs, 4 * (size_t)c * (size_t)sum_v}};
   const Range out[6] = {{verts_out, 12 * (size_t)out_v}, {attrs_out, 4 * (size_t)c * (size_t)out_v}, {faces_out, 12 * (size_t)out_f},
@@ -824,15 +774,13 @@ extern "C" int bdm_mesh_qem_finish(int b, int c, const float *attrs, const long 
   if (max_v > 0) {
     const dim3 grid_v((unsigned)cdivll(max_v, Q_THREADS), (unsigned)b);
     fill_ints(w.rank, sum_v + 1, 0, st);
-    fill_ints(w.seg, sum_v + 1, 0, st);
-    fill_ints(w.cursor, sum_v + 1, 0, st);
-    hipLaunchKernelGGL(q_root_kernel, grid_v, block, 0, st, w.vert_first, w.vlive, w.parent, w.root, w.rank, w.seg);
-    exclusive_scan_ints(w.rank, sum_v + 1, nullptr, w.bsum, st);
-    exclusive_scan_ints(w.seg, sum_v + 1, nullptr, w.bsum, st);
-    hipLaunchKernelGGL(q_member_kernel, grid_v, block, 0, st, w.vert_first, w.root, w.rank, w.seg, w.cursor, w.member, vert_map);
+    build_member_segments(
+        sum_v, w.rank, w.seg, w.cursor, w.bsum, st,
+        [&] { hipLaunchKernelGGL(q_root_kernel, grid_v, block, 0, st, w.vert_first, w.parent, w.root, w.rank, w.seg); },
+        [&] { hipLaunchKernelGGL(q_member_kernel, grid_v, block, 0, st, w.vert_first, w.root, w.rank, w.seg, w.cursor, w.member, vert_map); });
     if (c > 0) {
-      hipLaunchKernelGGL(q_clear_kernel, dim3((unsigned)cdivll(b, Q_THREADS)), block, 0, st, b, w.amax);
-      hipLaunchKernelGGL(q_amax_kernel, grid_v, block, 0, st, c, attrs, w.vert_first, w.amax);
+      hipLaunchKernelGGL(amax_clear_kernel, dim3((unsigned)cdivll(b, Q_THREADS)), block, 0, st, b, 1, w.amax);
+      hipLaunchKernelGGL(attr_amax_kernel, grid_v, block, 0, st, c, attrs, w.vert_first, 1, w.amax);
     }
     hipLaunchKernelGGL(q_vertex_out_kernel, grid_v, block, 0, st, c, attrs, w.vert_first, w.out_vert_first, w.pos, w.vlive, w.rank, w.seg, w.member,
                        w.amax, verts_out, attrs_out);

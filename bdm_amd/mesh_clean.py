@@ -26,7 +26,6 @@ import argparse
 import json
 import math
 import sys
-from pathlib import Path
 
 import torch
 
@@ -35,6 +34,7 @@ from . import ops
 from .mesh_fill import INFO_KEYS as FILL_KEYS   # what a clean_fn that fills holes adds to the info of a mesh (mesh_fill imports nothing of this module)
 from .mesh_decimate import INFO_KEYS as DECIMATE_KEYS   # likewise for one that decimates, under "decimate_" + key
 QEM_KEYS = ("rounds", "collapses", "locked_vertices")   # and for one that decimates by quadrics (sums; the maximum for rounds)
+from .mesh_batch import walk_tree, with_padded_colors
 from .ragged import mesh_lists, pack_meshes
 
 MAX_B, MAX_ITER = 65535, 10000   # limits of bdm_hip.h section 16
@@ -230,28 +230,19 @@ def process_tree(mesh_dir, out_dir, clean_fn, batch_size=16):
     """Walk mesh_dir for mesh .ply files in sorted path order, up to batch_size files per call of clean_fn(verts_list, faces_list,
     colors_list; host tensors of ragged sizes, a colour entry None for a file that carries none) -> (verts_list, faces_list,
     colors_list, info as remove_small_components returns it; host tensors), and write out_dir/<same relative path>."""
-    from .io import load_mesh_ply, save_mesh_ply
-    mesh_dir, out_dir = Path(mesh_dir), Path(out_dir)
-    if batch_size < 1:
-        raise ValueError("batch_size must be positive")
-    items = [(path.relative_to(mesh_dir), path) for path in sorted(mesh_dir.rglob("*.ply"))]
     sums, fill_sums, decimate_sums = [0] * 7, {}, {}
-    for lo in range(0, len(items), batch_size):
-        chunk = items[lo:lo + batch_size]
-        loaded = [load_mesh_ply(path, with_colors=True) for _, path in chunk]
-        verts, faces, colors, info = clean_fn([torch.from_numpy(v) for v, _, _ in loaded], [torch.from_numpy(f) for _, f, _ in loaded],
-                                              [None if c is None else torch.from_numpy(c) for _, _, c in loaded])
-        for (rel, _), (v_in, f_in, _), v, f, c, i in zip(chunk, loaded, verts, faces, colors, info):
-            save_mesh_ply(v.numpy(), f.numpy(), out_dir / rel, colors=None if c is None else c.numpy())
-            for k, add in enumerate((1, v_in.shape[0], f_in.shape[0], v.shape[0], f.shape[0], i["components"], i["removed_components"])):
-                sums[k] += int(add)
-            for k in FILL_KEYS:
-                if k in i:   # clean_fn filled holes as well
-                    fill_sums[k] = fill_sums.get(k, 0) + int(i[k])
-            for k in DECIMATE_KEYS + QEM_KEYS:
-                if "decimate_" + k in i:   # clean_fn decimated as well
-                    combine = max if k in ("largest_cluster", "rounds") else int.__add__
-                    decimate_sums["decimate_" + k] = combine(decimate_sums.get("decimate_" + k, 0), int(i["decimate_" + k]))
+
+    def visit(v_in, f_in, v, f, i):
+        for k, add in enumerate((1, v_in.shape[0], f_in.shape[0], v.shape[0], f.shape[0], i["components"], i["removed_components"])):
+            sums[k] += int(add)
+        for k in FILL_KEYS:
+            if k in i:   # clean_fn filled holes as well
+                fill_sums[k] = fill_sums.get(k, 0) + int(i[k])
+        for k in DECIMATE_KEYS + QEM_KEYS:
+            if "decimate_" + k in i:   # clean_fn decimated as well
+                combine = max if k in ("largest_cluster", "rounds") else int.__add__
+                decimate_sums["decimate_" + k] = combine(decimate_sums.get("decimate_" + k, 0), int(i["decimate_" + k]))
+    walk_tree(mesh_dir, out_dir, clean_fn, batch_size, visit)
     result = compose_result(*sums)
     result.update(fill_sums)
     result.update(decimate_sums)
@@ -270,35 +261,19 @@ def clean_batch(verts_list, faces_list, colors_list, device, min_fraction=0.1, m
     verts, faces, cols, info = remove_small_components((verts, faces), min_fraction, min_faces, keep_largest, colors_list=cols, return_info=True)
     if fill_holes:
         from . import mesh_fill
-        # a zero-width colour tensor needs no mean; a batch mixes files with and without colours only through mesh_fill.fill_batch's padding
-        widths = {c.shape[1] for c in cols}
-        if len(widths) > 1:
-            width = max(widths)
-            padded = [c if c.shape[1] == width else c.new_zeros(c.shape[0], width) for c in cols]
-            verts, faces, filled, fill_info = mesh_fill.fill_holes((verts, faces), int(fill_holes), colors_list=padded, return_info=True)
-            cols = [f if c.shape[1] == width else f[:, :0] for f, c in zip(filled, cols)]
-        else:
-            verts, faces, cols, fill_info = mesh_fill.fill_holes((verts, faces), int(fill_holes), colors_list=cols, return_info=True)
+        verts, faces, cols, fill_info = with_padded_colors(mesh_fill.fill_holes, (verts, faces), cols, int(fill_holes))
         info = [{**i, **fi} for i, fi in zip(info, fill_info)]
     if decimate_resolution:
         from . import mesh_decimate
-        widths = {c.shape[1] for c in cols}
-        width = max(widths, default=0)
-        padded = [c if c.shape[1] == width else c.new_zeros(c.shape[0], width) for c in cols] if len(widths) > 1 else cols
-        verts, faces, thinned, dec_info = mesh_decimate.simplify_vertex_clustering((verts, faces), resolution=int(decimate_resolution),
-                                                                                   colors_list=padded, return_info=True)
-        cols = [t if c.shape[1] == width else t[:, :0] for t, c in zip(thinned, cols)]
+        verts, faces, cols, dec_info = with_padded_colors(mesh_decimate.simplify_vertex_clustering, (verts, faces), cols,
+                                                          resolution=int(decimate_resolution))
         info = [{**i, **{"decimate_" + k: v for k, v in di.items()}} for i, di in zip(info, dec_info)]
     if decimate_fraction:
         from . import mesh_decimate
         if decimate_resolution:
             raise ValueError("decimate_resolution and decimate_fraction exclude each other")
-        widths = {c.shape[1] for c in cols}
-        width = max(widths, default=0)
-        padded = [c if c.shape[1] == width else c.new_zeros(c.shape[0], width) for c in cols] if len(widths) > 1 else cols
-        verts, faces, thinned, dec_info = mesh_decimate.simplify_quadric_decimation((verts, faces), target_fraction=float(decimate_fraction),
-                                                                                    colors_list=padded, return_info=True)
-        cols = [t if c.shape[1] == width else t[:, :0] for t, c in zip(thinned, cols)]
+        verts, faces, cols, dec_info = with_padded_colors(mesh_decimate.simplify_quadric_decimation, (verts, faces), cols,
+                                                          target_fraction=float(decimate_fraction))
         info = [{**i, **{"decimate_" + k: di[k] for k in QEM_KEYS}} for i, di in zip(info, dec_info)]
     if taubin_iters:
         verts = taubin_smoothing((verts, faces), lambd, mu, taubin_iters, weights=weights).verts_list()

@@ -24,16 +24,16 @@ the rounds (the maximum over the files) and the collapses."""
 import argparse
 import json
 import sys
-from pathlib import Path
 
 import torch
 
 from . import _lib as L
 from . import ops
-from .mesh_fill import _check_colors, _round_uint8
+from .mesh_batch import MAX_C, _check_colors, _round_uint8   # noqa: F401  (their names here are part of the module)
+from .mesh_batch import alloc_outputs, mesh_tuple, run_on_host_batch, split_outputs, stage_attrs, walk_tree
 from .ragged import first, mesh_lists, pack_meshes
 
-MAX_B, MAX_V, MAX_R, MAX_C = 65535, 2 ** 21, 1024, 16   # limits of bdm_hip.h section 20
+MAX_B, MAX_V, MAX_R = 65535, 2 ** 21, 1024   # limits of bdm_hip.h section 20 (with mesh_batch.MAX_C)
 CONTRACTIONS = {"average": 0, "first": 1}
 COLLAPSED, DUPLICATE, BAD = -1, -2, -3   # face_map of a dropped face
 INFO_KEYS = ("new_vertices", "new_faces", "collapsed_faces", "duplicate_faces", "bad_faces", "nonfinite_vertices", "largest_cluster",
@@ -128,40 +128,23 @@ def simplify_vertex_clustering(meshes, voxel_size=None, resolution=None, contrac
     resolution, sizes = _check_grid(voxel_size, resolution, len(verts_list))
     C = 0 if colors_list is None else _check_colors(colors_list, verts_list)
     if not verts_list:
-        return ([], []) + (([],) if colors_list is not None else ()) + (([],) if return_info else ())
+        return mesh_tuple([], [], [], colors_list) + (([],) if return_info else ())
     _check_sizes(verts_list, faces_list)
     verts, faces, vert_first, face_first = pack_meshes(verts_list, faces_list)
     B, dev = len(verts_list), verts.device
-    if C:
-        for c in colors_list:
-            L.ptr(c)
-        attrs = L.f32(torch.cat([c.float() for c in colors_list] + [torch.zeros(1, C, device=dev)]))   # one unread row: never empty
-    else:
-        attrs = torch.zeros(1, 1, dtype=torch.float32, device=dev)
+    attrs = stage_attrs(colors_list, C, dev)
     _, _, counts, ws = _cluster(verts, faces, vert_first, face_first, resolution, sizes, contraction)
     counts = counts.cpu()   # the one read-back: it sizes the outputs
     new_v, new_f = counts[:, 0].tolist(), counts[:, 1].tolist()
     out_vert_first, out_face_first = first(new_v), first(new_f)
-    verts_out = torch.zeros(max(int(out_vert_first[-1]), 1), 3, dtype=torch.float32, device=dev)
-    attrs_out = torch.zeros(max(int(out_vert_first[-1]), 1), max(C, 1), dtype=torch.float32, device=dev)
-    faces_out = torch.zeros(max(int(out_face_first[-1]), 1), 3, dtype=torch.int32, device=dev)
+    verts_out, attrs_out, faces_out = alloc_outputs(out_vert_first, out_face_first, C, dev)
     lib = L.lib()
     L.check(lib.bdm_mesh_decimate(B, resolution, None if sizes is None else sizes.data_ptr(), CONTRACTIONS[contraction], C, L.ptr(verts),
                                   L.ptr(attrs), L.ptr(faces), vert_first.data_ptr(), face_first.data_ptr(), out_vert_first.data_ptr(),
                                   out_face_first.data_ptr(), L.ptr(verts_out), L.ptr(attrs_out), L.ptr(faces_out), L.ptr(ws), L.stream()),
             "mesh_decimate")
-    out_v, out_f, out_c = [], [], []
-    for m in range(B):
-        v0, f0 = int(out_vert_first[m]), int(out_face_first[m])
-        out_v.append(verts_out[v0:v0 + new_v[m]])
-        out_f.append(faces_out[f0:f0 + new_f[m]].to(faces_list[m].dtype))
-        if C:
-            rows = attrs_out[v0:v0 + new_v[m]]
-            out_c.append(_round_uint8(rows) if colors_list[m].dtype == torch.uint8 else rows.to(colors_list[m].dtype))
-        elif colors_list is not None:
-            out_c.append(colors_list[m].new_zeros(new_v[m], 0))
-    info = [dict(zip(INFO_KEYS, row)) for row in counts.tolist()]
-    return (out_v, out_f) + ((out_c,) if colors_list is not None else ()) + ((info,) if return_info else ())
+    out = split_outputs(verts_out, attrs_out, faces_out, out_vert_first, out_face_first, faces_list, colors_list, C)
+    return out + (([dict(zip(INFO_KEYS, row)) for row in counts.tolist()],) if return_info else ())
 
 
 # ---- quadric edge collapse (bdm_hip.h section 23) -------------------------------------------------------------------------------------
@@ -241,7 +224,7 @@ def simplify_quadric_decimation(meshes, target_number_of_triangles=None, target_
     _check_qem(maximum_error, boundary_weight, max_rounds)
     C = 0 if colors_list is None else _check_colors(colors_list, verts_list)
     if not verts_list:
-        return ([], []) + (([],) if colors_list is not None else ()) + (([],) if return_info else ()) + ((([], []),) if return_maps else ())
+        return mesh_tuple([], [], [], colors_list) + (([],) if return_info else ()) + ((([], []),) if return_maps else ())
     if len(verts_list) > MAX_B:
         raise ValueError(f"{len(verts_list)} meshes exceed {MAX_B}: split the batch")
     nv, nf = [int(v.shape[0]) for v in verts_list], [int(f.shape[0]) for f in faces_list]
@@ -249,12 +232,7 @@ def simplify_quadric_decimation(meshes, target_number_of_triangles=None, target_
         raise ValueError("the batch reaches 2^31 vertices or incidence records (six per face): split it")
     verts, faces, vert_first, face_first = pack_meshes(verts_list, faces_list)
     B, dev, sum_v, sum_f = len(verts_list), verts.device, sum(nv), sum(nf)
-    if C:
-        for c in colors_list:
-            L.ptr(c)
-        attrs = L.f32(torch.cat([c.float() for c in colors_list] + [torch.zeros(1, C, device=dev)]))   # one unread row: never empty
-    else:
-        attrs = torch.zeros(1, 1, dtype=torch.float32, device=dev)
+    attrs = stage_attrs(colors_list, C, dev)
     lib = L.lib()
     ws = ops.workspace(lib.bdm_mesh_qem_workspace_bytes(B, sum_v, sum_f), dev, "mesh_qem")
     counts = torch.zeros(B, len(QEM_INFO_KEYS), dtype=torch.int32, device=dev)
@@ -273,24 +251,12 @@ def simplify_quadric_decimation(meshes, target_number_of_triangles=None, target_
     rows = counts.cpu()
     new_v, new_f = rows[:, 6].tolist(), rows[:, 4].tolist()
     out_vert_first, out_face_first = first(new_v), first(new_f)
-    verts_out = torch.zeros(max(int(out_vert_first[-1]), 1), 3, dtype=torch.float32, device=dev)
-    attrs_out = torch.zeros(max(int(out_vert_first[-1]), 1), max(C, 1), dtype=torch.float32, device=dev)
-    faces_out = torch.zeros(max(int(out_face_first[-1]), 1), 3, dtype=torch.int32, device=dev)
+    verts_out, attrs_out, faces_out = alloc_outputs(out_vert_first, out_face_first, C, dev)
     vert_map = torch.zeros(max(sum_v, 1), dtype=torch.int32, device=dev)
     face_map = torch.zeros(max(sum_f, 1), dtype=torch.int32, device=dev)
     L.check(lib.bdm_mesh_qem_finish(B, C, L.ptr(attrs), vf, ff, out_vert_first.data_ptr(), out_face_first.data_ptr(), L.ptr(verts_out),
                                     L.ptr(attrs_out), L.ptr(faces_out), L.ptr(vert_map), L.ptr(face_map), L.ptr(ws), L.stream()), "mesh_qem_finish")
-    out_v, out_f, out_c = [], [], []
-    for m in range(B):
-        v0, f0 = int(out_vert_first[m]), int(out_face_first[m])
-        out_v.append(verts_out[v0:v0 + new_v[m]])
-        out_f.append(faces_out[f0:f0 + new_f[m]].to(faces_list[m].dtype))
-        if C:
-            part = attrs_out[v0:v0 + new_v[m]]
-            out_c.append(_round_uint8(part) if colors_list[m].dtype == torch.uint8 else part.to(colors_list[m].dtype))
-        elif colors_list is not None:
-            out_c.append(colors_list[m].new_zeros(new_v[m], 0))
-    out = (out_v, out_f) + ((out_c,) if colors_list is not None else ())
+    out = split_outputs(verts_out, attrs_out, faces_out, out_vert_first, out_face_first, faces_list, colors_list, C)
     if return_info:
         out += ([qem_info(row) for row in rows.tolist()],)
     if return_maps:
@@ -302,16 +268,7 @@ def simplify_quadric_decimation(meshes, target_number_of_triangles=None, target_
 def decimate_batch(verts_list, faces_list, colors_list, device, voxel_size=None, resolution=None, contraction="average"):
     """Host tensors of ragged sizes (a colour entry None for a file that carries none) -> (verts_list, faces_list, colors_list, info) on
     the host, through simplify_vertex_clustering.  Files without colours ride along with zero rows of the batch's colour width."""
-    verts, faces = [v.to(device) for v in verts_list], [f.to(device) for f in faces_list]
-    have = [c for c in colors_list if c is not None]
-    if have:
-        like = have[0]
-        cols = [like.new_zeros(v.shape[0], like.shape[1]).to(device) if c is None else c.to(device) for c, v in zip(colors_list, verts)]
-        verts, faces, cols, info = simplify_vertex_clustering((verts, faces), voxel_size, resolution, contraction, colors_list=cols, return_info=True)
-    else:
-        verts, faces, info = simplify_vertex_clustering((verts, faces), voxel_size, resolution, contraction, return_info=True)
-        cols = [None] * len(verts)
-    return ([v.cpu() for v in verts], [f.cpu() for f in faces], [None if c0 is None else c.cpu() for c, c0 in zip(cols, colors_list)], info)
+    return run_on_host_batch(simplify_vertex_clustering, verts_list, faces_list, colors_list, device, voxel_size, resolution, contraction)
 
 
 QEM_CLI_KEYS = ("rounds", "collapses", "locked_vertices", "bad_faces")   # of the quadric method's JSON line: sums, rounds the maximum
@@ -320,18 +277,8 @@ QEM_CLI_KEYS = ("rounds", "collapses", "locked_vertices", "bad_faces")   # of th
 def quadric_batch(verts_list, faces_list, colors_list, device, target_faces=None, target_fraction=None, maximum_error=float("inf"),
                   boundary_weight=1.0):
     """decimate_batch for simplify_quadric_decimation."""
-    verts, faces = [v.to(device) for v in verts_list], [f.to(device) for f in faces_list]
-    kw = dict(target_number_of_triangles=target_faces, target_fraction=target_fraction, maximum_error=maximum_error, boundary_weight=boundary_weight,
-              return_info=True)
-    have = [c for c in colors_list if c is not None]
-    if have:
-        like = have[0]
-        cols = [like.new_zeros(v.shape[0], like.shape[1]).to(device) if c is None else c.to(device) for c, v in zip(colors_list, verts)]
-        verts, faces, cols, info = simplify_quadric_decimation((verts, faces), colors_list=cols, **kw)
-    else:
-        verts, faces, info = simplify_quadric_decimation((verts, faces), **kw)
-        cols = [None] * len(verts)
-    return ([v.cpu() for v in verts], [f.cpu() for f in faces], [None if c0 is None else c.cpu() for c, c0 in zip(cols, colors_list)], info)
+    return run_on_host_batch(simplify_quadric_decimation, verts_list, faces_list, colors_list, device, target_number_of_triangles=target_faces,
+                             target_fraction=target_fraction, maximum_error=maximum_error, boundary_weight=boundary_weight)
 
 
 def compose_result(files, info_sums, vertices_in, faces_in, vertices_out, faces_out, edges_in, open_in, edges_out, open_out):
@@ -357,27 +304,17 @@ def process_tree(mesh_dir, out_dir, decimate_fn, batch_size=16, info_keys=INFO_K
     """Walk mesh_dir for mesh .ply files in sorted path order, up to batch_size files per call of decimate_fn(verts_list, faces_list,
     colors_list) -> (verts_list, faces_list, colors_list, info; host tensors), and write out_dir/<same relative path>.  info_keys are
     summed over the files, those in max_keys take the maximum."""
-    from .io import load_mesh_ply, save_mesh_ply
-    mesh_dir, out_dir = Path(mesh_dir), Path(out_dir)
-    if batch_size < 1:
-        raise ValueError("batch_size must be positive")
-    items = [(path.relative_to(mesh_dir), path) for path in sorted(mesh_dir.rglob("*.ply"))]
     sums, sizes, edges = {k: 0 for k in info_keys}, [0, 0, 0, 0], [0, 0, 0, 0]
-    for lo in range(0, len(items), batch_size):
-        chunk = items[lo:lo + batch_size]
-        loaded = [load_mesh_ply(path, with_colors=True) for _, path in chunk]
-        verts, faces, colors, info = decimate_fn([torch.from_numpy(v) for v, _, _ in loaded], [torch.from_numpy(f) for _, f, _ in loaded],
-                                                 [None if c is None else torch.from_numpy(c) for _, _, c in loaded])
-        for (rel, _), (v_in, f_in, _), v, f, c, i in zip(chunk, loaded, verts, faces, colors, info):
-            save_mesh_ply(v.numpy(), f.numpy(), out_dir / rel, colors=None if c is None else c.numpy())
-            before, after = _stats(torch.from_numpy(v_in), torch.from_numpy(f_in)), _stats(v, f)
-            for k, add in enumerate((before["edges"], before["open_edges"], after["edges"], after["open_edges"])):
-                edges[k] += add
-            for k, add in enumerate((v_in.shape[0], f_in.shape[0], v.shape[0], f.shape[0])):
-                sizes[k] += int(add)
-            for k in info_keys:
-                sums[k] = max(sums[k], int(i[k])) if k in max_keys else sums[k] + int(i[k])
-    return compose_result(len(items), sums, *sizes, *edges)
+
+    def visit(v_in, f_in, v, f, i):
+        before, after = _stats(torch.from_numpy(v_in), torch.from_numpy(f_in)), _stats(v, f)
+        for k, add in enumerate((before["edges"], before["open_edges"], after["edges"], after["open_edges"])):
+            edges[k] += add
+        for k, add in enumerate((v_in.shape[0], f_in.shape[0], v.shape[0], f.shape[0])):
+            sizes[k] += int(add)
+        for k in info_keys:
+            sums[k] = max(sums[k], int(i[k])) if k in max_keys else sums[k] + int(i[k])
+    return compose_result(walk_tree(mesh_dir, out_dir, decimate_fn, batch_size, visit), sums, *sizes, *edges)
 
 
 def parse_args(argv):

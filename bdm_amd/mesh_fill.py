@@ -15,15 +15,16 @@ gradients.  max_hole_edges = 32 is an interface default (MeshLab's close-holes d
 import argparse
 import json
 import sys
-from pathlib import Path
 
 import torch
 
 from . import _lib as L
 from . import ops
+from .mesh_batch import MAX_C, _check_colors, _round_uint8   # noqa: F401  (their names here are part of the module)
+from .mesh_batch import alloc_outputs, mesh_tuple, run_on_host_batch, split_outputs, stage_attrs, walk_tree
 from .ragged import first, mesh_lists, pack_meshes
 
-MAX_B, MAX_EDGES, MAX_C = 65535, 65535, 16   # limits of bdm_hip.h section 19
+MAX_B, MAX_EDGES = 65535, 65535   # limits of bdm_hip.h section 19 (with mesh_batch.MAX_C)
 FILLED, TOO_LARGE, PINCHED, NONFINITE = 1, 2, 4, 8   # loop flags
 INFO_KEYS = ("boundary_edges", "loops", "filled_loops", "too_large_loops", "pinched_loops", "nonfinite_loops", "blocked_edges", "new_vertices",
              "new_faces")
@@ -41,24 +42,6 @@ def _check_sizes(verts_list, faces_list):
     sum_v, sum_f = sum(int(v.shape[0]) for v in verts_list), sum(int(f.shape[0]) for f in faces_list)
     if 6 * sum_f >= 2 ** 31 or sum_v + sum_f >= 2 ** 31 - 1:
         raise ValueError("the batch reaches 2^31 corner records (six per face) or vertex indices: split it")
-
-
-def _check_colors(colors_list, verts_list):
-    """-> C.  One (V_i, C) tensor per mesh, uint8 or floating point, the same C <= 16 everywhere."""
-    if not isinstance(colors_list, (list, tuple)) or len(colors_list) != len(verts_list):
-        raise ValueError("colors_list must be a list with one (V_i, C) tensor per mesh")
-    C = None
-    for c, v in zip(colors_list, verts_list):
-        if not torch.is_tensor(c) or c.dim() != 2 or c.shape[0] != v.shape[0]:
-            raise ValueError(f"a colour tensor is not ({v.shape[0]}, C)")
-        if c.dtype != torch.uint8 and not c.dtype.is_floating_point:
-            raise ValueError(f"a colour tensor is {c.dtype}, neither uint8 nor floating point")
-        C = c.shape[1] if C is None else C
-        if c.shape[1] != C:
-            raise ValueError("the colour tensors differ in their number of channels")
-    if C is not None and C > MAX_C:
-        raise ValueError(f"{C} colour channels exceed {MAX_C}")
-    return C or 0
 
 
 def _loops(verts, faces, vert_first, face_first, max_hole_edges):
@@ -96,11 +79,6 @@ def boundary_loops(meshes, max_hole_edges=32):
     return out
 
 
-def _round_uint8(rows):
-    """float32 means of uint8 values -> uint8: to nearest, halves to even, clamped; a NaN (it cannot come from uint8 sources) -> 0."""
-    return torch.nan_to_num(rows, nan=0.0).round().clamp(0, 255).to(torch.uint8)
-
-
 @torch.no_grad()
 def fill_holes(meshes, max_hole_edges=32, colors_list=None, return_info=False):
     """Close the small holes of every mesh -> (verts_list, faces_list[, colors_list][, info]).  Every boundary loop of at most
@@ -115,58 +93,30 @@ def fill_holes(meshes, max_hole_edges=32, colors_list=None, return_info=False):
     verts_list, faces_list = mesh_lists(meshes)
     C = 0 if colors_list is None else _check_colors(colors_list, verts_list)
     if not verts_list:
-        return ([], []) + (([],) if colors_list is not None else ()) + (([],) if return_info else ())
+        return mesh_tuple([], [], [], colors_list) + (([],) if return_info else ())
     _check_sizes(verts_list, faces_list)
     verts, faces, vert_first, face_first = pack_meshes(verts_list, faces_list)
     B, dev = len(verts_list), verts.device
-    if C:
-        for c in colors_list:
-            L.ptr(c)
-        attrs = L.f32(torch.cat([c.float() for c in colors_list] + [torch.zeros(1, C, device=dev)]))   # one unread row: never empty
-    else:
-        attrs = torch.zeros(1, 1, dtype=torch.float32, device=dev)
+    attrs = stage_attrs(colors_list, C, dev)
     _, _, _, counts, ws = _loops(verts, faces, vert_first, face_first, max_hole_edges)
     counts = counts.cpu()   # the one read-back: it sizes the outputs
     new_v, new_f = counts[:, 7].tolist(), counts[:, 8].tolist()
     nv, nf = [int(v.shape[0]) for v in verts_list], [int(f.shape[0]) for f in faces_list]
     out_vert_first, out_face_first = first(a + b for a, b in zip(nv, new_v)), first(a + b for a, b in zip(nf, new_f))
-    verts_out = torch.zeros(max(int(out_vert_first[-1]), 1), 3, dtype=torch.float32, device=dev)
-    attrs_out = torch.zeros(max(int(out_vert_first[-1]), 1), max(C, 1), dtype=torch.float32, device=dev)
-    faces_out = torch.zeros(max(int(out_face_first[-1]), 1), 3, dtype=torch.int32, device=dev)
+    verts_out, attrs_out, faces_out = alloc_outputs(out_vert_first, out_face_first, C, dev)
     lib = L.lib()
     L.check(lib.bdm_mesh_fill_holes(B, C, L.ptr(verts), L.ptr(attrs), L.ptr(faces), vert_first.data_ptr(), face_first.data_ptr(),
                                     out_vert_first.data_ptr(), out_face_first.data_ptr(), L.ptr(verts_out), L.ptr(attrs_out), L.ptr(faces_out),
                                     L.ptr(ws), L.stream()), "mesh_fill_holes")
-    out_v, out_f, out_c = [], [], []
-    for m in range(B):
-        v0, f0 = int(out_vert_first[m]), int(out_face_first[m])
-        v_old, f_old = verts_list[m], faces_list[m]
-        rows = verts_out[v0 + nv[m]:v0 + nv[m] + new_v[m]]
-        out_v.append(torch.cat([v_old, rows.to(v_old.dtype)]) if v_old.dtype == torch.float32 else verts_out[v0:v0 + nv[m] + new_v[m]])
-        out_f.append(torch.cat([f_old, faces_out[f0 + nf[m]:f0 + nf[m] + new_f[m]].to(f_old.dtype)]))   # the old rows keep their bits
-        if C:
-            c_old, rows = colors_list[m], attrs_out[v0 + nv[m]:v0 + nv[m] + new_v[m]]
-            out_c.append(torch.cat([c_old, _round_uint8(rows) if c_old.dtype == torch.uint8 else rows.to(c_old.dtype)]))
-        elif colors_list is not None:
-            out_c.append(torch.cat([colors_list[m], colors_list[m].new_zeros(new_v[m], 0)]))
-    info = [dict(zip(INFO_KEYS, row)) for row in counts.tolist()]
-    return (out_v, out_f) + ((out_c,) if colors_list is not None else ()) + ((info,) if return_info else ())
+    out = split_outputs(verts_out, attrs_out, faces_out, out_vert_first, out_face_first, faces_list, colors_list, C, old_verts=verts_list)
+    return out + (([dict(zip(INFO_KEYS, row)) for row in counts.tolist()],) if return_info else ())   # the old rows keep their bits
 
 
 # ---- command line ------------------------------------------------------------------------------------------------------------------
 def fill_batch(verts_list, faces_list, colors_list, device, max_hole_edges=32):
     """Host tensors of ragged sizes (a colour entry None for a file that carries none) -> (verts_list, faces_list, colors_list, info) on
     the host, through fill_holes.  Files without colours ride along with zero rows of the batch's colour width."""
-    verts, faces = [v.to(device) for v in verts_list], [f.to(device) for f in faces_list]
-    have = [c for c in colors_list if c is not None]
-    if have:
-        like = have[0]
-        cols = [like.new_zeros(v.shape[0], like.shape[1]).to(device) if c is None else c.to(device) for c, v in zip(colors_list, verts)]
-        verts, faces, cols, info = fill_holes((verts, faces), max_hole_edges, colors_list=cols, return_info=True)
-    else:
-        verts, faces, info = fill_holes((verts, faces), max_hole_edges, return_info=True)
-        cols = [None] * len(verts)
-    return ([v.cpu() for v in verts], [f.cpu() for f in faces], [None if c0 is None else c.cpu() for c, c0 in zip(cols, colors_list)], info)
+    return run_on_host_batch(fill_holes, verts_list, faces_list, colors_list, device, max_hole_edges)
 
 
 def compose_result(files, info_sums, edges_in, open_in, edges_out, open_out):
@@ -182,26 +132,16 @@ def compose_result(files, info_sums, edges_in, open_in, edges_out, open_out):
 def process_tree(mesh_dir, out_dir, fill_fn, batch_size=16):
     """Walk mesh_dir for mesh .ply files in sorted path order, up to batch_size files per call of fill_fn(verts_list, faces_list,
     colors_list) -> (verts_list, faces_list, colors_list, info; host tensors), and write out_dir/<same relative path>."""
-    from .io import load_mesh_ply, save_mesh_ply
     from .surface import mesh_stats
-    mesh_dir, out_dir = Path(mesh_dir), Path(out_dir)
-    if batch_size < 1:
-        raise ValueError("batch_size must be positive")
-    items = [(path.relative_to(mesh_dir), path) for path in sorted(mesh_dir.rglob("*.ply"))]
     sums, edges = {k: 0 for k in INFO_KEYS}, [0, 0, 0, 0]
-    for lo in range(0, len(items), batch_size):
-        chunk = items[lo:lo + batch_size]
-        loaded = [load_mesh_ply(path, with_colors=True) for _, path in chunk]
-        verts, faces, colors, info = fill_fn([torch.from_numpy(v) for v, _, _ in loaded], [torch.from_numpy(f) for _, f, _ in loaded],
-                                             [None if c is None else torch.from_numpy(c) for _, _, c in loaded])
-        for (rel, _), (v_in, f_in, _), v, f, c, i in zip(chunk, loaded, verts, faces, colors, info):
-            save_mesh_ply(v.numpy(), f.numpy(), out_dir / rel, colors=None if c is None else c.numpy())
-            before, after = mesh_stats(torch.from_numpy(v_in), torch.from_numpy(f_in)), mesh_stats(v, f)
-            for k, add in enumerate((before["edges"], before["open_edges"], after["edges"], after["open_edges"])):
-                edges[k] += add
-            for k in INFO_KEYS:
-                sums[k] += int(i[k])
-    return compose_result(len(items), sums, *edges)
+
+    def visit(v_in, f_in, v, f, i):
+        before, after = mesh_stats(torch.from_numpy(v_in), torch.from_numpy(f_in)), mesh_stats(v, f)
+        for k, add in enumerate((before["edges"], before["open_edges"], after["edges"], after["open_edges"])):
+            edges[k] += add
+        for k in INFO_KEYS:
+            sums[k] += int(i[k])
+    return compose_result(walk_tree(mesh_dir, out_dir, fill_fn, batch_size, visit), sums, *edges)
 
 
 def parse_args(argv):

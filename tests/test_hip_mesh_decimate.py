@@ -257,6 +257,26 @@ def test_scans_of_more_than_256_partial_sums_carry(hip, merge):
     assert R.same_floats(g["verts"][want["vert_map"][unused]], v[unused])
 
 
+@pytest.mark.parametrize("large_first", (False, True))
+def test_16_channels_with_a_nonfinite_member_in_the_last_and_per_mesh_magnitudes_2_to_the_20_apart(hip, large_first):
+    """c = 16 is the last channel the shared accumulator (csrc/mesh_emit.h) holds, and the attributes' largest magnitude of mesh m lives
+    at stride 8 in the per-mesh statistics.  The cube of cube_r2, flattened along z so that a voxel size of 0.5 merges it into four
+    clusters of two, twice: channel 15 has one non-finite member (its cluster's channel 15 is NaN, every other mean is finite) and the
+    second copy's attributes are 2^20 times the first's: a mean under the other mesh's fixed point, in either order, has other bits."""
+    v, f, _ = R.hand_meshes()["cube_r2"]
+    v = v * torch.tensor([1.0, 1.0, 0.4])
+    a = torch.randn(8, 16, generator=torch.Generator().manual_seed(2016)) * 3.0
+    small, large = a.clone(), a * 2.0 ** 20
+    small[5, 15], large[5, 15] = float("nan"), float("-inf")
+    meshes = [(v, f, large), (v, f, small)] if large_first else [(v, f, small), (v, f, large)]
+    p = Packed(meshes, 16)
+    for m, (g, (v_, f_, a_)) in enumerate(zip(_split(p, _run(p, dict(sizes=[0.5, 0.5]))), meshes)):
+        r = R.decimate(v_, f_, voxel_size=0.5, attrs=a_)
+        assert r["info"]["new_vertices"] == 4 and r["info"]["largest_cluster"] == 2 and r["info"]["merged_vertices"] == 8
+        assert torch.isnan(r["attrs"][:, 15]).tolist() == [False, True, False, False] and bool(torch.isfinite(r["attrs"][:, :15]).all())
+        _assert_mesh(g, r, 16, f"mesh {m} of two at 16 channels")
+
+
 def test_33_meshes_cross_the_launch_boundary_of_the_offsets_upload(hip):
     """b + 1 = 34 offsets (and 33 cell sizes) are one launch more than the 32 a launch carries: a wrong entry of the second launch
     mis-addresses mesh 32 or gives it another cell.  Squashed cubes and the two-triangle mesh in turn, mesh 16 empty."""

@@ -196,6 +196,26 @@ def test_33_meshes_cross_the_launch_boundary_of_the_offsets_upload(hip):
         _assert_mesh(g_, R.fill(mesh[0], mesh[1], 32, attrs=mesh[2]), 1, f"mesh {m} of 33")
 
 
+@pytest.mark.parametrize("large_first", (False, True))
+def test_16_channels_with_a_nonfinite_member_in_the_last_and_per_mesh_magnitudes_2_to_the_20_apart(hip, large_first):
+    """c = 16 is the last channel the shared accumulator (csrc/mesh_emit.h) holds.  The octahedron with a square hole, twice: channel 15
+    has one non-finite value on the rim of the hole (the new vertex's channel 15 is NaN, its other channels are means of four) and the
+    second copy's attributes are 2^20 times the first's, so the fixed point of one mesh is not the other's: a mean that read the other
+    mesh's largest magnitude, in either order of the two, has other bits."""
+    v, f, _ = R.hand_meshes()["octa_too_large"]
+    a = torch.randn(v.shape[0], 16, generator=torch.Generator().manual_seed(1916)) * 3.0
+    small, large = a.clone(), a * 2.0 ** 20
+    small[0, 15], large[0, 15] = float("nan"), float("inf")   # vertex 0 is on the rim of the hole: asserted on the new row below
+    meshes = [(v, f, large), (v, f, small)] if large_first else [(v, f, small), (v, f, large)]
+    p = Packed(meshes, 16)
+    for m, (g, (v_, f_, a_)) in enumerate(zip(_split(p, _run(p, 32)), meshes)):
+        r = R.fill(v_, f_, 32, attrs=a_)
+        assert r["info"]["filled_loops"] == 1 and r["info"]["new_vertices"] == 1
+        new = r["attrs"][v_.shape[0]:]
+        assert bool(torch.isnan(new[:, 15]).all()) and bool(torch.isfinite(new[:, :15]).all())
+        _assert_mesh(g, r, 16, f"mesh {m} of two at 16 channels")
+
+
 def test_scans_of_more_than_256_partial_sums_carry_with_a_host_and_a_device_count(hip):
     """87 400 separate triangles (and 10 unused vertices) have H = 262 200 half-edges, all on the boundary: the scan of the H + 1 flags
     (count from the host) and the scans of rankv and rankf over the compacted list (its length H read from the device) each have 257

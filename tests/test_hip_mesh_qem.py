@@ -59,12 +59,13 @@ def batch():
 
 
 class Packed:
-    def __init__(self, rows):
+    def __init__(self, rows, channels=C):
+        self.C = channels
         self.names = [r[0] for r in rows]
         self.nv, self.nf = [r[1].shape[0] for r in rows], [r[2].shape[0] for r in rows]
         self.b, self.sum_v, self.sum_f = len(rows), sum(self.nv), sum(self.nf)
         self.verts = torch.cat([r[1] for r in rows] + [torch.zeros(1, 3)]).float().cuda().contiguous()
-        self.attrs = torch.cat([r[3] for r in rows] + [torch.zeros(1, C)]).float().cuda().contiguous()
+        self.attrs = torch.cat([r[3] for r in rows] + [torch.zeros(1, channels)]).float().cuda().contiguous()
         self.faces = torch.cat([r[2] for r in rows] + [torch.zeros(1, 3, dtype=torch.int64)]).int().cuda().contiguous()
         self.vert_first = torch.tensor([0] + self.nv, dtype=torch.int64).cumsum(0)
         self.face_first = torch.tensor([0] + self.nf, dtype=torch.int64).cumsum(0)
@@ -113,7 +114,7 @@ class Run:
                 "key": take(o[4], 3 * p.sum_f, torch.int64, 8), "sel": take(o[5], 3 * p.sum_f, torch.int32, 4)}
 
     def finish(self):
-        p, L = self.p, self.L
+        p, L, C = self.p, self.L, self.p.C
         rows = self.info()
         ov = torch.tensor([0] + rows[:, 6].tolist(), dtype=torch.int64).cumsum(0)
         of = torch.tensor([0] + rows[:, 4].tolist(), dtype=torch.int64).cumsum(0)
@@ -260,6 +261,27 @@ def test_a_mesh_alone_has_the_bits_it_has_in_the_batch_and_max_rounds_stops(stag
         one = Packed([("grid", gv * torch.tensor([1.0, 1.3, 1.0]) + 0.1 * torch.sin(7.0 * gv[:, :1]) * torch.tensor([0.0, 0.0, 1.0]), gf, R.attrs_for(81, 5, C), 20)])
         r = R.decimate(one.verts[:-1].cpu(), gf, 20, boundary_weight=w, attrs=one.attrs[:-1].cpu())
         _assert_mesh(Run(one, weight=w).whole(8)[0], r, f"bent grid at weight {w}")
+
+
+@pytest.mark.parametrize("large_first", (False, True))
+def test_16_channels_with_a_nonfinite_member_in_the_last_and_per_mesh_magnitudes_2_to_the_20_apart(hip, large_first):
+    """c = 16 is the last channel the shared accumulator (csrc/mesh_emit.h) holds, and the attributes' largest magnitude of mesh m lives
+    at stride 1 here.  The octahedron, the smallest closed mesh of the table that collapses, down to six faces, twice: vertex 1 merges
+    into vertex 0 and channel 15 is non-finite at vertex 1 alone (the survivor's channel 15 is NaN, its other channels are means of
+    two), and the second copy's attributes are 2^20 times the first's: a mean under the other mesh's fixed point, in either order,
+    has other bits."""
+    v, f = R.hand_meshes()["octahedron"]
+    a = torch.randn(6, 16, generator=torch.Generator().manual_seed(2316)) * 3.0
+    small, large = a.clone(), a * 2.0 ** 20
+    small[1, 15], large[1, 15] = float("nan"), float("inf")
+    rows = [("small", v, f, small, 6), ("large", v, f, large, 6)]
+    rows = rows[::-1] if large_first else rows
+    got = Run(Packed(rows, 16)).whole(8)
+    for g, (name, v_, f_, a_, target) in zip(got, rows):
+        r = R.decimate(v_, f_, target, attrs=a_)
+        assert r["info"]["collapses"] == 1 and r["members"][0] == [0, 1]
+        assert torch.isnan(r["attrs"][:, 15]).tolist() == [True] + [False] * 4 and bool(torch.isfinite(r["attrs"][:, :15]).all())
+        _assert_mesh(g, r, f"{name} at 16 channels")
 
 
 def test_every_documented_limit_returns_1_and_leaves_the_outputs_untouched(hip):
