@@ -1,7 +1,8 @@
 // mesh_incidence.h -- what the operators on the vertex incidence of packed triangle meshes share (mesh_clean.hip, mesh_fill.hip;
 // DESIGN.md section 17.1): the checks every entry point starts with, an int fill, the exclusive int scan, the connected-face rule,
 // the two passes that give every packed vertex a segment of two records per face around it, and the per-thread sort of a segment.
-// Integer code only.  What a record is (Rec, below) and the limits on the sums stay with the operator.
+// Integer code only.  What a record is (Rec, below) and the limits on the sums stay with the operator.  The other mesh operators
+// take MESH_THREADS, the checks, fill_ints and connected_face from here (mesh_render.hip: the first and the last only).
 //
 // The library is built one translation unit at a time without relocatable device code, so the kernels have internal linkage: every
 // .hip that includes this header gets its own instances.

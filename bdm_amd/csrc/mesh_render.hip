@@ -4,18 +4,16 @@
 //
 // The rule in one paragraph: vertices are projected in float32, operation by operation (camera.h; no FMA contraction, and in this
 // file division correctly rounded), and snapped to 1/256 pixel; coverage is decided by three int64 edge functions at the pixel centre with a
-// half-plane rule for centres ON an edge; depth and barycentrics are float32 quotients of those integers; the pixel keeps the
+// half-plane rule for centres ON an edge (tri_cover.h); depth and barycentrics are float32 quotients of those integers; the pixel keeps the
 // smallest (bits of z) << 32 | face index.  Nothing depends on execution order: the only atomic is an integer minimum.
 //
 // Three kernels, after send_offsets (ragged.h) has put the two host offset arrays into the workspace.
 //   mesh_vertex_kernel    one thread per vertex: view transform, NDC, screen, snap -> (SX, SY, zv, usable), 16 bytes per vertex.
 //   mesh_raster_kernel    one thread per face: set-up (face_setup), the bounding box of the pixel centres it can cover clamped to
-//                         the image, then every centre of the box through face_pixel and, for a covered one, atomicMin on the
-//                         64-bit key image (preset to all ones).  A box of more than 16 x 16 pixels is not walked by its lane:
-//                         after the small faces the wave takes its large faces one at a time (ballot), all 64 lanes spread over
-//                         the box, so a full-screen triangle costs a wave and not a thread.  The key is read before the atomic
-//                         and a losing fragment skipped: the minimum only ever decreases, so a stale read can only let through
-//                         an atomic that then changes nothing.
+//                         the image, then every centre of the box (tri_walk_boxes of tri_cover.h: small boxes by their lane, large
+//                         ones by the whole wave) through face_pixel and, for a covered one, atomicMin on the 64-bit key image
+//                         (preset to all ones).  The key is read before the atomic and a losing fragment skipped: the minimum
+//                         only ever decreases, so a stale read can only let through an atomic that then changes nothing.
 //   mesh_resolve_kernel   one thread per pixel: the winner's face_setup and face_pixel again -- the same device functions, the
 //                         same bits -- then pix_to_face, zbuf, bary (swapped back to the face's own order) and the image.
 // The tile-binned form of render.hip (one workgroup per tile streams ALL faces) needs no atomics but reads an 88 000-face mesh
@@ -23,7 +21,8 @@
 #include "../../include/bdm_hip.h"
 #include "camera.h"
 #include "common.h"
-#include "ragged.h"
+#include "mesh_incidence.h"
+#include "tri_cover.h"
 
 #include <limits.h>
 
@@ -31,11 +30,8 @@
 
 using namespace bdm;
 
-#define MESH_THREADS 256
-#define MESH_SMALL_BOX 16                 // boxes up to 16 x 16 pixel centres are walked by the face's own lane
 #define MESH_MAX_C 4
 #define MESH_MAX_SIDE 4096
-#define MESH_SNAP 256                     // sub-pixel positions per pixel
 #define MESH_GUARD 4194304.f              // 2^22: |SX|, |SY| beyond it make the vertex unusable (edge products stay below 2^48)
 #define MESH_EMPTY_KEY 0xFFFFFFFFFFFFFFFFull
 
@@ -59,60 +55,41 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_vertex_kernel(int b, int su
   const float *p = verts + (size_t)i * 3;
   float u, v, zv;
   project_point(c, p[0], p[1], p[2], ortho, u, v, zv);
-  const float px = ((1.f - u) * half_w) * (float)MESH_SNAP, py = ((1.f - v) * half_h) * (float)MESH_SNAP;
+  const float px = ((1.f - u) * half_w) * (float)TRI_SNAP, py = ((1.f - v) * half_h) * (float)TRI_SNAP;
   // NaN fails every comparison; fabsf(inf) <= 2^22 is false
   const bool usable = zv > 0.f && zv < INFINITY && fabsf(px) <= MESH_GUARD && fabsf(py) <= MESH_GUARD;
   vrec[i] = usable ? make_int4((int)rintf(px), (int)rintf(py), __float_as_int(zv), 1) : make_int4(0, 0, 0, 0);
 }
 
 struct MeshFace {
-  int x0, y0, x1, y1, x2, y2;  // snapped screen positions, v1 and v2 swapped when the face was wound with A < 0
-  float z0, z1, z2;
+  Tri2 t;                      // snapped screen positions, v1 and v2 swapped when the face was wound with A < 0
+  float z0, z1, z2;            // in t's order
   long long area;              // > 0
   bool swapped;
 };
 
-__device__ __forceinline__ long long mesh_edge(int ax, int ay, int bx, int by, long long px, long long py) {
-  return (long long)(bx - ax) * (py - ay) - (long long)(by - ay) * (px - ax);
-}
-
-__device__ __forceinline__ bool mesh_owns(int dx, int dy) { return dy > 0 || (dy == 0 && dx > 0); }
-
 // row: the face's row in the packed array; vbase, nv: first vertex row and vertex count of its mesh.  false = the face is dropped.
+// connected_face also refuses a repeated index, which changes nothing: such a face has area 0, and no count tells the reasons apart.
 __device__ __forceinline__ bool face_setup(const int *__restrict__ faces, const int4 *__restrict__ vrec, long long row, long long vbase,
                                            long long nv, int cull, MeshFace &f) {
-  const int *fp = faces + (size_t)row * 3;
-  const int i0 = fp[0], i1 = fp[1], i2 = fp[2];
-  if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= nv || i1 >= nv || i2 >= nv) return false;
-  const int4 a = vrec[vbase + i0], b = vrec[vbase + i1], c = vrec[vbase + i2];
+  int idx[3];
+  if (!connected_face(faces, row, nv, idx)) return false;
+  const int4 a = vrec[vbase + idx[0]];
+  int4 b = vrec[vbase + idx[1]], c = vrec[vbase + idx[2]];
   if (!(a.w && b.w && c.w)) return false;
-  long long area = mesh_edge(a.x, a.y, b.x, b.y, c.x, c.y);
+  const long long area = tri_wind(f.t, a, b, c);   // b and c change places with their depths
   if (area == 0 || (cull && area > 0)) return false;
   f.swapped = area < 0;
-  f.x0 = a.x; f.y0 = a.y; f.z0 = __int_as_float(a.z);
-  if (f.swapped) {
-    f.x1 = c.x; f.y1 = c.y; f.z1 = __int_as_float(c.z);
-    f.x2 = b.x; f.y2 = b.y; f.z2 = __int_as_float(b.z);
-    area = -area;
-  } else {
-    f.x1 = b.x; f.y1 = b.y; f.z1 = __int_as_float(b.z);
-    f.x2 = c.x; f.y2 = c.y; f.z2 = __int_as_float(c.z);
-  }
-  f.area = area;
+  f.z0 = __int_as_float(a.z), f.z1 = __int_as_float(b.z), f.z2 = __int_as_float(c.z);
+  f.area = f.swapped ? -area : area;
   return true;
 }
 
 // the fragment of face f at pixel (xi, yi): false = not covered or dropped; z its depth; WITH_BARY: b0 .. b2 in f's (swapped) order
 template <bool WITH_BARY>
 __device__ __forceinline__ bool face_pixel(const MeshFace &f, int xi, int yi, int ortho, float &z, float &b0, float &b1, float &b2) {
-  const long long px = (long long)MESH_SNAP * xi + MESH_SNAP / 2, py = (long long)MESH_SNAP * yi + MESH_SNAP / 2;
-  const long long e0 = mesh_edge(f.x1, f.y1, f.x2, f.y2, px, py);
-  const long long e1 = mesh_edge(f.x2, f.y2, f.x0, f.y0, px, py);
-  const long long e2 = mesh_edge(f.x0, f.y0, f.x1, f.y1, px, py);
-  if (e0 < 0 || e1 < 0 || e2 < 0) return false;
-  if (e0 == 0 && !mesh_owns(f.x2 - f.x1, f.y2 - f.y1)) return false;
-  if (e1 == 0 && !mesh_owns(f.x0 - f.x2, f.y0 - f.y2)) return false;
-  if (e2 == 0 && !mesh_owns(f.x1 - f.x0, f.y1 - f.y0)) return false;
+  long long e0, e1, e2;
+  if (!tri_covers<true>(f.t, xi, yi, e0, e1, e2)) return false;   // the image's y runs downwards
   const float area = (float)f.area;
   const float w0 = (float)e0 / area, w1 = (float)e1 / area, w2 = (float)e2 / area;
   if (ortho) {
@@ -127,19 +104,19 @@ __device__ __forceinline__ bool face_pixel(const MeshFace &f, int xi, int yi, in
   return z > 0.f && z < INFINITY;
 }
 
-__device__ __forceinline__ void mesh_try_pixel(const MeshFace &f, int xi, int yi, int ortho, unsigned int face_in_mesh,
-                                               unsigned long long *__restrict__ keys_of_mesh, int w) {
-  float z, u0, u1, u2;
-  if (!face_pixel<false>(f, xi, yi, ortho, z, u0, u1, u2)) return;
-  const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | face_in_mesh;
-  unsigned long long *slot = keys_of_mesh + (size_t)yi * w + xi;  // 0 <= xi < w, 0 <= yi < h: the box is clamped to the image
-  if (key < __atomic_load_n(slot, __ATOMIC_RELAXED)) atomicMin(slot, key);
-}
+// a face on its way to the key image: what a lane needs per pixel, for its own face or for a broadcast one
+struct MeshItem {
+  MeshFace f;
+  unsigned long long *keys;  // of the face's mesh
+  unsigned int id;           // the face's index within its mesh
+};
 
-// pixel centres 256 i + 128 inside [lo, hi] (snapped coordinates), clamped to [0, size): first and last index, first > last = none
-__device__ __forceinline__ void mesh_span(int lo, int hi, int size, int &first, int &last) {
-  first = max((lo + (MESH_SNAP / 2 - 1)) >> 8, 0);   // ceil((lo - 128) / 256); >> on a negative int is arithmetic
-  last = min((hi - MESH_SNAP / 2) >> 8, size - 1);   // floor((hi - 128) / 256)
+__device__ __forceinline__ void mesh_try_pixel(const MeshItem &it, int xi, int yi, int ortho, int w) {
+  float z, u0, u1, u2;
+  if (!face_pixel<false>(it.f, xi, yi, ortho, z, u0, u1, u2)) return;
+  const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | it.id;
+  unsigned long long *slot = it.keys + (size_t)yi * w + xi;  // 0 <= xi < w, 0 <= yi < h: the box is clamped to the image
+  if (key < __atomic_load_n(slot, __ATOMIC_RELAXED)) atomicMin(slot, key);
 }
 
 __global__ __launch_bounds__(MESH_THREADS) void mesh_raster_kernel(int b, int sum_f, int h, int w, int ortho, int cull,
@@ -148,40 +125,21 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_raster_kernel(int b, int su
                                                                    const long long *__restrict__ face_first,
                                                                    unsigned long long *__restrict__ keys) {
   const int row = blockIdx.x * MESH_THREADS + threadIdx.x;  // the grid covers sum_f < 2^31 exactly once
-  MeshFace f;
+  const auto setup = [&](int bm, int brow, MeshItem &it) {   // the lane's own row and mesh, or broadcast ones
+    it.keys = keys + (size_t)bm * h * w;
+    it.id = (unsigned int)(brow - face_first[bm]);   // loaded before the set-up can refuse the face: measured faster than after it
+    return face_setup(faces, vrec, brow, vert_first[bm], vert_first[bm + 1] - vert_first[bm], cull, it.f);
+  };
+  MeshItem it;
   int m = 0, xa = 0, xb = -1, ya = 0, yb = -1;
-  bool live = row < sum_f;
+  bool live = row < sum_f;   // no lane leaves before the walk: its wave may hold large faces, and faces of several meshes
   if (live) {
     m = mesh_of_row(face_first, b, row);
-    live = face_setup(faces, vrec, row, vert_first[m], vert_first[m + 1] - vert_first[m], cull, f);
+    live = setup(m, row, it) && tri_box(it.f.t, w, h, xa, xb, ya, yb);
   }
-  if (live) {
-    mesh_span(min(f.x0, min(f.x1, f.x2)), max(f.x0, max(f.x1, f.x2)), w, xa, xb);
-    mesh_span(min(f.y0, min(f.y1, f.y2)), max(f.y0, max(f.y1, f.y2)), h, ya, yb);
-    live = xa <= xb && ya <= yb;
-  }
-  const bool large = live && (xb - xa >= MESH_SMALL_BOX || yb - ya >= MESH_SMALL_BOX);
-  if (live && !large) {
-    unsigned long long *km = keys + (size_t)m * h * w;
-    const unsigned int id = (unsigned int)(row - face_first[m]);
-    for (int yi = ya; yi <= yb; ++yi)        // at most 16 x 16 trips
-      for (int xi = xa; xi <= xb; ++xi) mesh_try_pixel(f, xi, yi, ortho, id, km, w);
-  }
-  // the wave's large faces, one at a time, all lanes on one box; the set-up is redone from the broadcast row (uniform loads)
-  unsigned long long todo = __ballot(large);
-  const int lane = threadIdx.x & 63;
-  for (int trip = 0; trip < 64 && todo; ++trip) {
-    const int src = __ffsll((long long)todo) - 1;
-    todo &= todo - 1;
-    const int brow = __shfl(row, src), bm = __shfl(m, src);
-    const int bxa = __shfl(xa, src), bxb = __shfl(xb, src), bya = __shfl(ya, src), byb = __shfl(yb, src);
-    MeshFace g;
-    if (!face_setup(faces, vrec, brow, vert_first[bm], vert_first[bm + 1] - vert_first[bm], cull, g)) continue;  // (it passed once)
-    unsigned long long *km = keys + (size_t)bm * h * w;
-    const unsigned int id = (unsigned int)(brow - face_first[bm]);
-    const int bw = bxb - bxa + 1, count = bw * (byb - bya + 1);  // <= h w <= 2^24
-    for (int i = lane; i < count; i += 64) mesh_try_pixel(g, bxa + i % bw, bya + i / bw, ortho, id, km, w);
-  }
+  // a large face is set up again from its broadcast row and mesh
+  tri_walk_boxes(live, xa, xb, ya, yb, it, [&](int src, MeshItem &g) { return setup(__shfl(m, src), __shfl(row, src), g); },
+                 [&](const MeshItem &g, int xi, int yi) { mesh_try_pixel(g, xi, yi, ortho, w); });
 }
 
 __global__ __launch_bounds__(MESH_THREADS) void mesh_resolve_kernel(int total, int h, int w, int c, int ortho, int cull,
@@ -254,15 +212,12 @@ struct MeshWs {
 };
 
 static MeshWs mesh_ws(void *ws, int b, long long sum_v, int h, int w) {
+  Carve c{(char *)ws, 0};
   MeshWs m;
-  char *p = (char *)ws;
-  const size_t key_bytes = sizeof(unsigned long long) * (size_t)b * h * w, rec_bytes = sizeof(int4) * (size_t)sum_v;
-  const size_t key_padded = align16(key_bytes);  // the records are loaded 16 bytes at a time
-  m.keys = (unsigned long long *)p;
-  m.vrec = (int4 *)(p + key_padded);
-  m.vert_first = (long long *)(p + key_padded + rec_bytes);
-  m.face_first = m.vert_first + (b + 1);
-  m.bytes = key_padded + rec_bytes + 2 * sizeof(long long) * (size_t)(b + 1);
+  m.keys = c.take<unsigned long long>((size_t)b * h * w);   // padded to 16 bytes: the records are loaded 16 bytes at a time
+  m.vrec = c.take<int4>((size_t)sum_v);
+  m.vert_first = c.take_offsets(b), m.face_first = m.vert_first + (b + 1);
+  m.bytes = c.o;
   return m;
 }
 

@@ -7,7 +7,7 @@
 // is dropped and counted.  Every predicate is evaluated at the centre moved by (eps, eps^2, eps^3), eps positive and infinitesimal, so
 // the ties of all three rays describe one point that is never on the surface.  Ray along axis w, (u, v) the two other axes in
 // increasing order: the column centre is covered when the three int64 edge functions of the face (corners b and c swapped when its
-// projected area is negative; area 0 contributes nothing) are > 0, or == 0 on an owned edge (mv_owns).  Cell k of a covered column
+// projected area is negative; area 0 contributes nothing) are > 0, or == 0 on an owned edge (tri_cover.h).  Cell k of a covered column
 // lies below the face when sign~(g(k)) sign(n_w) < 0, n = (b - a) x (c - a), g(k) = n . (p_k - a), sign~(0) = the sign of the first
 // non-zero of (n_x, n_y, n_z).  The face flips the parity of the cells below it; a cell is inside along w when its flips are odd.
 // Nothing depends on execution order: the only atomics are integer XORs and integer adds.
@@ -20,11 +20,11 @@
 // Kernels, after send_offsets (ragged.h) has put the offsets and the bits of the frames into the workspace.
 //   mv_snap_kernel     one thread per vertex: (qx, qy, qz, usable), 16 bytes.
 //   mv_flip_kernel     one thread per (face, axis): set-up (mv_setup), the box of the column centres the projection can cover clamped to
-//                      the grid, then every centre of the box through mv_column: coverage, the number c of cells below by a binary
-//                      search with the exact predicate (below is monotone in k: g is linear in k with slope 256 n_w), and for c > 0 one
-//                      atomicXor of bit c - 1 into the column's flip words (ceil(R / 32) words per column, axis and mesh).  A box of
-//                      more than 16 x 16 columns is not walked by its lane: the wave takes them one at a time, as mesh_raster_kernel
-//                      does.  Faces used and dropped are summed on chip, one atomic add each per workgroup.
+//                      the grid, then every centre of the box (tri_walk_boxes of tri_cover.h: small boxes by their lane, large ones by
+//                      the whole wave) through mv_column: coverage, the number c of cells below by a binary search with the exact
+//                      predicate (below is monotone in k: g is linear in k with slope 256 n_w), and for c > 0 one atomicXor of bit
+//                      c - 1 into the column's flip words (ceil(R / 32) words per column, axis and mesh).  Faces used and dropped are
+//                      summed on chip, one atomic add each per workgroup.
 //   mv_parity_kernel   one thread per column: the suffix XOR of its flip words in place (shift-doubling inside a word, a carry across
 //                      words): bit k becomes the parity of cell k.
 //   mv_resolve_kernel  one thread per cell of a workgroup's strip, 256 neighbouring cells at a time: the three parities, occupancy by
@@ -33,6 +33,7 @@
 #include "../../include/bdm_hip.h"
 #include "common.h"
 #include "mesh_incidence.h"
+#include "tri_cover.h"
 
 #include <limits.h>
 #include <math.h>
@@ -44,10 +45,8 @@
 using namespace bdm;
 
 #define MV_THREADS MESH_THREADS
-#define MV_SNAP 256                       // snapped positions per cell, as mesh_render.hip's MESH_SNAP
 #define MV_GUARD 524288.f                 // 2^19
 #define MV_MAX_R 512
-#define MV_SMALL_BOX 16                   // boxes up to 16 x 16 columns are walked by the item's own lane
 #define MV_STRIPS 2048                    // workgroups of the resolve kernel per mesh, at most
 #define MV_COUNTS 8                       // per-mesh counters, in the order of bdm_hip.h section 21
 
@@ -66,8 +65,8 @@ __global__ __launch_bounds__(MV_THREADS) void mv_snap_kernel(const float *__rest
   if (i >= nv) return;
   const float ox = mv_lo_float(frame_a[m]), oy = mv_hi_float(frame_a[m]), oz = mv_lo_float(frame_b[m]), h = mv_hi_float(frame_b[m]);
   const float *p = verts + 3 * (size_t)(vbase + i);
-  const float qx = rintf(((p[0] - ox) / h) * (float)MV_SNAP), qy = rintf(((p[1] - oy) / h) * (float)MV_SNAP),
-              qz = rintf(((p[2] - oz) / h) * (float)MV_SNAP);
+  const float qx = rintf(((p[0] - ox) / h) * (float)TRI_SNAP), qy = rintf(((p[1] - oy) / h) * (float)TRI_SNAP),
+              qz = rintf(((p[2] - oz) / h) * (float)TRI_SNAP);
   // NaN fails every comparison; fabsf(inf) <= 2^19 is false
   const bool usable = finite3(p[0], p[1], p[2]) && fabsf(qx) <= MV_GUARD && fabsf(qy) <= MV_GUARD && fabsf(qz) <= MV_GUARD;
   vrec[vbase + i] = usable ? make_int4((int)qx, (int)qy, (int)qz, 1) : make_int4(0, 0, 0, 0);
@@ -76,24 +75,15 @@ __global__ __launch_bounds__(MV_THREADS) void mv_snap_kernel(const float *__rest
 // One face seen along one axis: its corners in the projection plane, wound positive, and G(k) = sign(n_w) g(k) as
 // nu (pu - au) + nv (pv - av) + base + slope k.
 struct MvItem {
-  int au, av, bu, bv, cu, cv;
+  Tri2 t;                          // (u, v) of the corners
   long long nu, nv, base, slope;   // slope = 256 |n_w| > 0
   bool tie_below;                  // G(k) == 0: the perturbed centre lies below
+  unsigned *col;                   // the flip words of the item's mesh and axis
 };
-
-__device__ __forceinline__ long long mv_edge(int ax, int ay, int bx, int by, long long px, long long py) {
-  return (long long)(bx - ax) * (py - ay) - (long long)(by - ay) * (px - ax);
-}
-
-// A centre ON an edge with vector (du, dv) belongs to the face when the centre moved by (eps_u, eps_v), eps_u >> eps_v > 0 (u comes
-// before v in x, y, z), is inside: the edge function changes by du eps_v - dv eps_u, positive iff dv < 0, or dv == 0 and du > 0.
-// This is NOT mesh_owns of mesh_render.hip: the rasteriser's image y runs downwards (pixel row 0 is the top), so its top-left rule
-// reads dy > 0 in its snapped coordinates; here both axes of the plane run upwards and the rule is the perturbation's.
-__device__ __forceinline__ bool mv_owns(int du, int dv) { return dv < 0 || (dv == 0 && du > 0); }
 
 __device__ __forceinline__ int mv_pick(const int4 &q, int axis) { return axis == 0 ? q.x : (axis == 1 ? q.y : q.z); }
 
-// 0: the face is dropped; 1: it is used and contributes nothing along w (projected area 0); 2: it is used, f is set
+// 0: the face is dropped; 1: it is used and contributes nothing along w (projected area 0); 2: it is used, f is set (but for col)
 __device__ __forceinline__ int mv_setup(const int *__restrict__ faces, const int4 *__restrict__ vrec, long long row, long long vbase, long long nv,
                                         int w, MvItem &f) {
   int idx[3];
@@ -103,50 +93,35 @@ __device__ __forceinline__ int mv_setup(const int *__restrict__ faces, const int
   const int u = w == 0 ? 1 : 0, v = w == 2 ? 1 : 2;   // the two other axes in increasing order
   const int au = mv_pick(a, u), av = mv_pick(a, v), aw = mv_pick(a, w);
   const int bu = mv_pick(b, u), bv = mv_pick(b, v), cu = mv_pick(c, u), cv = mv_pick(c, v);
-  const long long area = mv_edge(au, av, bu, bv, cu, cv);
-  if (area == 0) return 1;
+  int2 pb = make_int2(bu, bv), pc = make_int2(cu, cv);
+  if (tri_wind(f.t, make_int2(au, av), pb, pc) == 0) return 1;
   const long long e1x = b.x - a.x, e1y = b.y - a.y, e1z = b.z - a.z, e2x = c.x - a.x, e2y = c.y - a.y, e2z = c.z - a.z;
   const long long nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
   const long long n_u = u == 0 ? nx : ny, n_v = v == 1 ? ny : nz, n_w = w == 0 ? nx : (w == 1 ? ny : nz);   // n_w = +-area, not 0
   const long long first = nx != 0 ? nx : (ny != 0 ? ny : nz);
   const bool neg = n_w < 0;
-  f.au = au, f.av = av;
-  if (area < 0) f.bu = cu, f.bv = cv, f.cu = bu, f.cv = bv;
-  else f.bu = bu, f.bv = bv, f.cu = cu, f.cv = cv;
   f.nu = neg ? -n_u : n_u, f.nv = neg ? -n_v : n_v;
   const long long mag = neg ? -n_w : n_w;
-  f.base = mag * (long long)(MV_SNAP / 2 - aw);
-  f.slope = mag * MV_SNAP;
+  f.base = mag * (long long)(TRI_SNAP / 2 - aw);
+  f.slope = mag * TRI_SNAP;
   f.tie_below = (first < 0) != neg;   // sign(first) sign(n_w) < 0
   return 2;
 }
 
 // the column (iu, iv) of item f: nothing when its centre is not covered, else one XOR of bit c - 1 when c > 0 cells lie below the face.
-// col: the flip words of the item's mesh and axis, [word][iu][iv]: word k of all columns lies together, so that the lanes of the
-// resolve kernel, which run along iv, read neighbouring words.  0 <= iu, iv < r: the box is clamped to the grid.
-__device__ __forceinline__ void mv_column(const MvItem &f, int iu, int iv, int r, int words, unsigned *__restrict__ col) {
-  const long long pu = (long long)MV_SNAP * iu + MV_SNAP / 2, pv = (long long)MV_SNAP * iv + MV_SNAP / 2;
-  const long long e0 = mv_edge(f.bu, f.bv, f.cu, f.cv, pu, pv);
-  const long long e1 = mv_edge(f.cu, f.cv, f.au, f.av, pu, pv);
-  const long long e2 = mv_edge(f.au, f.av, f.bu, f.bv, pu, pv);
-  if (e0 < 0 || e1 < 0 || e2 < 0) return;
-  if (e0 == 0 && !mv_owns(f.cu - f.bu, f.cv - f.bv)) return;
-  if (e1 == 0 && !mv_owns(f.au - f.cu, f.av - f.cv)) return;
-  if (e2 == 0 && !mv_owns(f.bu - f.au, f.bv - f.av)) return;
-  const long long g0 = f.nu * (pu - f.au) + f.nv * (pv - f.av) + f.base;
+// f.col is [word][iu][iv]: word k of all columns lies together, so that the lanes of the resolve kernel, which run along iv, read
+// neighbouring words.  0 <= iu, iv < r: the box is clamped to the grid.
+__device__ __forceinline__ void mv_column(const MvItem &f, int iu, int iv, int r) {
+  long long e0, e1, e2;
+  if (!tri_covers<false>(f.t, iu, iv, e0, e1, e2)) return;   // both axes of the plane run upwards
+  const long long g0 = f.nu * (tri_centre(iu) - f.t.ax) + f.nv * (tri_centre(iv) - f.t.ay) + f.base;
   int lo = 0, hi = r;   // below(k) for k < lo, not below(k) for k >= hi; at most 10 halvings for r <= 512
   for (int step = 0; step < 10 && lo < hi; ++step) {
     const int mid = (lo + hi) >> 1;
     const long long g = g0 + f.slope * mid;
     if (g < 0 || (g == 0 && f.tie_below)) lo = mid + 1; else hi = mid;
   }
-  if (lo > 0) atomicXor(col + ((size_t)((lo - 1) >> 5) * r + iu) * r + iv, 1u << ((lo - 1) & 31));   // lo - 1 < r: a word of the column
-}
-
-// cell centres 256 i + 128 inside [lo, hi] (snapped coordinates), clamped to [0, size): first and last index, first > last = none
-__device__ __forceinline__ void mv_span(int lo, int hi, int size, int &first, int &last) {
-  first = max((lo + (MV_SNAP / 2 - 1)) >> 8, 0);   // ceil((lo - 128) / 256); >> on a negative int is arithmetic
-  last = min((hi - MV_SNAP / 2) >> 8, size - 1);   // floor((hi - 128) / 256)
+  if (lo > 0) atomicXor(f.col + ((size_t)((lo - 1) >> 5) * r + iu) * r + iv, 1u << ((lo - 1) & 31));   // lo - 1 < r: a word of the column
 }
 
 // flips: [b][3][words][r][r], zeroed.  counts[8 m + 0] += faces used, [8 m + 1] += faces dropped.
@@ -156,47 +131,27 @@ __global__ __launch_bounds__(MV_THREADS) void mv_flip_kernel(int r, int words, c
   __shared__ int part[2];
   const int m = blockIdx.y;
   const long long fbase = face_first[m], nf = face_first[m + 1] - fbase;
-  if ((long long)blockIdx.x * MV_THREADS >= 3 * nf) return;   // the whole workgroup
+  if ((long long)blockIdx.x * MV_THREADS >= 3 * nf) return;   // the whole workgroup: no lane may leave alone before the walk below
   const long long vbase = vert_first[m], nv = vert_first[m + 1] - vbase;
   if (threadIdx.x < 2) part[threadIdx.x] = 0;
   __syncthreads();
   const long long t = (long long)blockIdx.x * MV_THREADS + threadIdx.x;
   const int i = (int)(t / 3), w = (int)(t - 3 * (long long)i);   // 3 nf < 2^31
-  unsigned *mesh_flips = flips + (size_t)m * 3 * r * r * words;
-  const size_t axis_words = (size_t)r * r * words;
+  const auto setup = [&](int bi, int bw, MvItem &g) {   // the lane's own face and axis, or broadcast ones
+    g.col = flips + ((size_t)3 * m + bw) * r * r * words;
+    return mv_setup(faces, vrec, fbase + bi, vbase, nv, bw, g);
+  };
   MvItem f;
   int ua = 0, ub = -1, va = 0, vb = -1;
   bool live = i < nf;
   if (live) {
-    const int state = mv_setup(faces, vrec, fbase + i, vbase, nv, w, f);
+    const int state = setup(i, w, f);
     if (w == 0) atomicAdd(part + (state == 0 ? 1 : 0), 1);
-    live = state == 2;
+    live = state == 2 && tri_box(f.t, r, r, ua, ub, va, vb);
   }
-  if (live) {
-    mv_span(min(f.au, min(f.bu, f.cu)), max(f.au, max(f.bu, f.cu)), r, ua, ub);
-    mv_span(min(f.av, min(f.bv, f.cv)), max(f.av, max(f.bv, f.cv)), r, va, vb);
-    live = ua <= ub && va <= vb;
-  }
-  const bool large = live && (ub - ua >= MV_SMALL_BOX || vb - va >= MV_SMALL_BOX);
-  if (live && !large) {
-    unsigned *col = mesh_flips + w * axis_words;
-    for (int iv = va; iv <= vb; ++iv)        // at most 16 x 16 trips
-      for (int iu = ua; iu <= ub; ++iu) mv_column(f, iu, iv, r, words, col);
-  }
-  // the wave's large items, one at a time, all lanes on one box; the set-up is redone from the broadcast item (uniform loads)
-  unsigned long long todo = __ballot(large);
-  const int lane = threadIdx.x & 63;
-  for (int trip = 0; trip < 64 && todo; ++trip) {
-    const int src = __ffsll((long long)todo) - 1;
-    todo &= todo - 1;
-    const int bi = __shfl(i, src), bw = __shfl(w, src);
-    const int bua = __shfl(ua, src), bub = __shfl(ub, src), bva = __shfl(va, src), bvb = __shfl(vb, src);
-    MvItem g;
-    if (mv_setup(faces, vrec, fbase + bi, vbase, nv, bw, g) != 2) continue;   // (it passed once)
-    unsigned *col = mesh_flips + bw * axis_words;
-    const int width = bub - bua + 1, count = width * (bvb - bva + 1);   // <= r r <= 2^18
-    for (int e = lane; e < count; e += 64) mv_column(g, bua + e % width, bva + e / width, r, words, col);
-  }
+  // a large item is set up again from its broadcast face and axis
+  tri_walk_boxes(live, ua, ub, va, vb, f, [&](int src, MvItem &g) { return setup(__shfl(i, src), __shfl(w, src), g) == 2; },
+                 [&](const MvItem &g, int iu, int iv) { mv_column(g, iu, iv, r); });
   __syncthreads();
   if (threadIdx.x < 2 && part[threadIdx.x]) atomicAdd(counts + MV_COUNTS * m + threadIdx.x, part[threadIdx.x]);
 }

@@ -1,5 +1,6 @@
-// ragged.h -- what the operators on packed, ragged batches share on the host side (mesh_render.hip, mesh_metrics.hip, knn.hip,
-// face_point.hip, align.hip, and through mesh_incidence.h mesh_clean.hip and mesh_fill.hip): the checks on
+// ragged.h -- what the operators on packed, ragged batches share on the host side (mesh_metrics.hip, knn.hip, face_point.hip,
+// align.hip, and through mesh_incidence.h mesh_render.hip, mesh_clean.hip, mesh_fill.hip, mesh_decimate.hip, mesh_voxel.hip and
+// mesh_qem.hip): the checks on
 // the host "first row" offset arrays, their upload, the overlap checks of the pointer arguments, the workspace paddings and the
 // carver that lays a workspace out, and the workgroup scan of mesh_metrics.hip and mesh_incidence.h.  The limits on batch sizes and
 // sums differ per operator and stay at the call sites.

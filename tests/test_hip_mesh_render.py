@@ -95,6 +95,95 @@ def test_batch_rows_equal_single_calls_and_calls_repeat(hip):
         _assert_equal(f"mesh {j} alone", _call(alone), {k: whole[k][j:j + 1] for k in OUTPUTS})
 
 
+def _blank_image(want):
+    """The restatement's fragments plus the image of a call without features: zeros where a face shows, the background elsewhere."""
+    return dict(want, image=torch.where((want["pix_to_face"] >= 0)[..., None], torch.zeros(3), torch.tensor(M.BACKGROUND[:3])))
+
+
+def _boxes_16_and_17():
+    """Four right triangles with their vertices ON pixel centres of a 32 x 32 image, legs along the axes: boxes of 16 x 16, 17 x 16,
+    16 x 17 and 17 x 17 pixel centres, wound alternately, each at its own depth (they share pixel column 15 and row 15)."""
+    corners = [((0, 0), (15, 0), (0, 15)), ((31, 0), (15, 0), (31, 15)), ((0, 31), (0, 15), (15, 31)), ((31, 31), (31, 15), (15, 31))]
+    verts = torch.cat([M.on_centres(list(tri), 32, 32, z=0.1 * k) for k, tri in enumerate(corners)])
+    faces = torch.tensor([[0, 1, 2], [3, 5, 4], [6, 8, 7], [9, 10, 11]])
+    return M._case([verts], [faces], M.ortho_pixel_camera(), 32, 32)
+
+
+def _box_sizes(c, mesh=0):
+    """(columns, rows) of pixel centres 256 i + 128 inside each face's bounding box, from the snapped coordinates, clamped to the image."""
+    sx, sy, _, usable = M.project(c["verts"][mesh], c["cams"][mesh], c["H"], c["W"], c["ortho"])
+    assert bool(usable.all())
+    sizes = []
+    for f in c["faces"][mesh]:
+        n = []
+        for s, size in ((sx[f], c["W"]), (sy[f], c["H"])):
+            first, last = max(-((128 - int(s.min())) // 256), 0), min((int(s.max()) - 128) // 256, size - 1)
+            n.append(last - first + 1)
+        sizes.append(tuple(n))
+    return sizes
+
+
+def test_boxes_of_16_centres_are_walked_by_a_lane_and_boxes_of_17_by_the_wave(hip):
+    """The threshold between the two walks of tri_walk_boxes, both kinds in one call; the restatement knows of neither."""
+    c = _boxes_16_and_17()
+    assert _box_sizes(c) == [(16, 16), (17, 16), (16, 17), (17, 17)]
+    want = M.render_batch(c["verts"], c["faces"], c["cams"], 32, 32, True, False)
+    assert sorted(set(want["pix_to_face"].flatten().tolist())) == [-1, 0, 1, 2, 3]
+    for mutant in ("own_never", "own_always"):   # centres lie ON the legs: the tie rule decides pixels here
+        assert not torch.equal(M.render_batch(c["verts"], c["faces"], c["cams"], 32, 32, True, False, mutant=mutant)["pix_to_face"], want["pix_to_face"])
+    _assert_equal("boxes of 16 and 17", _call(c), _blank_image(want))
+
+
+def _two_meshes_with_a_large_face_each():
+    """Two meshes of three small faces and one triangle over the whole 32 x 32 image each: eight packed rows, so both large faces sit
+    in the first wave, with different meshes.  The small faces lie nearer to the camera than the large one of their mesh."""
+    from bdm_amd.cameras import join_cameras
+    small = [[(3, 3), (9, 4), (5, 10)], [(20, 6), (27, 5), (24, 12)], [(8, 20), (15, 22), (10, 28)]]
+    large = [[(-2, -2), (70, -2), (-2, 70)], [(33, 33), (-70, 33), (33, -70)]]
+    verts, faces = [], []
+    for m in range(2):
+        sv = torch.cat([M.on_centres([(i + 2 * m, j + m) for i, j in tri], 32, 32, z=-0.5 + 0.1 * k) for k, tri in enumerate(small)])
+        lv = M.on_centres(large[m], 32, 32)
+        lv[:, 2] = torch.tensor([0.0, 0.3, 0.6]) + 0.05 * m
+        verts.append(torch.cat([sv, lv]))
+        faces.append(torch.tensor([[0, 1, 2], [3, 5, 4], [6, 7, 8], [9, 10, 11] if m == 0 else [9, 11, 10]]))
+    cam = M.ortho_pixel_camera()
+    return M._case(verts, faces, join_cameras([cam, cam]), 32, 32)
+
+
+def test_two_large_faces_of_different_meshes_share_a_wave(hip):
+    """The raster kernel's grid runs over the packed faces, so one wave holds faces of several meshes: what is broadcast for a large
+    face has to carry its mesh."""
+    c = _two_meshes_with_a_large_face_each()
+    assert sum(f.shape[0] for f in c["faces"]) == 8
+    for m in range(2):
+        sizes = _box_sizes(c, m)
+        assert sizes[3] == (32, 32) and all(max(s) <= 16 for s in sizes[:3])
+    want = M.render_batch(c["verts"], c["faces"], c["cams"], 32, 32, True, False)
+    for m in range(2):
+        shown = want["pix_to_face"][m]
+        assert int((shown == 3).sum()) > 900 and int((shown >= 0).sum()) == 1024 and all(int((shown == k).sum()) > 5 for k in range(3))
+    assert not torch.equal(want["zbuf"][0], want["zbuf"][1])
+    whole = _call(c)
+    _assert_equal("two meshes", whole, _blank_image(want))
+    for j in (1, 0):
+        alone = dict(c, verts=c["verts"][j:j + 1], faces=c["faces"][j:j + 1], cams=c["cams"][j:j + 1])
+        _assert_equal(f"mesh {j} alone", _call(alone), {k: whole[k][j:j + 1] for k in OUTPUTS})
+
+
+def test_a_face_with_a_repeated_index_is_no_face(hip):
+    """Faces (0, 1, 1) and (2, 2, 2) around a good face: the good face keeps its index 1 and its pixels, the others show nowhere."""
+    verts = M.on_centres([[2, 8], [13, 8], [7, 2]], 16, 16)
+    faces = torch.tensor([[0, 1, 1], [0, 1, 2], [2, 2, 2]])
+    cam = M.ortho_pixel_camera()
+    trio, alone = M._case([verts], [faces], cam, 16, 16), M._case([verts], [faces[1:2]], cam, 16, 16)
+    got, single = _call(trio), _call(alone)
+    assert int((single["pix_to_face"] == 0).sum()) > 10
+    assert torch.equal(got["pix_to_face"], torch.where(single["pix_to_face"] >= 0, 1, -1).int())
+    _assert_equal("good face alone", got, single, keys=("zbuf", "bary", "image"))
+    _assert_equal("repeated indices", got, _blank_image(M.render_batch(trio["verts"], trio["faces"], trio["cams"], 16, 16, True, False)))
+
+
 @pytest.mark.parametrize("per", ["vert", "face"])
 @pytest.mark.parametrize("channels", [1, 3, 4])
 def test_images_from_features(hip, channels, per):

@@ -143,6 +143,54 @@ def test_a_triangle_across_the_grid_takes_the_wave_path_beside_small_faces(hip):
     assert refs[0]["counts"][6] > 3000 and refs[1]["counts"][6] == 0   # the open triangle is seen differently by the three rays
 
 
+def _box_sizes(v, f, Rs, w):
+    """(columns along u, columns along v) of the centres inside each face's projected bounding box along axis w, clamped to the grid;
+    frame origin 0, cell 1."""
+    q, usable = R.snap(v.numpy(), (0, 0, 0), 1.0)
+    assert bool(usable.all())
+    sizes = []
+    for tri in q[f.numpy()]:
+        spans = [R._span(int(tri[:, k].min()), int(tri[:, k].max()), Rs) for k in R.UV[w]]
+        sizes.append(tuple(int(last) - int(first) + 1 for first, last in spans))
+    return sizes
+
+
+@pytest.mark.parametrize("w", [0, 1, 2])
+def test_boxes_of_16_columns_are_walked_by_a_lane_and_boxes_of_17_by_the_wave(hip, w):
+    """The threshold between the two walks of tri_walk_boxes, both kinds in one call: four right triangles with their corners ON cell
+    centres of a 24^3 grid and their legs along the two axes of the plane of the ray along w, slightly tilted, wound alternately, one
+    above the other.  Their projected boxes are 16 x 16, 17 x 16, 16 x 17 and 17 x 17 columns; the restatement knows of no boxes."""
+    corners = [((0, 0), (15, 0), (0, 15)), ((23, 0), (7, 0), (23, 15)), ((0, 23), (0, 7), (15, 23)), ((23, 23), (23, 7), (7, 23))]
+    a, b = R.UV[w]
+    v = torch.zeros(12, 3)
+    for k, tri in enumerate(corners):
+        for j, (iu, iv) in enumerate(tri):
+            v[3 * k + j, a], v[3 * k + j, b], v[3 * k + j, w] = iu + 0.5, iv + 0.5, 3.3 + 5 * k + 0.2 * j
+    f = torch.tensor([[0, 1, 2], [3, 5, 4], [6, 8, 7], [9, 10, 11]])
+    assert _box_sizes(v, f, 24, w) == [(16, 16), (17, 16), (16, 17), (17, 17)]
+    ref = R.voxelize(v, f, 24, (0, 0, 0), 1.0)
+    assert ref["counts"][0] == 4 and ref["counts"][2 + w] > 1000
+    assert not torch.equal(R.voxelize(v, f, 24, (0, 0, 0), 1.0, mutant="render_owns")["axes"], ref["axes"])   # centres lie ON the legs
+    got = _run(Packed([(v, f)]), 24, "vote", np.zeros((1, 3), dtype=np.float32), np.ones(1, dtype=np.float32))
+    _assert_mesh(got, 0, ref, "vote", f"boxes of 16 and 17 along axis {w}")
+
+
+def test_two_large_faces_in_one_wave_are_taken_in_turn_on_every_axis(hip):
+    """Two triangles across a 32^3 grid among the twelve faces of a lattice box: 14 faces x 3 axes = 42 items, all in the first wave,
+    six of them large, so that the wave's loop over its large items makes several trips with different faces and axes."""
+    bv, bf = R.lattice_box((3, 4, 5), (9, 11, 13))
+    big = torch.tensor([[-3.0, -2.0, 1.3], [35.0, 1.0, 20.2], [2.0, 34.0, 30.9], [30.5, -1.0, 28.2], [-2.0, 33.0, 25.5], [1.0, 0.5, -1.7]])
+    v, f = torch.cat([bv, big]), torch.cat([bf[:6], torch.tensor([[8, 9, 10]]), bf[6:], torch.tensor([[11, 13, 12]])])
+    assert 3 * f.shape[0] <= 64
+    for w in range(3):
+        sizes = _box_sizes(v, f, 32, w)
+        assert all(max(sizes[i]) >= 17 for i in (6, 13)) and all(max(s) <= 16 for i, s in enumerate(sizes) if i not in (6, 13))
+    ref = R.voxelize(v, f, 32, (0, 0, 0), 1.0)
+    assert ref["counts"][0] == 14 and ref["counts"][6] > 1000
+    got = _run(Packed([(v, f)]), 32, "vote", np.zeros((1, 3), dtype=np.float32), np.ones(1, dtype=np.float32))
+    _assert_mesh(got, 0, ref, "vote", "two large faces")
+
+
 def test_a_grid_of_a_million_cells_is_resolved_in_strips(hip):
     """Above 2048 x 256 cells a workgroup of the resolve kernel takes more than one run of 256 cells: at R = 100 a strip is 512 cells,
     1954 workgroups per mesh, the last one with 64 cells.  A closed mesh, an open one and the large triangle."""

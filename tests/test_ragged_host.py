@@ -68,3 +68,22 @@ def test_mesh_workspace_sizes_are_what_they_were(name):
     fn = getattr(L.lib(), f"bdm_mesh_{name}_workspace_bytes")
     nargs = 3 if name in ("adjacency", "fill") else 2
     assert [fn(*row[:nargs]) for row in WORKSPACE_ROWS] == WORKSPACE_BYTES[name]
+
+
+# (b, sum V, sum F, h, w) for the mesh rasteriser, whose workspace is keys (8 b h w bytes, padded to 16), records (16 sum V), offsets:
+# b of 0, 1 and 33, an odd pixel count (the padding), sums either side of multiples of 4, 224 x 224 and 1 x 1, the largest accepted
+# sizes, and from (-1, 10, 10, 16, 16) on the sizes that the operator refuses
+RENDER_WORKSPACE_ROWS = [(0, 0, 0, 1, 1), (0, 7, 9, 224, 224), (1, 0, 0, 1, 1), (1, 3, 1, 1, 1), (1, 3, 5, 224, 224), (1, 4, 3, 224, 224), (1, 5, 4, 3, 3),
+                         (1, 1023, 2047, 5, 7), (33, 0, 0, 1, 1), (33, 4911, 6575, 1, 1), (33, 4912, 6576, 3, 5), (33, 4913, 6577, 224, 224),
+                         (16, 100000, 200000, 224, 224), (1, 2 ** 31 - 1, 2 ** 31 - 1, 4096, 4096), (127, 3, 1, 4096, 4096),
+                         (-1, 10, 10, 16, 16), (1, 2 ** 31, 10, 16, 16), (1, 10, 2 ** 31, 16, 16), (1, -1, 10, 16, 16), (1, 10, -1, 16, 16),
+                         (1, 10, 10, 4097, 16), (1, 10, 10, 16, 4097), (1, 10, 10, 0, 16), (1, 10, 10, 16, 0), (128, 10, 10, 4096, 4096)]
+# The values the library returned before mesh_render.hip laid its workspace out with the carver (commit dfe440f built and asked).
+RENDER_WORKSPACE_BYTES = [16, 128, 48, 96, 401488, 401504, 192, 16688, 816, 79392, 83104, 13325616, 8022800, 34493956112, 17045653552,
+                          0, 0, 0, 0, 0, 0, 0, 0, 0, 0]
+
+
+def test_render_workspace_sizes_are_what_they_were():
+    from bdm_amd import _lib as L
+    fn = L.lib().bdm_render_meshes_workspace_bytes
+    assert [fn(*row) for row in RENDER_WORKSPACE_ROWS] == RENDER_WORKSPACE_BYTES
