@@ -1773,6 +1773,77 @@ int bdm_mesh_qem_finish(int b, int c, const float *attrs, const long long *vert_
  * int32, the keys (3 sum F) uint64 and the selected flags (3 sum F) int32 of the last round.  Returns 1 outside the limits. */
 int bdm_mesh_qem_layout(int b, long long sum_v, long long sum_f, long long *offsets);
 
+/* ------------------------------------------------------------------------------------
+ * 24. Rays against the meshes (csrc/mesh_bvh.hip, csrc/mesh_raycast.hip, csrc/bvh.h): a linear bounding-volume hierarchy over the
+ *     faces of a packed batch, and the closest hit, the occlusion flag and the crossing count of arbitrary rays, with the tree and
+ *     without it.  The rule is this project's own text, restated by tests/mesh_raycast_ref.py.  DESIGN.md section 28.
+ * ---------------------------------------------------------------------------------- */
+/* Meshes: verts, faces, vert_first, face_first exactly as bdm_mesh_adjacency takes them.  Float32 throughout, every operation rounded
+ * on its own in the order written, no contraction, division correctly rounded; fmin / fmax ignore a NaN operand.
+ * 1. Rays: rays (sum R, 8) float32 = origin o (3), direction d (3), tmin, tmax; mesh m owns the rows ray_first[m] .. ray_first[m + 1]
+ *    (b + 1 int64 in HOST memory).  d need not be unit; t is in units of d.  A ray is INVALID when a component of o or d or tmin is
+ *    not finite, d == (0, 0, 0), tmax is NaN or tmin > tmax (tmax = +inf is allowed).  An invalid ray misses everything and is counted.
+ * 2. Faces: a face with an index outside its mesh, a repeated index or a non-finite vertex is DROPPED and counted; every other is USED.
+ * 3. The triangle test (Woop, Benthin, Wald 2013).  kz = the axis of the largest |d| (the lowest on a tie), kx = (kz + 1) % 3,
+ *    ky = (kz + 2) % 3, swapped when d[kz] < 0.  Sx = d[kx] / d[kz], Sy = d[ky] / d[kz], Sz = 1 / d[kz].  For each corner P of
+ *    (a, b, c): p = P - o, Px = p[kx] - Sx * p[kz], Py = p[ky] - Sy * p[kz], Pz = Sz * p[kz].  U = Cx * By - Cy * Bx,
+ *    V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax.  When one of them == 0 all three are taken again in float64 (the products of
+ *    the float32 factors are exact there, the difference is rounded once).  The signs are judged on these values: the face is
+ *    rejected when one is < 0 and another > 0.  Then U, V, W are rounded to float32, det = (U + V) + W, rejected when det == 0;
+ *    t = ((U * Az + V * Bz) + W * Cz) / det, b1 = V / det, b2 = W / det (the weights of corners 1 and 2), back = det < 0 (the ray
+ *    runs along the normal (b - a) x (c - a)).
+ * 4. The face interval.  lo, hi = the float32 min / max of the three corners per axis.  Per axis with inv = 1 / d (the infinity of
+ *    its sign for a zero): d >= +0: tn = (lo - o) * inv, tf = (hi - o) * inv; d <= -0: tn = (hi - o) * inv, tf = (lo - o) * inv.
+ *    tn is then multiplied by 1 - 2^-16 when >= 0 and by 1 + 2^-16 otherwise, tf by 1 + 2^-16 when >= 0 and by 1 - 2^-16
+ *    otherwise.  near = fmax(fmax(fmax(tmin, tn_x), tn_y), tn_z), far = fmin(fmin(fmin(tmax, tf_x), tf_y), tf_z): a NaN (0 times
+ *    infinity: the ray runs in a plane of the box) constrains nothing.  The face is ACCEPTED when it passes rule 3, t is finite and
+ *    near <= t && t <= far.  Every step is monotone in lo and hi, so a box that encloses the face's gives an interval that encloses
+ *    [near, far]: culling by node boxes never changes an answer.
+ * 5. Answers per valid ray.  mode 0 (closest): the accepted face of minimum t, the lowest face index on equal t: t, face (index
+ *    inside its mesh), bary = (b1, b2), back; a miss or an invalid ray gives +inf, -1, (0, 0), 0.  mode 1 (any): occluded = 1 when a face
+ *    is accepted, else 0.  mode 2 (count): crossings = the number of accepted faces.  A ray through a shared edge or vertex is
+ *    accepted by every face that touches it: the count is then higher than the number of crossings of the surface.
+ *
+ * The hierarchy: one binary tree per mesh over its n used faces, in a caller-owned buffer of bdm_mesh_bvh_bytes(b, sum_f) bytes:
+ *   b records of 4 int32 (n, faces dropped, 0, 0), padded to 16 bytes, then 2 sum F nodes of 32 bytes, those of mesh m from node
+ *   2 face_first[m] on.  A node = lo (3 float32), hi (3 float32), link, skip (int32).  Nodes 0 .. n - 2 are internal (link = the left
+ *   child), nodes n - 1 .. 2 n - 2 leaves (link = the face, box = the face's own); node 0 is the root; skip = the node a walk goes
+ *   to when it leaves the subtree, -1 at the end.  A walk "visit node; enter link when its interval is not empty, else go to skip"
+ *   visits every node at most once and needs no stack.  An internal box is the min / max of its children's.
+ *   Build: bdm_mesh_bvh_keys writes one int64 key per face, (m << 32) | (dropped << 30) | the 30-bit Morton code of
+ *   ((a + b) + c) * (1 / 3 as float32) in the box of the mesh's finite vertices, 10 bits per axis: q = fmin(fmax((c - lo) * s, 0), 1023)
+ *   truncated, s = 1024 / (hi - lo), or 0 where hi - lo is not positive and finite.  The caller sorts the keys ascending with a
+ *   STABLE sort (ties keep the face order) and hands the sorted keys and the permutation (int64 packed face rows) to
+ *   bdm_mesh_bvh_build: the tree is the radix tree of (key, position) of Karras 2012, the boxes are fitted bottom-up, one arrival
+ *   counter per internal node.  counts (b, 2) int32: faces used, faces dropped.
+ * bdm_mesh_raycast walks the tree, bdm_mesh_raycast_exhaustive tests every face (staged through LDS): both give the same bits.
+ *   Outputs, each (sum R) rows: t float32, face int32, bary (sum R, 2) float32, back uint8 (mode 0); occluded uint8 (mode 1); crossings
+ *   int32 (mode 2).  Any of them may be NULL and only those of the mode are written.  counts (b, 5) int32, never NULL: valid rays,
+ *   invalid rays, rays with an accepted face, faces used, faces dropped.
+ * Limits: 0 <= b <= 65535, sum V < 2^31, 3 sum F < 2^31, sum R < 2^31, offsets non-decreasing from 0, mode 0 .. 2, no NULL pointer
+ *   other than the per-ray outputs, the workspace and the hierarchy 16-byte aligned, no output and no part of the workspace
+ *   overlapping an input or another output.  b == 0 returns 0 and launches nothing; anything else outside the limits returns 1,
+ *   launches nothing and leaves the outputs untouched; the _bytes functions return 0 outside the limits.
+ * workspace: bdm_mesh_bvh_workspace_bytes(b, sum_v, sum_f) for the two build calls (the offsets, six floats per mesh, 24 bytes per
+ *   face), bdm_mesh_raycast_workspace_bytes(b) for the queries (the offsets); contents irrelevant before each call.
+ * Determinism: min / max of floats and integer adds are the only atomics; no spin-wait, no grid barrier, no loop that waits for
+ *   another workgroup: the first thread to arrive at an internal node leaves, the second fits it.  The walk of a ray ends after at
+ *   most 2 n nodes whatever the buffer holds, and a link outside the mesh ends it.  Mesh j of a batch has the bits of that mesh
+ *   alone, and so has a repeated call. */
+size_t bdm_mesh_bvh_bytes(int b, long long sum_f);
+size_t bdm_mesh_bvh_workspace_bytes(int b, long long sum_v, long long sum_f);
+int bdm_mesh_bvh_keys(int b, const float *verts, const int *faces, const long long *vert_first, const long long *face_first, long long *keys,
+                      void *workspace, void *stream);
+int bdm_mesh_bvh_build(int b, const float *verts, const int *faces, const long long *vert_first, const long long *face_first,
+                       const long long *keys, const long long *order, int *counts, void *bvh, void *workspace, void *stream);
+size_t bdm_mesh_raycast_workspace_bytes(int b);
+int bdm_mesh_raycast(int mode, int b, const float *verts, const int *faces, const long long *vert_first, const long long *face_first,
+                     const void *bvh, const float *rays, const long long *ray_first, float *t, int *face, float *bary, unsigned char *back,
+                     unsigned char *occluded, int *crossings, int *counts, void *workspace, void *stream);
+int bdm_mesh_raycast_exhaustive(int mode, int b, const float *verts, const int *faces, const long long *vert_first,
+                                const long long *face_first, const float *rays, const long long *ray_first, float *t, int *face, float *bary,
+                                unsigned char *back, unsigned char *occluded, int *crossings, int *counts, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
